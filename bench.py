@@ -14,7 +14,11 @@ kernels), the softmax / entropy MC epilogue, and -- for N > 1 -- the one packed 
 HBM before the timed region. scaling: "weak" = S samples per rank (cfg3's default; the job does N*S per step), "strong" = a fixed
 global sample count sharded over the ranks with mc_dist.shard (cfg5's default: 128 samples over the node).
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the K steps and prints the line; the legs below run only
+with --full (each can still be dropped there with its --no-* option; without --full they are null or absent in the line).
+  --dump-outputs DIR  after the timed steps, what the last timed step computed (mean_prob [B, C], mean_entropy [B], mean_logits
+                [B, C], kl []; --train: loss []) as DIR/<name>.npy in float32. Inputs, parameters and draw coordinates are seeded:
+                the same arguments give the same inputs on every run, so two builds can be compared output for output.
   roofline      a second pass of the same K steps with a HIP-event pair around every fused launch (events on the launch stream).
                 The headline fields describe the DOMINANT kernel instance against the pipe it issues on: the split kernels run on
                 the bf16 matrix pipe (2.5 PFLOP/s dense), `achieved` = 6 x executed fp32-equivalent FLOPs (the six piece products)
@@ -85,18 +89,36 @@ def parse_args(argv=None):
     ap.add_argument("--samples", type=int, default=0, help="MC samples per GPU per step (weak) / in total (strong); default: the workload's")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="weak: S samples per rank; strong: a fixed global sample count sharded over the ranks (mc_dist.shard). Default: cfg5 strong, the rest weak")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_with_pack_rebuild and eager_caller_loop")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two child rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs: roofline pass (+ its traffic passes), extras, parity and CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass (and the traffic passes)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_with_pack_rebuild and eager_caller_loop")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the two child rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying a captured HIP graph")
     ap.add_argument("--no-fuse", action="store_true", help="keep BatchNorm/ReLU/add as separate torch modules")
-    ap.add_argument("--layers-json", default="", help="write the per-layer roofline table here")
+    ap.add_argument("--layers-json", default="", help="with --full: write the per-layer roofline table here")
     ap.add_argument("--train", action="store_true", help="secondary line: one TRAINING step per MC sample (forward + KL + HIP backward + SGD step, S = 1, BatchNorm in train mode)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launcher / rendezvous / sharding / collective rehearsal WITHOUT any kernel (runs on CPU-only hosts under BT_DIST_BACKEND=gloo): prints a line with value null")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.layers_json and not (args.full and not args.no_roofline):
+        ap.error("--layers-json is the roofline pass's table: it needs --full (and no --no-roofline)")
+    if not args.full:          # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_roofline = args.no_parity = args.no_extras = args.no_traffic = True
+    return args
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, as d/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v.detach().float().cpu().numpy())
 
 
 # ======================================================================================================== multi-rank launcher
@@ -543,6 +565,8 @@ def train_bench(args, w, dev, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     assert torch.isfinite(loss)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(loss=loss))
     if rank == 0:
         print(json.dumps(dict(metric="training MC-samples/sec (forward+KL+backward+SGD step, 1 MC sample per step), " + w["desc"],
                               value=round(world * args.steps / dt, 2), unit="MC-samples/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -673,6 +697,8 @@ def main(argv=None):
     dt, buf = timed(step, args.warmup, args.steps)
     res = mc_dist.unpack(buf, B, (buf.numel() - 1 - B) // (2 * B), S_total)
     assert torch.isfinite(res["kl"]).all()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
 
     # ---- roofline pass: same steps, an event pair around every fused-forward launch --------------------------
     roof = None

@@ -45,6 +45,22 @@ def test_launcher_refuses_more_ranks_than_gpus_without_touching_one():
     assert p.returncode == 2 and b"visible GPUs" in p.stderr
 
 
+def test_plain_run_is_lean_and_full_brings_the_legs_back():
+    """`bench.py --steps K --warmup W` times the steps and prints the line; roofline, traffic, extras, parity and the CPU baseline
+    run only under --full, where each --no-* option still drops its leg."""
+    import pytest
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs == ""
+    assert a.no_roofline and a.no_traffic and a.no_extras and a.no_parity and a.no_cpu_baseline
+    f = bench.parse_args(["--full", "--no-parity", "--dump-outputs", "out"])
+    assert f.full and f.no_parity and f.dump_outputs == "out"
+    assert not (f.no_roofline or f.no_traffic or f.no_extras or f.no_cpu_baseline)
+    for bad in (["--layers-json", "l.json"], ["--full", "--no-roofline", "--layers-json", "l.json"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_a_failing_rank_fails_the_launch():
     # strong scaling with fewer samples than ranks is refused by every rank (before any collective): the parent must exit non-zero
     p = _run(["--gpus", "2", "--scaling", "strong", "--samples", "1", "--no-traffic"], env={"BT_DIST_BACKEND": "gloo"}, timeout=600)

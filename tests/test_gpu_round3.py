@@ -348,6 +348,38 @@ def test_bench_bare_command_launches_two_ranks_on_one_gpu():
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["global_samples_per_step"] == 16 and d["value"] > 0
 
 
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py` run times the steps and nothing else; --dump-outputs writes the last timed step's outputs, and two runs
+    with the same arguments (seeded inputs, parameters and draw coordinates) write the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "cfg2", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        rows = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(rows) == 1, p.stdout.decode()[:500]
+        line = json.loads(rows[0])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+        assert line["roofline"] is None and line["parity"] is None and line["cpu_baseline"] is None and "eager_caller_loop" not in line
+        got.append({k: np.load(d / (k + ".npy")) for k in ("mean_prob", "mean_entropy", "mean_logits", "kl")})
+    a, b = got
+    assert a["mean_prob"].shape == (256, 10) and a["mean_entropy"].shape == (256,) and a["mean_logits"].shape == (256, 10) and a["kl"].shape == ()
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert np.allclose(a["mean_prob"].sum(1), 1.0, atol=1e-5)
+    for k in a:
+        assert np.allclose(a[k], b[k], rtol=1e-6, atol=1e-6 * float(np.abs(b[k]).max())), k
+
+
 # ------------------------------------------------------------------------------------------------ the split-K ("skinny") kernel
 # kind, Ci, Co, k, stride, pad, dil, groups, H, B, S, bias, extras
 SKINNY = {   # (kind, Ci, Co, k, stride, pad, dil, groups, H, B, S, bias, extras) -- at most 8 workgroups per sample (launch_skinny's gate)

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 tag=${1:-r01}
 wl=${2:-cfg3}
 steps=${3:-10}
-args="--workload $wl --steps $steps --warmup 2 --no-cpu-baseline --no-traffic --no-extras --no-parity"
+args="--full --workload $wl --steps $steps --warmup 2 --no-cpu-baseline --no-traffic --no-extras --no-parity"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_stats -- python bench.py $args > gpurun_out/prof_${tag}_stats.log 2>&1
 # PMC passes are separate runs with nothing but the counters (FETCH_SIZE and WRITE_SIZE do not fit one pass)
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof_${tag}_fetch -- python bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-traffic --no-extras --no-parity > gpurun_out/prof_${tag}_fetch.log 2>&1
