@@ -46,6 +46,11 @@ class bt_pack_seg(C.Structure):
         + [("Co", C.c_int64), ("Ci", C.c_int64), ("taps", C.c_int64), ("force", C.c_int32), ("reserved", C.c_int32)]
 
 
+class bt_pack_kl(C.Structure):
+    _fields_ = [(n, _vp) for n in ("prior_mu_w", "prior_sigma_w", "mu_b", "rho_b", "prior_mu_b", "prior_sigma_b", "kl_out")] \
+        + [("n_bias", C.c_int64)]
+
+
 class bt_conv2d_geom(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "Ci", "H", "W", "Co", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "groups")]
 
@@ -77,6 +82,7 @@ _PROTOS = {
     "bt_kl_normal": (C.c_int, [C.c_int32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64),
                                C.POINTER(C.c_int32), C.c_uint32, _vp, _vp, C.c_size_t, _vp]),
     "bt_pack_sync": (C.c_int, [C.c_int32, C.POINTER(bt_pack_seg), _vp, C.c_size_t, _vp]),
+    "bt_pack_sync_kl": (C.c_int, [C.c_int32, C.POINTER(bt_pack_seg), C.POINTER(bt_pack_kl), _vp, C.c_size_t, _vp]),
     "bt_pack_params": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "bt_rng_normal_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "bt_rng_sign_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, _vp, _vp]),

@@ -9,6 +9,10 @@
 // layer's fingerprint with the one stored when its pack was last built. Launch 2 rebuilds the packs of exactly the layers that
 // differ (its blocks return at once for the others). Nothing comes back to the host, so both launches sit inside a captured
 // HIP graph like any other kernel: a replay follows parameter updates.
+//
+// bt_pack_sync_kl: launch 1 also reads the priors of the layers that ask for it and produces their KL terms (the fused forwards'
+// closed form and per-element order; one double partial per block, summed in block order by the last block: deterministic).
+// The forwards of those layers then run without a KL sweep of their own: 8 B/weight read here instead of 16 B/weight there.
 #include "bt_api_internal.h"
 
 namespace bt {
@@ -28,6 +32,27 @@ struct PackSegs {
   int nseg;
 };
 
+// The fingerprint launch's own argument block (what it reads; the pack geometry stays with pack_dirty_kernel's PackSegs).
+struct FpSegs {
+  const float* mu[BT_PACK_MAX_SEGMENTS];
+  const float* rho[BT_PACK_MAX_SEGMENTS];
+  unsigned long long* state[BT_PACK_MAX_SEGMENTS];
+  long long n[BT_PACK_MAX_SEGMENTS];
+  // KL (bt_pack_sync_kl): kl_out[i] == nullptr -> segment i produces none
+  const float* pmu[BT_PACK_MAX_SEGMENTS];
+  const float* psig[BT_PACK_MAX_SEGMENTS];
+  const float* mu_b[BT_PACK_MAX_SEGMENTS];
+  const float* rho_b[BT_PACK_MAX_SEGMENTS];
+  const float* pmu_b[BT_PACK_MAX_SEGMENTS];
+  const float* psig_b[BT_PACK_MAX_SEGMENTS];
+  float* kl_out[BT_PACK_MAX_SEGMENTS];
+  int n_bias[BT_PACK_MAX_SEGMENTS];
+  int first_block[BT_PACK_MAX_SEGMENTS + 1];
+  unsigned long long force;
+  int nseg;
+  int any_kl;
+};
+
 constexpr int kFpThreads = 256;
 constexpr int kFpElemsPerBlock = kFpThreads * 4 * 4;
 
@@ -39,23 +64,34 @@ __device__ __forceinline__ unsigned long long fp_mix(unsigned long long i, float
   return h;
 }
 
-__global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(PackSegs sg, unsigned* counter, int total_blocks) {
-  __shared__ int is_last;
-  int seg = 0;
-  while (seg + 1 < sg.nseg && (int)blockIdx.x >= sg.first_block[seg + 1]) ++seg;
-  const int nb = sg.first_block[seg + 1] - sg.first_block[seg], lb = blockIdx.x - sg.first_block[seg];
+// One element's KL term, as the fused forwards' sweep forms it (bt_fused_split.h, kl_terms): the four terms of an aligned quad are
+// added in fp32 in pairs, and the pairs go into the double accumulator.
+__device__ __forceinline__ double kl_quad(const float4& m, const float4& r, const float4& p, const float4& q) {
+  const float t0 = kl_term(m.x, softplus(r.x), p.x, q.x) + kl_term(m.y, softplus(r.y), p.y, q.y);
+  const float t1 = kl_term(m.z, softplus(r.z), p.z, q.z) + kl_term(m.w, softplus(r.w), p.w, q.w);
+  return (double)t0 + (double)t1;
+}
+
+template <bool KL>
+__device__ __forceinline__ void fp_sweep(const FpSegs& sg, int seg, int nb, int lb, unsigned long long& acc, double& kacc) {
   const long long n = sg.n[seg];
   const float* __restrict__ mu = sg.mu[seg];
   const float* __restrict__ rho = sg.rho[seg];
-  const bool vec_ok = ((((uintptr_t)mu | (uintptr_t)rho) & 15u) == 0);
-  unsigned long long acc = 0ull;
+  const float* __restrict__ pm = sg.pmu[seg];
+  const float* __restrict__ ps = sg.psig[seg];
+  uintptr_t align = (uintptr_t)mu | (uintptr_t)rho;
+  if (KL) align |= (uintptr_t)pm | (uintptr_t)ps;
+  const bool vec_ok = (align & 15u) == 0;
   const long long n4 = vec_ok ? (n >> 2) : 0;
   for (long long base = (long long)lb * (kFpThreads * 4); base < n4; base += (long long)nb * (kFpThreads * 4)) {
-    float4 m[4], r[4];
+    float4 m[4], r[4], p[4], q[4];
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       const long long i = base + v * kFpThreads + threadIdx.x;
-      if (i < n4) m[v] = reinterpret_cast<const float4*>(mu)[i], r[v] = reinterpret_cast<const float4*>(rho)[i];
+      if (i < n4) {
+        m[v] = reinterpret_cast<const float4*>(mu)[i], r[v] = reinterpret_cast<const float4*>(rho)[i];
+        if (KL) p[v] = reinterpret_cast<const float4*>(pm)[i], q[v] = reinterpret_cast<const float4*>(ps)[i];
+      }
     }
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
@@ -63,18 +99,46 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(PackSegs s
       if (i < n4) {
         const unsigned long long e = (unsigned long long)i * 4ull;
         acc += fp_mix(e, m[v].x, r[v].x) + fp_mix(e + 1, m[v].y, r[v].y) + fp_mix(e + 2, m[v].z, r[v].z) + fp_mix(e + 3, m[v].w, r[v].w);
+        if (KL) kacc += kl_quad(m[v], r[v], p[v], q[v]);
       }
     }
   }
-  for (long long i = (n4 << 2) + (long long)lb * kFpThreads + threadIdx.x; i < n; i += (long long)nb * kFpThreads) acc += fp_mix((unsigned long long)i, mu[i], rho[i]);
+  for (long long i = (n4 << 2) + (long long)lb * kFpThreads + threadIdx.x; i < n; i += (long long)nb * kFpThreads) {
+    const float mi = mu[i], ri = rho[i];
+    acc += fp_mix((unsigned long long)i, mi, ri);
+    if (KL) kacc += (double)kl_term(mi, softplus(ri), pm[i], ps[i]);
+  }
+}
+
+__global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg, unsigned* counter, double* slots, int total_blocks) {
+  __shared__ int is_last;
+  __shared__ double kred[kFpThreads / 64];
+  int seg = 0;
+  while (seg + 1 < sg.nseg && (int)blockIdx.x >= sg.first_block[seg + 1]) ++seg;
+  const int nb = sg.first_block[seg + 1] - sg.first_block[seg], lb = blockIdx.x - sg.first_block[seg];
+  const bool kl = sg.kl_out[seg] != nullptr;
+  unsigned long long acc = 0ull;
+  double kacc = 0.0;
+  if (kl) fp_sweep<true>(sg, seg, nb, lb, acc, kacc);
+  else fp_sweep<false>(sg, seg, nb, lb, acc, kacc);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   // One agent-scope add per wave (performed at L2), drained before the block's ticket: the last arriver's agent-scope loads see
   // every add (MI355X_MICROARCH.md "Valid forms": all handed-off words written and read with agent-scope atomics).
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(&sg.state[seg][0], acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (kl) {
+    kacc = wave_sum(kacc);
+    if ((threadIdx.x & 63) == 0) kred[threadIdx.x >> 6] = kacc;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x == 0) is_last = (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)total_blocks - 1u) ? 1 : 0;
+  if (threadIdx.x == 0) {
+    if (kl) {   // the block's KL partial, stored write-through (agent scope) and drained before the ticket: the same hand-off as the adds
+      __hip_atomic_store(&slots[blockIdx.x], (kred[0] + kred[1]) + (kred[2] + kred[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    is_last = (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)total_blocks - 1u) ? 1 : 0;
+  }
   __syncthreads();
   if (!is_last) return;
   if ((int)threadIdx.x < sg.nseg) {
@@ -88,6 +152,25 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(PackSegs s
     __hip_atomic_store(&st[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // accumulator left zeroed for the next call
   }
   if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!sg.any_kl) return;
+  // KL finish: one wave per segment, the block partials in block order (fixed lane split + fixed butterfly: deterministic)
+  const int lane = threadIdx.x & 63;
+  for (int s = threadIdx.x >> 6; s < sg.nseg; s += kFpThreads / 64) {
+    if (sg.kl_out[s] == nullptr) continue;
+    double t = 0.0;
+    for (int b = sg.first_block[s] + lane; b < sg.first_block[s + 1]; b += 64) t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = wave_sum(t);
+    double bt_ = 0.0;
+    const float *mb = sg.mu_b[s], *rb = sg.rho_b[s], *pb = sg.pmu_b[s], *qb = sg.psig_b[s];
+    if (mb)
+      for (int c = lane; c < sg.n_bias[s]; c += 64) bt_ += (double)kl_term(mb[c], softplus(rb[c]), pb[c], qb[c]);
+    bt_ = wave_sum(bt_);
+    if (lane == 0) {
+      float v = (float)(t / (double)sg.n[s]);
+      if (mb) v += (float)(bt_ / (double)sg.n_bias[s]);
+      sg.kl_out[s][0] = v;
+    }
+  }
 }
 
 // packed[(co*T + t)*C4 + c] <- natural[co][c][t] for the segments marked dirty (the layout of bt_pack_params). A work item is (row co,
@@ -132,14 +215,29 @@ __global__ __launch_bounds__(256) void pack_dirty_kernel(PackSegs sg) {
 
 }  // namespace bt
 
-extern "C" int bt_pack_sync(int32_t n_segments, const bt_pack_seg* segs, void* workspace, size_t workspace_bytes, bt_stream_t stream) {
+extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, const bt_pack_kl* kls, void* workspace, size_t workspace_bytes,
+                               bt_stream_t stream) {
   using namespace bt;
   if (n_segments <= 0 || n_segments > BT_PACK_MAX_SEGMENTS) return set_error(BT_ERR_BAD_ARG, "bt_pack_sync: n_segments must be in [1, 64]");
   if (!segs) return set_error(BT_ERR_BAD_ARG, "bt_pack_sync: null argument");
   if (!workspace || workspace_bytes < BT_WORKSPACE_BYTES) return set_error(BT_ERR_WORKSPACE, "bt_pack_sync: workspace smaller than BT_WORKSPACE_BYTES");
+  FpSegs fs = {};
   PackSegs fp, pk;
   int fblocks = 0, pblocks = 0;
   fp.force = 0ull;
+  for (int i = 0; i < n_segments; ++i) {
+    const bt_pack_kl* k = kls ? &kls[i] : nullptr;
+    if (!k || !k->kl_out) continue;
+    if (!k->prior_mu_w || !k->prior_sigma_w) return set_error(BT_ERR_BAD_ARG, "bt_pack_sync_kl: kl_out given but weight priors are NULL");
+    const bool b = k->mu_b != nullptr;
+    if (b != (k->rho_b != nullptr) || b != (k->prior_mu_b != nullptr) || b != (k->prior_sigma_b != nullptr))
+      return set_error(BT_ERR_BAD_ARG, "bt_pack_sync_kl: give all four bias tensors or none");
+    if (b && (k->n_bias <= 0 || k->n_bias >= (1ll << 30))) return set_error(BT_ERR_BAD_ARG, "bt_pack_sync_kl: bad n_bias");
+    fs.pmu[i] = k->prior_mu_w, fs.psig[i] = k->prior_sigma_w, fs.kl_out[i] = k->kl_out;
+    fs.mu_b[i] = k->mu_b, fs.rho_b[i] = k->rho_b, fs.pmu_b[i] = k->prior_mu_b, fs.psig_b[i] = k->prior_sigma_b;
+    fs.n_bias[i] = b ? (int)k->n_bias : 0;
+    fs.any_kl = 1;
+  }
   for (int i = 0; i < n_segments; ++i) {
     const bt_pack_seg& s = segs[i];
     if (!s.mu_w || !s.rho_w || !s.mu_packed || !s.sigma_packed || !s.state || s.Co <= 0 || s.Ci <= 0 || s.taps <= 0)
@@ -159,6 +257,7 @@ extern "C" int bt_pack_sync(int32_t n_segments, const bt_pack_seg* segs, void* w
     const bt_pack_seg& s_ = segs[i];
     long long nb = (fp.n[i] + kFpElemsPerBlock - 1) / kFpElemsPerBlock;
     if (nb > 128) nb = 128;   // (more blocks are slower: every wave ends in one 64-bit atomic on the segment's accumulator -- 1024 blocks: 14 -> 25 us for 1.5 M weights)
+    if (fs.any_kl && nb > kMaxSlots / n_segments) nb = kMaxSlots / n_segments;   // one KL slot per block in the workspace
     fp.first_block[i] = fblocks, fblocks += (int)nb;
     const long long C4 = (s_.Ci + 3) & ~3ll;
     long long pb = s_.Co * ((C4 + kPackCh - 1) / kPackCh);   // (row, 64-channel chunk) work items
@@ -168,7 +267,9 @@ extern "C" int bt_pack_sync(int32_t n_segments, const bt_pack_seg* segs, void* w
   }
   fp.first_block[n_segments] = fblocks, pk.first_block[n_segments] = pblocks;
   fp.nseg = pk.nseg = n_segments;
-  hipLaunchKernelGGL(pack_fingerprint_kernel, dim3(fblocks), dim3(kFpThreads), 0, (hipStream_t)stream, fp, ws_counter(workspace), fblocks);
+  for (int i = 0; i < n_segments; ++i) fs.mu[i] = fp.mu[i], fs.rho[i] = fp.rho[i], fs.state[i] = fp.state[i], fs.n[i] = fp.n[i], fs.first_block[i] = fp.first_block[i];
+  fs.first_block[n_segments] = fblocks, fs.force = fp.force, fs.nseg = n_segments;
+  hipLaunchKernelGGL(pack_fingerprint_kernel, dim3(fblocks), dim3(kFpThreads), 0, (hipStream_t)stream, fs, ws_counter(workspace), ws_slots(workspace), fblocks);
   if (int rc = check_launch("bt_pack_sync (fingerprint)")) return rc;
   const size_t lds = (size_t)max_taps * (kPackCh + 1) * sizeof(float2);
   if (max_taps > 128) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_sync: kernels larger than 128 taps are not supported");
@@ -184,4 +285,8 @@ extern "C" int bt_pack_sync(int32_t n_segments, const bt_pack_seg* segs, void* w
   }
   hipLaunchKernelGGL(pack_dirty_kernel, dim3(pblocks), dim3(256), lds, (hipStream_t)stream, pk);
   return check_launch("bt_pack_sync (pack)");
+}
+
+extern "C" int bt_pack_sync(int32_t n_segments, const bt_pack_seg* segs, void* workspace, size_t workspace_bytes, bt_stream_t stream) {
+  return bt_pack_sync_kl(n_segments, segs, nullptr, workspace, workspace_bytes, stream);
 }

@@ -182,23 +182,46 @@ def pack_buffers(Co, Ci, taps, device):
     return mp, torch.empty_like(mp), torch.zeros(4, dtype=torch.int64, device=device)
 
 
-def pack_sync(segments, owner="pack"):
+def _kl_entry(kl):
+    """kl = (prior_mu_w, prior_sigma_w, mu_b|None, rho_b|None, prior_mu_b|None, prior_sigma_b|None, kl_out) -> (bt_pack_kl, tensors kept)."""
+    pm, ps = _lib.dev_f32(kl[0], "prior_mu_w"), _lib.dev_f32(kl[1], "prior_sigma_w")
+    b = [None if t is None else _lib.dev_f32(t.detach(), "bias") for t in kl[2:6]]
+    out = kl[6]
+    n_bias = 0 if b[0] is None else b[0].numel()
+    if any((t is None) != (b[0] is None) or (t is not None and t.numel() != n_bias) for t in b):
+        raise RuntimeError("pack_sync: give all four bias tensors of a layer's KL, of one size, or none")
+    return _lib.bt_pack_kl(pm.data_ptr(), ps.data_ptr(), *[_lib.ptr(t) for t in b], out.data_ptr(), n_bias), (pm, ps, b, out)
+
+
+def pack_sync(segments, owner="pack", kls=None):
     """segments: list of dict(mu, rho, src_mu|None, src_rho|None, mu_packed, sigma_packed, state, Co, Ci, taps, force) on ONE device.
     Re-packs, ON THE DEVICE and in the current stream, exactly the layers whose (mu, rho) no longer match the fingerprint their pack
-    was built from (bt_pack_sync: two launches per 64 layers, no host synchronisation, graph-capturable)."""
+    was built from (bt_pack_sync: two launches per 64 layers, no host synchronisation, graph-capturable).
+    kls: None, or one entry per segment -- None or (prior_mu_w, prior_sigma_w, mu_b, rho_b, prior_mu_b, prior_sigma_b, kl_out): the
+    sweep then also writes that layer's KL term ('normal' prior) into the 0-dim fp32 device tensor kl_out (bt_pack_sync_kl), and the
+    layer's forward can go without its own KL sweep."""
     if not segments:
         return
     L = _lib.lib()
     dev = segments[0]["mu"].device
+    if kls is not None and all(k is None for k in kls):
+        kls = None
     if len(segments) == 1 and "_c" in segments[0]:      # a layer checking itself again: its marshalled entry is still valid (same tensors, same buffers)
         arr = segments[0]["_c"][0]
         arr[0].force = 1 if segments[0].get("force") else 0
         with _lib.on(dev):
-            _lib.check(L.bt_pack_sync(1, arr, _lib.workspace((owner, "pack"), dev).data_ptr(), _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+            ws = _lib.workspace((owner, "pack"), dev).data_ptr()
+            if kls is None:
+                _lib.check(L.bt_pack_sync(1, arr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+            else:
+                karr = (_lib.bt_pack_kl * 1)(_kl_entry(kls[0])[0])
+                _lib.check(L.bt_pack_sync_kl(1, arr, karr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
         return
     for c0 in range(0, len(segments), _lib.PACK_MAX_SEGMENTS):
         chunk = segments[c0:c0 + _lib.PACK_MAX_SEGMENTS]
+        kchunk = None if kls is None else kls[c0:c0 + _lib.PACK_MAX_SEGMENTS]
         arr = (_lib.bt_pack_seg * len(chunk))()
+        karr = None if kchunk is None else (_lib.bt_pack_kl * len(chunk))()
         keep = []
         for i, sg in enumerate(chunk):
             mu, rho = _lib.dev_f32(sg["mu"], "mu_w"), _lib.dev_f32(sg["rho"], "rho_w")
@@ -212,10 +235,19 @@ def pack_sync(segments, owner="pack"):
                 raise RuntimeError("pack_sync: geometry does not match the parameter tensors")
             arr[i] = _lib.bt_pack_seg(mu.data_ptr(), rho.data_ptr(), _lib.ptr(smu), _lib.ptr(srho), sg["mu_packed"].data_ptr(), sg["sigma_packed"].data_ptr(),
                                       sg["state"].data_ptr(), sg["Co"], sg["Ci"], sg["taps"], 1 if sg.get("force") else 0, 0)
+            if kchunk is not None and kchunk[i] is not None:
+                if kchunk[i][0].numel() != mu.numel():
+                    raise RuntimeError("pack_sync: the weight priors do not have mu_w's size")
+                karr[i], kept = _kl_entry(kchunk[i])
+                keep.append(kept)
         if len(segments) == 1:
-            segments[0]["_c"] = (arr, keep)
+            segments[0]["_c"] = (arr, keep[:1])
         with _lib.on(dev):
-            _lib.check(L.bt_pack_sync(len(chunk), arr, _lib.workspace((owner, "pack"), dev).data_ptr(), _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+            ws = _lib.workspace((owner, "pack"), dev).data_ptr()
+            if karr is None:
+                _lib.check(L.bt_pack_sync(len(chunk), arr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+            else:
+                _lib.check(L.bt_pack_sync_kl(len(chunk), arr, karr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
 
 
 def mc_epilogue(logits):

@@ -35,6 +35,7 @@ def _tup(v, n):
 class FamilyConvLayer(FusedBayesLayer):
     _kind, _wname = "conv", "kernel"
     _nd, _transposed = 2, False
+    _sync_kl = False     # (forward() takes the KL from kl_loss())
 
     def _setup(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, output_padding, prior_mean, prior_variance,
                posterior_mu_init, posterior_rho_init, bias, tuple_inits):

@@ -24,6 +24,7 @@ _warned = [False]
 
 import os as _os
 _NO_SEG_CACHE = bool(_os.environ.get("BT_NO_SEG_CACHE"))   # A/B knob of the eager path's host time (tools/profile_eager.py)
+BT_FUSED_KL = bool(_os.environ.get("BT_FUSED_KL"))         # A/B knob: inference forwards sweep their own KL instead of the pack check
 
 
 class FusedBayesLayer(BaseVariationalLayer_):
@@ -181,18 +182,33 @@ class FusedBayesLayer(BaseVariationalLayer_):
         self._seg_cache = (self._pack, (pm.data_ptr(), pr.data_ptr(), pm.device), sg) if same else None
         return sg
 
+    _sync_kl = True      # the pack check may produce this layer's KL term (the family layers take theirs from kl_loss())
+
+    def _sync_kl_entry(self):
+        """This layer's KL request to bt_pack_sync_kl, with a fresh 0-dim result tensor, or None when the sweep cannot produce it
+        (the closed form there is the 'normal' prior's)."""
+        if not self._sync_kl or self._prior_kind() != "normal":
+            return None
+        out = torch.empty((), dtype=torch.float32, device=self._w("mu").device)
+        return (self.prior_weight_mu, self.prior_weight_sigma, self.mu_bias, self.rho_bias, self.prior_bias_mu, self.prior_bias_sigma, out)
+
     def _packed(self):
-        """(mu_packed, sigma_packed): tap-major copies of (mu, softplus(rho)) for the fast kernels, verified against the
+        return self._packed_kl(False)[:2]
+
+    def _packed_kl(self, want_kl):
+        """(mu_packed, sigma_packed, kl): tap-major copies of (mu, softplus(rho)) for the fast kernels, verified against the
         parameters on the device before EVERY forward (bt_pack_sync: a fingerprint sweep of (mu, rho) + a rebuild of the
         packs that differ, both in the stream). ``mc_forward`` / ``McGraph`` / ``TrainGraph`` run the check once per model
-        (``mc.sync_model_packs``); a layer called on its own checks itself."""
+        (``mc.sync_model_packs``); a layer called on its own checks itself. ``kl``: this layer's KL term when the check produced
+        it (``want_kl`` or the context asked for it; 'normal' priors), else None -- the forward then sweeps it itself."""
         ctx = mc.current()
         if ctx is not None and id(self) in ctx.synced and self._pack is not None and not self._pack_force:
             if id(self) in ctx.late:
                 mc.join_packs(ctx)      # this layer's pack was verified on the side stream: the launch stream waits for it (once)
-            return self._pack[1], self._pack[2]
-        F.pack_sync([self._pack_segment()], owner=("layer", self._ws_id))
-        return self._pack[1], self._pack[2]
+            return self._pack[1], self._pack[2], (ctx.sync_kl.pop(id(self), None) if want_kl else None)
+        kl = self._sync_kl_entry() if want_kl else None
+        F.pack_sync([self._pack_segment()], owner=("layer", self._ws_id), kls=None if kl is None else [kl])
+        return self._pack[1], self._pack[2], None if kl is None else kl[-1]
 
     def pack_rebuilds(self):
         """How many times this layer's pack has been (re)built -- a device counter kept by bt_pack_sync (synchronises)."""
@@ -267,6 +283,7 @@ class FusedBayesLayer(BaseVariationalLayer_):
             draw = self._draw_torch(x, S, B, conv) if rng.get_mode() == "torch" else {}
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self._w("mu").requires_grad or self._w("rho").requires_grad
                                                   or (self.mu_bias is not None and self.mu_bias.requires_grad))
+        fwd_kl = want_kl      # the forward kernel sweeps the KL term itself
         if needs_grad:
             # training path: same fused forward kernel, gradients through the autograd bridge (autograd.py)
             if self.post_scale is not None or residual is not None or self.post_relu or self.post_pool:
@@ -293,20 +310,26 @@ class FusedBayesLayer(BaseVariationalLayer_):
                     flat = [t for sg in self._kl_segments() for t in sg]
                     kl = KLNormal.apply((("layer", self._ws_id), kind), *flat)
         else:
-            priors = (self.prior_weight_mu, self.prior_weight_sigma, self.prior_bias_mu, self.prior_bias_sigma) if want_kl else None
+            # the pack check ahead of the forward sweeps (mu, rho) anyway: when it also produced the KL term, the forward goes without
+            sync_kl = not BT_FUSED_KL and self.inject_draw is None and want_kl
+            mu_pk, sg_pk, kl_synced = self._packed_kl(sync_kl)
+            fwd_kl = want_kl and kl_synced is None
+            priors = (self.prior_weight_mu, self.prior_weight_sigma, self.prior_bias_mu, self.prior_bias_sigma) if fwd_kl else None
             out, kl = F.fused_forward(x, mu_t, rho_t, self.mu_bias, self.rho_bias, flip=self._flip, conv=conv,
                                       S=S, shared_x=shared, priors=priors, eps_w=draw.get("eps_w"), eps_b=draw.get("eps_b"),
                                       sign_in=draw.get("sign_in"), sign_out=draw.get("sign_out"), seed=seed, call=call,
-                                      layer_id=self._layer_id, sample0=sample0, call_base=call_base, want_kl=want_kl,
+                                      layer_id=self._layer_id, sample0=sample0, call_base=call_base, want_kl=fwd_kl,
                                       workspace_owner=("layer", self._ws_id), post_scale=self.post_scale, post_shift=self.post_shift,
-                                      residual=residual, relu=self.post_relu, pool=self.post_pool, packed=self._packed(), prior_type=kind)
+                                      residual=residual, relu=self.post_relu, pool=self.post_pool, packed=(mu_pk, sg_pk), prior_type=kind)
+            if kl_synced is not None:
+                kl = kl_synced
         conv_shape = tuple(out.shape[1:])     # shape of one sample's contraction output (sign_out's shape): before any fused pooling
         if self.post_pool and conv is not None:
             conv_shape = (out.shape[1],) + F.conv_out_hw(x.shape[2], x.shape[3], mu_t.shape[2], mu_t.shape[3], *conv["stride"],
                                                          *conv["padding"], *conv["dilation"])
         self._last = dict(draw=draw or None, rng=(seed, call_base, call, self._layer_id, sample0), S=S,
                           kernel=_lib.lib().bt_last_kernel_name().decode(), launch=_lib.last_launch_info(),
-                          shared_x=shared, residual=residual is not None, fused_kl=bool(want_kl and not needs_grad),
+                          shared_x=shared, residual=residual is not None, fused_kl=bool(not needs_grad and fwd_kl),
                           x_shape=(B,) + tuple(x.shape[1:]), out_shape=(B,) + conv_shape)
         if lead is not None:
             out = out.reshape(lead + (self.out_features,))

@@ -24,6 +24,7 @@ class McContext:
         self.kls = []            # per-layer 0-dim KL tensors in execution order (collect_kl)
         self.call_base = call_base  # device uint32 word (graph replay) or None
         self.synced = set()      # id() of the layers whose packs sync_model_packs has verified inside this context
+        self.sync_kl = {}        # id() of a layer -> its KL term, produced by that pack check (bt_pack_sync_kl) for the layer's forward to take
         self.pack_event = None   # recorded on the side stream that verifies every layer but the first (sync_model_packs)
         self.late = set()        # id() of the layers verified there: the first of them to run makes the launch stream wait
         self.train_fused = False  # TrainGraph: forwards carry their KL term along (FusedForward's second output) ...
@@ -63,23 +64,39 @@ def sync_model_packs(model, ctx=None, force=False, overlap=True):
     With a context the sweep is split: the FIRST layer is verified in the launch stream (a few KB), all the others on a side
     stream that forks here and is joined by the first of them to run (``join_packs``) -- the HBM-bound sweep of the whole model
     (ResNet18: 89 MB, ~30 us) then runs beside the first layer's kernel instead of in front of it. Under graph capture the fork
-    and the join become edges of the graph."""
+    and the join become edges of the graph.
+    When the context collects KL terms outside autograd, the same sweep also produces every eligible layer's KL term
+    (bt_pack_sync_kl: it reads the priors beside (mu, rho)), handed to the layer's forward through ``ctx.sync_kl``: the forward
+    kernels then run without their own KL sweep."""
     from . import functional as F
+    from .layers import _fused
     by_dev = {}
     for m in model.modules():
         if hasattr(m, "_pack_segment") and m._w("mu").is_cuda:
             if force:
                 m._pack_force = True
             by_dev.setdefault(m._w("mu").device, []).append(m)
+    with_kl = (ctx is not None and ctx.collect_kl and not torch.is_grad_enabled() and not _fused.BT_FUSED_KL)
+
+    def kls(layers):
+        if not with_kl:
+            return None
+        out = [None if m.inject_draw is not None else m._sync_kl_entry() for m in layers]
+        for m, k in zip(layers, out):
+            if k is not None:
+                ctx.sync_kl[id(m)] = k[-1]
+        return out
+
     for dev, layers in by_dev.items():
         if ctx is None or not overlap or len(layers) < 2 or len(by_dev) > 1:
-            F.pack_sync([m._pack_segment() for m in layers], owner=("model", id(model)))
+            F.pack_sync([m._pack_segment() for m in layers], owner=("model", id(model)), kls=kls(layers))
         else:
-            F.pack_sync([layers[0]._pack_segment()], owner=("model", id(model), "first"))
+            F.pack_sync([layers[0]._pack_segment()], owner=("model", id(model), "first"), kls=kls(layers[:1]))
             cur, side = torch.cuda.current_stream(dev), _side_stream(dev)
             side.wait_stream(cur)
+            rest = kls(layers[1:])        # (the result tensors are allocated on the launch stream, which reads them after the join)
             with torch.cuda.stream(side):
-                F.pack_sync([m._pack_segment() for m in layers[1:]], owner=("model", id(model), "rest"))
+                F.pack_sync([m._pack_segment() for m in layers[1:]], owner=("model", id(model), "rest"), kls=rest)
                 ctx.pack_event = torch.cuda.Event()
                 ctx.pack_event.record(side)
             ctx.late.update(id(m) for m in layers[1:])

@@ -209,6 +209,20 @@ typedef struct bt_pack_seg {
 } bt_pack_seg;
 int bt_pack_sync(int32_t n_segments, const bt_pack_seg *segs, void *workspace, size_t workspace_bytes, bt_stream_t stream);
 
+/* bt_pack_sync that also produces layers' KL terms from the sweep it makes anyway: for every segment whose kls[i].kl_out is
+ * not NULL, kl_out (DEVICE float) <- mean over the weights of kl_div's 'normal' branch + (bias given) the mean over the bias,
+ * the value a fused forward with kl_out writes (each mean accumulated in double, then rounded to fp32 and added), so that the
+ * layer's forward can run without its own KL sweep. The priors have mu_w's shape; the bias tensors have n_bias elements, or
+ * are all NULL. kls: HOST array of n_segments entries, or NULL (= bt_pack_sync). */
+typedef struct bt_pack_kl {
+  const float *prior_mu_w, *prior_sigma_w;
+  const float *mu_b, *rho_b, *prior_mu_b, *prior_sigma_b;
+  float *kl_out;
+  int64_t n_bias;
+} bt_pack_kl;
+int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg *segs, const bt_pack_kl *kls, void *workspace, size_t workspace_bytes,
+                    bt_stream_t stream);
+
 /* The on-chip draws, materialised (test / replay hook: the fused kernels never call these).
  * They emit exactly the streams the fused kernels consume for (rng, tensor_id):
  * tensor_id 0 = eps_w, 1 = eps_b, 2 = sign_in, 3 = sign_out.
