@@ -80,6 +80,8 @@ struct FwdArgs {
   int sk_nsl, sk_ks, sk_cpt;           // slices per tile, slice width (channels), slices per tap
   int sk_kh0, sk_nh, sk_kw0, sk_nw;    // the rectangle of taps whose input pixel exists for the one output pixel
   int d_tap;     // direct flavour: the ONE tap of the kernel window that meets data (0 for 1x1 kernels; the centre of a padded window over a 1x1 image)
+  int spw, n_sg;        // quad flavour, sample walk: samples per workgroup, sample groups = ceil(S / spw) (launch_quad)
+  uint32_t inv_n_sg;
 };
 
 // Blocks are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2). Give every XCD a CONTIGUOUS range of

@@ -66,11 +66,11 @@ static int launch_split_xm(FwdArgs& a, int mode, int xm, hipStream_t stream) {
 
 // Layers with <= 4 input channels per group (the ResNet stems): bt_fused_split_quad.h. Whole-image 512-wide tiles, output through
 // the LDS-staged read-out (optionally with the fused 3x3 / stride-2 max-pool, power-of-two pooled widths).
-template <bool POOL>
+template <bool POOL, bool WALK = false>
 static int launch_quad_cfg(FwdArgs& a, int mode, hipStream_t stream) {
   constexpr int lds = split_lds_bytes<64, 512, 3>();
   auto launch = [&](auto kern, const char* nm) -> int {
-    static bool flags[2][64] = {};
+    static bool flags[2][64] = {};   // (one set per instantiation)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "fused forward (split): hipGetDevice failed");
     if (!flags[mode == 2][dev]) {
@@ -84,7 +84,32 @@ static int launch_quad_cfg(FwdArgs& a, int mode, hipStream_t stream) {
     return check_launch("fused forward (split, quad)");
   };
   // (the opt-in two-piece form is not instantiated for the stems: they run the exact split in every split mode)
+  if constexpr (WALK) return launch(fused_split_quad_kernel<3, true, false, true>, "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=1,walk>");
   return launch(fused_split_quad_kernel<3, POOL>, POOL ? "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=1>" : "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=0>");
+}
+
+// Samples per workgroup of the quad flavour's sample walk (0: the one-sample path). Pooled 16x16 maps in tiles of two images over
+// an input that every sample shares: the patch is staged once for a run of samples. The largest of 8 / 4 / 2 that still gives a
+// workgroup to every CU (at least kKlSlices workgroups: the fused KL sweep keeps its slices, so its sum is the one-sample path's).
+// BT_QUAD_SPW (measurement knob, read at every launch) caps it: 1 = the one-sample path.
+static int quad_spw(const FwdArgs& a, long long tiles) {
+  if (!a.ep_pool || a.x_sample_stride != 0 || a.S < 2 || a.Ho != 16 || a.Wo != 16 || a.t_NI != 2 || a.ep_Hp != 8 || a.ep_Wp != 8) return 0;
+  int nd[2] = {};
+  tap_window(a.KH, a.DH, a.SH, a.PH, a.H, a.Ho, false, &nd[0], &nd[1]);
+  int nw, dxs;
+  tap_window(a.KW, a.DW, a.SW, a.PW, a.W, a.Wo, false, &nw, &dxs);
+  const long long PHt = 15ll * (nd[1] ? a.SH : 1) + nd[1] + 1, PWt = 15ll * (dxs ? a.SW : 1) + dxs + 1;
+  if (2 * PHt * PWt * 24 + kWalkBytes > kQuadXBytes) return 0;   // the walk's slots sit behind the patch
+  static int n_cu[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (!n_cu[dev] && hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu[dev] = 0;
+  const long long fill = n_cu[dev] > 256 ? n_cu[dev] : 256;
+  const char* e = getenv("BT_QUAD_SPW");
+  const int cap = e ? atoi(e) : 8;
+  for (int spw = 8; spw >= 2; spw >>= 1)
+    if (spw <= cap && spw <= a.S && tiles * ((a.S + spw - 1) / spw) >= fill) return spw;
+  return 0;
 }
 
 static int launch_quad(FwdArgs& a, int mode, hipStream_t stream) {
@@ -117,10 +142,14 @@ static int launch_quad(FwdArgs& a, int mode, hipStream_t stream) {
   }
   a.n_tiles = (a.Cog + 63) / 64;
   a.t_NI = NI, a.t_R = R, a.t_Wt = a.Wo, a.n_bt = (a.B + NI - 1) / NI, a.n_rt = (a.Ho + R - 1) / R, a.n_ct = 1, a.m_tiles = a.n_bt * a.n_rt;
-  const long long total = (long long)a.G * a.n_tiles * a.S * a.m_tiles;
+  const long long tiles = (long long)a.G * a.n_tiles * a.m_tiles;
+  const int spw = quad_spw(a, tiles);
+  a.spw = spw ? spw : 1, a.n_sg = (a.S + a.spw - 1) / a.spw;
+  const long long total = tiles * a.n_sg;
   if (total <= 0 || total > 0x7FFFFFFFll) return 1;
   a.total_blocks = (int)total;
   a.kl_slices = total < 256 ? (int)total : 256;
+  if (spw) return launch_quad_cfg<true, true>(a, mode, stream);
   return a.ep_pool ? launch_quad_cfg<true>(a, mode, stream) : launch_quad_cfg<false>(a, mode, stream);
 }
 

@@ -18,7 +18,7 @@ static inline uint32_t inv_u32(long long d, long long nmax) {
 static inline void split_fill_inverses(FwdArgs& a) {
   static const bool off = getenv("BT_NO_HOST_INV") != nullptr;   // test hook: every kernel-side division takes its fallback path
   if (off) {
-    a.inv_m_tiles = a.inv_S = a.inv_n_tiles = a.inv_n_bt = a.inv_n_ct = a.inv_rw = a.inv_wt = a.inv_kw = 0u;
+    a.inv_m_tiles = a.inv_S = a.inv_n_tiles = a.inv_n_bt = a.inv_n_ct = a.inv_rw = a.inv_wt = a.inv_kw = a.inv_n_sg = 0u;
     return;
   }
   const long long tb = a.total_blocks;
@@ -30,6 +30,7 @@ static inline void split_fill_inverses(FwdArgs& a) {
   a.inv_rw = inv_u32((long long)a.t_R * a.t_Wt, 1024);
   a.inv_wt = inv_u32(a.t_Wt, 1024);
   a.inv_kw = inv_u32(a.KW, 64);
+  a.inv_n_sg = inv_u32(a.n_sg, tb);
 }
 
 // Extent of the window of taps that can meet data along one axis (the kernel's own rule: bt_fused_split.h), for the whole

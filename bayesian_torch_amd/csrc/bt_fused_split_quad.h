@@ -26,7 +26,14 @@ constexpr int quad_lds_bytes() { return 2 * split_w_bytes<64, 3, FLIP>() + (FLIP
 // the PADDING channel of its first piece (bits 0-2 of that bf16: a denormal that only ever meets the zero weights of the padding
 // channel), so the patch stays 24 B per pixel and the 37x37 patch of a CIFAR stem fits beside the two weight images; a
 // consumer expands them to sign masks and flips its x fragments in registers between the two contractions.
-template <int NP, bool POOL, bool FLIP = false>
+// WALK (Reparameterization, shared x, pooled 16x16 maps in tiles of two images; launch_quad): a workgroup runs the samples
+// s0 .. s0 + a.spw - 1 of its (pixel tile, channel tile) over ONE staged patch. The producers' W pipeline flows across the
+// sample boundary (sample s+1's stage 0 is drawn while the consumers finish sample s); the output stage pools from the
+// accumulators (the consumer arm's walk below) and leaves the patch and the W buffers alone.
+constexpr int kWalkRowBytes = 2 * 64 * 16 * 4;                 // one image row of each of the tile's 2 images, 64 channels
+constexpr int kWalkBytes = 2 * kWalkRowBytes + 2 * 3 * 64 * 4;  // [2 samples] shared rows + [2 samples] bias / scale / shift
+
+template <int NP, bool POOL, bool FLIP = false, bool WALK = false>
 __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) {
   constexpr int BN = 64, BM = FLIP ? 256 : 512, kProducers = 256, kThreadsAll = 512, STEPS = kSplitSteps, TPS = 4 * STEPS;  // taps per stage
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32, NOP = FLIP ? 2 : 1;
@@ -36,11 +43,15 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
   // (the patch region holds XQ_BYTES / PBQ pixels: the host checks PCH against it)
   constexpr int SROWS = BN, SROW = BM + 4;
   static_assert(!FLIP || NP == 3, "Flipout: the exact split");
+  static_assert(!WALK || (POOL && !FLIP && CWM == 4 && TN == 2 && TM == 4), "the walk: Reparameterization, pooled, 4 x 128-pixel consumer waves");
   static_assert((4 * BN + NOP * SROWS * SROW) * 4 <= 2 * W_BYTES + XQ_BYTES, "output staging fits the operand buffers");
 
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   char* const wbuf = smem_c;                  // [2][W_BYTES]
   char* const xq = smem_c + 2 * W_BYTES;      // one patch, XQ_BYTES
+  // walk: the tail of the patch room (host: PCH * PBQ + kWalkBytes <= XQ_BYTES)
+  float* const wrow = reinterpret_cast<float*>(xq + XQ_BYTES - kWalkBytes);  // [sample & 1][image][channel][16 cols]: image row 7
+  float* const wcon = wrow + 2 * kWalkRowBytes / 4;                           // [sample & 1][bias | scale | shift][channel]
   float* const smem = reinterpret_cast<float*>(smem_c);
   int4* const taptab = reinterpret_cast<int4*>(smem_c + 2 * W_BYTES + XQ_BYTES);
   double* const red = reinterpret_cast<double*>(smem_c + 2 * W_BYTES + XQ_BYTES + kMaxTaps * 16);
@@ -64,8 +75,9 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
   int L = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, a.total_blocks));   // (reciprocals from the host: bt_fused_split_host.h)
   int Lq = udiv_inv(L, a.m_tiles, a.inv_m_tiles);
   const int mt = __builtin_amdgcn_readfirstlane(L - Lq * a.m_tiles);
-  L = Lq, Lq = udiv_inv(L, a.S, a.inv_S);
-  const int s = __builtin_amdgcn_readfirstlane(L - Lq * a.S);
+  const int SD = WALK ? a.n_sg : a.S;  // walk: sample groups of a.spw
+  L = Lq, Lq = udiv_inv(L, SD, WALK ? a.inv_n_sg : a.inv_S);
+  const int s = __builtin_amdgcn_readfirstlane((L - Lq * SD) * (WALK ? a.spw : 1));  // (walk: the group's first sample)
   L = Lq, Lq = udiv_inv(L, a.n_tiles, a.inv_n_tiles);
   const int nt = __builtin_amdgcn_readfirstlane(L - Lq * a.n_tiles);
   const int g = __builtin_amdgcn_readfirstlane(Lq);
@@ -254,6 +266,32 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     }
   };
 
+  // ---- producers' weight units: unit u = (row n = u & 63, tap slot of the stage q = u >> 6): 4 sampled weights = one Philox block ----
+  constexpr int UMAX = (BN * TPS + kProducers - 1) / kProducers;  // 5
+  int l_off[UMAX];
+  uint32_t u_co[UMAX];
+#pragma unroll
+  for (int i = 0; i < UMAX; ++i) {
+    const int u = ptid + kProducers * i, n = u & (BN - 1), q = u >> 6;  // q < TPS
+    const int st_ = q >> 2, hf = (q >> 1) & 1, sub = q & 1;
+    const int co_g = n0 + n;
+    u_co[i] = co_g < a.Cog ? (uint32_t)(g * a.Cog + co_g) : 0xFFFFFFFFu;
+    l_off[i] = st_ * W_STEP + hf * W_HALF + (n ^ ((2 * st_ + hf) & 7)) * 16 + sub * 8;
+  }
+  float4 mu[UMAX], rs[UMAX];
+  uint32_t ue[UMAX];  // draw index of the unit in this stage, or OOB
+  auto load_w = [&](int st) {
+#pragma unroll
+    for (int i = 0; i < UMAX; ++i) {
+      const int ai = st * TPS + ((ptid + kProducers * i) >> 6);
+      const bool in = ai < nA && u_co[i] != 0xFFFFFFFFu;
+      const int tap = taptab[ai < nA ? ai : 0].w;
+      ue[i] = in ? (u_co[i] * (uint32_t)T + (uint32_t)tap) * 4u : (kOOB >> 2);
+      mu[i] = ldf4(r_mu, in ? 4u * ue[i] : kOOB), rs[i] = ldf4(r_rs, in ? 4u * ue[i] : kOOB);
+    }
+  };
+  if (!FLIP && producer && NS > 0) load_w(0);  // stage 0's loads in flight under the patch fetch (Flipout: after it, as measured)
+
 // ---- the patch, once, by ALL 8 waves (the consumers have nothing to do before the first stage): a thread owns pixels
 //      tid + 512 i; <= 4 channels per pixel, split on the way to LDS ----
   {
@@ -307,61 +345,33 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     // (no producer priority here, unlike bt_fused_split.h's wide tiles: without it the Reparameterization stem measured 228 -> 222 us alone
     //  and 253.5 -> 247.7 us inside the cfg3 graph, the Flipout stem 474.0 -> 459.1 us inside cfg4's -- same box, BT_LIB_PATH A/B)
     // =================================================== PRODUCERS ===========================================================
-    // ---- weights: unit u = (row n = u & 63, tap slot of the stage q = u >> 6): 4 sampled weights = one Philox block ----
-    constexpr int UMAX = (BN * TPS + kProducers - 1) / kProducers;  // 5
-    int l_off[UMAX];
-    uint32_t u_co[UMAX];
+    // stage st of sample smp -> the W buffer Wt (the units' mu / sigma: load_w(st))
+    auto draw_stage = [&](uint32_t smp, char* const Wt) {
+      float ep[UMAX][4];
 #pragma unroll
-    for (int i = 0; i < UMAX; ++i) {
-      const int u = ptid + kProducers * i, n = u & (BN - 1), q = u >> 6;  // q < TPS
-      const int st_ = q >> 2, hf = (q >> 1) & 1, sub = q & 1;
-      const int co_g = n0 + n;
-      u_co[i] = co_g < a.Cog ? (uint32_t)(g * a.Cog + co_g) : 0xFFFFFFFFu;
-      l_off[i] = st_ * W_STEP + hf * W_HALF + (n ^ ((2 * st_ + hf) & 7)) * 16 + sub * 8;
-    }
-    float4 mu[UMAX], rs[UMAX];
-    uint32_t ue[UMAX];  // draw index of the unit in this stage, or OOB
-    auto load_w = [&](int st) {
+      for (int i = 0; i < UMAX; ++i) philox_normal4(key_w, smp, ue[i] >> 2, ep[i]);
 #pragma unroll
       for (int i = 0; i < UMAX; ++i) {
-        const int ai = st * TPS + ((ptid + kProducers * i) >> 6);
-        const bool in = ai < nA && u_co[i] != 0xFFFFFFFFu;
-        const int tap = taptab[ai < nA ? ai : 0].w;
-        ue[i] = in ? (u_co[i] * (uint32_t)T + (uint32_t)tap) * 4u : (kOOB >> 2);
-        mu[i] = ldf4(r_mu, in ? 4u * ue[i] : kOOB), rs[i] = ldf4(r_rs, in ? 4u * ue[i] : kOOB);
+        const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
+        uint32_t wh[4], wm_[4], wl[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)  // masked units (dead taps, rows past Cog) loaded zeros: w = 0 -- and the slot IS written
+          split_pieces(FLIP ? m4[j] : __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j])), wh[j], wm_[j], wl[j]);
+        char* const dst = Wt + l_off[i];
+        *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
+        *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+        if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
+        if constexpr (FLIP) {  // second image: the perturbation sigma * eps
+#pragma unroll
+          for (int j = 0; j < 4; ++j) split_pieces(__fmul_rn(s4[j], ep[i][j]), wh[j], wm_[j], wl[j]);
+          *reinterpret_cast<uint2*>(dst + W_OP) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
+          *reinterpret_cast<uint2*>(dst + W_OP + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+          *reinterpret_cast<uint2*>(dst + W_OP + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
+        }
       }
     };
-    if (NS > 0) load_w(0);
-    for (int st = 0; st <= NS; ++st) {  // NS + 1 barriers, like the consumer arm
-      if (st < NS) {
-        char* const Wt = wbuf + (st & 1) * W_BYTES;
-        float ep[UMAX][4];
-#pragma unroll
-        for (int i = 0; i < UMAX; ++i) philox_normal4(key_w, sample, ue[i] >> 2, ep[i]);
-#pragma unroll
-        for (int i = 0; i < UMAX; ++i) {
-          const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
-          uint32_t wh[4], wm_[4], wl[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)  // masked units (dead taps, rows past Cog) loaded zeros: w = 0 -- and the slot IS written
-            split_pieces(FLIP ? m4[j] : __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j])), wh[j], wm_[j], wl[j]);
-          char* const dst = Wt + l_off[i];
-          *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
-          *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
-          if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
-          if constexpr (FLIP) {  // second image: the perturbation sigma * eps
-#pragma unroll
-            for (int j = 0; j < 4; ++j) split_pieces(__fmul_rn(s4[j], ep[i][j]), wh[j], wm_[j], wl[j]);
-            *reinterpret_cast<uint2*>(dst + W_OP) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
-            *reinterpret_cast<uint2*>(dst + W_OP + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
-            *reinterpret_cast<uint2*>(dst + W_OP + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
-          }
-        }
-        if (st + 1 < NS) load_w(st + 1);
-      }
-      __syncthreads();
-    }
-    if (ptid < BN) {  // bias draw + output-stage constants
+    // bias draw + output-stage constants of sample smp (threads ptid < BN)
+    auto bias_consts = [&](uint32_t smp, float* const b0p, float* const b1p, float* const scp, float* const shp) {
       float bv = 0.f;
       const int co_g = n0 + ptid;
       if (a.mu_b && co_g < a.Cog) {
@@ -369,22 +379,51 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
         RngKey kb = key_w;
         kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
         float z[4];
-        philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
+        philox_normal4(kb, smp, (uint32_t)(co >> 2), z);
         const int sel = co & 3;
         const float e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
         const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
         bv = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
-        if constexpr (FLIP) bias1[ptid] = dl;
+        if constexpr (FLIP) b1p[ptid] = dl;
       } else if constexpr (FLIP) {
-        bias1[ptid] = 0.f;
+        b1p[ptid] = 0.f;
       }
-      bias0[ptid] = bv;
+      b0p[ptid] = bv;
       const bool cv = a.ep_scale && co_g < a.Cog;
       const int cs = cv ? g * a.Cog + co_g : 0;
       const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
-      osc[ptid] = cv ? sc : 1.f;
-      osh[ptid] = cv ? sh : 0.f;
+      scp[ptid] = cv ? sc : 1.f;
+      shp[ptid] = cv ? sh : 0.f;
+    };
+    if constexpr (WALK) {
+      // stage stream of the samples sample .. sample + nsw - 1, back to back: G counts the stages (W buffer G & 1); a sample's
+      // output constants go with its stage 0, into its parity's slot
+      const int nsw = min(a.spw, a.S - s), NSE = NS > 0 ? NS : 1;
+      int G = 0;
+      for (int k = 0; k < nsw; ++k) {
+        const uint32_t smp = sample + (uint32_t)k;
+        float* const cs_ = wcon + (k & 1) * 3 * BN;
+        for (int st = 0; st < NSE; ++st, ++G) {
+          if (st < NS) {
+            draw_stage(smp, wbuf + (G & 1) * W_BYTES);
+            if (st + 1 < NS) load_w(st + 1);
+            else if (k + 1 < nsw) load_w(0);  // the next sample's stage 0: no bubble at the sample boundary
+          }
+          if (st == 0 && ptid < BN) bias_consts(smp, cs_, cs_, cs_ + BN, cs_ + 2 * BN);
+          __syncthreads();
+        }
+      }
+      __syncthreads();  // the consumers' last stage
+    } else {
+    if (FLIP && NS > 0) load_w(0);
+    for (int st = 0; st <= NS; ++st) {  // NS + 1 barriers, like the consumer arm
+      if (st < NS) {
+        draw_stage(sample, wbuf + (st & 1) * W_BYTES);
+        if (st + 1 < NS) load_w(st + 1);
+      }
+      __syncthreads();
     }
+    if (ptid < BN) bias_consts(sample, bias0, bias1, osc, osh);
     __syncthreads();
     __syncthreads();
     if constexpr (FLIP) {
@@ -393,6 +432,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     }
     if constexpr (POOL) readout_pool(wave);
     else readout_quads(tid);
+    }
   } else {
     // =================================================== CONSUMERS ===========================================================
     long long kl_i = 0, kl_hi = 0;
@@ -467,11 +507,8 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[o][i][j][r] = 0.f;
 
-    __syncthreads();  // patch and stage 0 staged
-    if (stamp0) dbg_[0] = __builtin_amdgcn_s_memtime();
-    for (int st = 0; st < NS; ++st) {
-      if (stamp0) dbg_[2 + 2 * st] = __builtin_amdgcn_s_memtime();
-      const char* const Wt = wbuf + (st & 1) * W_BYTES;
+    // one stage: tap chunk st of the K loop over the W buffer Wt
+    auto run_stage = [&](int st, const char* const Wt) {
       const int left = nA - st * TPS, nstep = left >= TPS ? STEPS : (left + 3) >> 2;
       // (step, column group) units in a software pipeline, as in bt_fused_split.h: the stage's tap offsets are fetched first,
       // the fragments of unit u+1 are read before the MFMAs of unit u.
@@ -546,6 +583,107 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
           }
         }
       }
+    };
+    if constexpr (WALK) {
+      const int nsw = min(a.spw, a.S - s), NSE = NS > 0 ? NS : 1;
+      const bool odd = (wm & 1) != 0;  // a wave = 8 rows of one 16x16 image: odd waves hold rows 8..15 and take row 7 from LDS
+      const int bimg = b0 + (wm >> 1);
+      auto nmax = [](float m, float v) { return (v > m || v != v) ? v : m; };
+      __syncthreads();  // patch, the first sample's stage 0 and output constants staged
+      if (stamp0) dbg_[0] = __builtin_amdgcn_s_memtime();
+      int G = 0;
+      for (int k = 0; k < nsw; ++k) {
+        if (k > 0) {
+#pragma unroll
+          for (int i = 0; i < TN; ++i)
+#pragma unroll
+            for (int j = 0; j < TM; ++j)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) acc[0][i][j][r] = 0.f;
+        }
+        const float* const cs_ = wcon + (k & 1) * 3 * BN;
+        float* const xrow = wrow + (k & 1) * (kWalkRowBytes / 4) + (wm >> 1) * (BN * 16);
+        for (int st = 0; st < NSE; ++st, ++G) {
+          if (stamp0 && G < 48) dbg_[2 + 2 * G] = __builtin_amdgcn_s_memtime();
+          if (st < NS) run_stage(st, wbuf + (G & 1) * W_BYTES);
+          if (stamp0 && G < 48) dbg_[2 + 2 * G + 1] = __builtin_amdgcn_s_memtime();
+          if (st + 1 == NSE) {
+            // output-stage constants in place, in the staged path's order: ((acc + bias) * sc) + sh; even waves publish their
+            // image row 7 (registers 8..15 of column group 3: cols 4 lh + e and 8 + 4 lh + e)
+#pragma unroll
+            for (int i = 0; i < TN; ++i) {
+              const int co_l = i * 32 + li;
+              const float bsv = cs_[co_l], scv = cs_[BN + co_l], shv = cs_[2 * BN + co_l];
+#pragma unroll
+              for (int j = 0; j < TM; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[0][i][j][r] = __fadd_rn(__fmul_rn(__fadd_rn(acc[0][i][j][r], bsv), scv), shv);
+              if (!odd) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                  *reinterpret_cast<float4*>(xrow + co_l * 16 + 8 * h + 4 * lh) =
+                      make_float4(acc[0][i][3][8 + 4 * h], acc[0][i][3][9 + 4 * h], acc[0][i][3][10 + 4 * h], acc[0][i][3][11 + 4 * h]);
+              }
+            }
+            if (kl_block) {
+              if (k + 1 == nsw) kl_finish();
+              else kl_group();
+            }
+          } else if (kl_block) {
+            kl_group();
+          }
+          __syncthreads();
+        }
+        // ---- MaxPool2d(3, 2, 1) from the accumulators: wave row r (-1..7) = column group r >> 1, registers 4 (2 (r & 1) + h) + e
+        //      hold cols 8 h + 4 lh + e. A lane pools the columns centred on 8 h + 4 lh + 2 sub (pooled column 4 h + 2 lh + sub);
+        //      the left neighbour of sub 0 is the other lane half's col 8 h + 4 lh - 1 (register e = 3). NaN wins, -inf padding,
+        //      the read-out's order: per row, left / centre / right.
+        float* const out_k = a.out + (long long)(s + k) * a.out_elems;
+#pragma unroll
+        for (int i = 0; i < TN; ++i) {
+          const int co_l = i * 32 + li;
+          const bool ok = bimg < a.B && n0 + co_l < a.Cog;
+          float* const oplane = out_k + (ok ? (bimg * a.Co + g * a.Cog + n0 + co_l) * 64 : 0) + 32 * (wm & 1);
+          float top[2][4];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const float4 t = odd ? *reinterpret_cast<const float4*>(xrow + co_l * 16 + 8 * h + 4 * lh) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            top[h][0] = t.x, top[h][1] = t.y, top[h][2] = t.z, top[h][3] = t.w;
+          }
+          auto val = [&](int r, int h, int e) -> float { return r < 0 ? top[h][e] : acc[0][i][r >> 1][4 * (2 * (r & 1) + h) + e]; };
+#pragma unroll
+          for (int py = 0; py < 4; ++py) {
+            float m[2][2] = {{-INFINITY, -INFINITY}, {-INFINITY, -INFINITY}};
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+              const int r = 2 * py - 1 + dy;
+              const float x0 = __shfl_xor(val(r, 0, 3), 32, 64), x1 = __shfl_xor(val(r, 1, 3), 32, 64);
+#pragma unroll
+              for (int h = 0; h < 2; ++h) {
+                const float l0 = lh ? (h ? x1 : x0) : (h ? x0 : -INFINITY);
+                m[h][0] = nmax(nmax(nmax(m[h][0], l0), val(r, h, 0)), val(r, h, 1));
+                m[h][1] = nmax(nmax(nmax(m[h][1], val(r, h, 1)), val(r, h, 2)), val(r, h, 3));
+              }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              if (relu) {  // max and ReLU commute
+                m[h][0] = m[h][0] < 0.f ? 0.f : m[h][0];
+                m[h][1] = m[h][1] < 0.f ? 0.f : m[h][1];
+              }
+              if (ok) *reinterpret_cast<float2*>(oplane + 8 * py + 4 * h + 2 * lh) = make_float2(m[h][0], m[h][1]);
+            }
+          }
+        }
+      }
+      if (stamp0) dbg_[1] = __builtin_amdgcn_s_memtime();
+      if (kl_block && wave == 0) kl_ticket();  // (the last barrier published the KL partials)
+    } else {
+    __syncthreads();  // patch and stage 0 staged
+    if (stamp0) dbg_[0] = __builtin_amdgcn_s_memtime();
+    for (int st = 0; st < NS; ++st) {
+      if (stamp0) dbg_[2 + 2 * st] = __builtin_amdgcn_s_memtime();
+      run_stage(st, wbuf + (st & 1) * W_BYTES);
       if (stamp0) dbg_[2 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
       if (kl_block) kl_group();
       __syncthreads();
@@ -596,6 +734,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     if constexpr (POOL) readout_pool(wave);
     else readout_quads(tid);
     if (stamp0) dbg_[126] = __builtin_amdgcn_s_memtime();
+    }
   }
   if (dbg_ && dbg_[201] && tid == 0) {
     dbg_[256 + 4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
