@@ -269,8 +269,8 @@ extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, cons
   fp.nseg = pk.nseg = n_segments;
   for (int i = 0; i < n_segments; ++i) fs.mu[i] = fp.mu[i], fs.rho[i] = fp.rho[i], fs.state[i] = fp.state[i], fs.n[i] = fp.n[i], fs.first_block[i] = fp.first_block[i];
   fs.first_block[n_segments] = fblocks, fs.force = fp.force, fs.nseg = n_segments;
-  hipLaunchKernelGGL(pack_fingerprint_kernel, dim3(fblocks), dim3(kFpThreads), 0, (hipStream_t)stream, fs, ws_counter(workspace), ws_slots(workspace), fblocks);
-  if (int rc = check_launch("bt_pack_sync (fingerprint)")) return rc;
+  // Everything that can refuse the call is checked before the first launch: the fingerprint launch stores every segment's new
+  // fingerprint and dirty flag, so a refusal after it would leave the packs stale against fingerprints that say they are current.
   const size_t lds = (size_t)max_taps * (kPackCh + 1) * sizeof(float2);
   if (max_taps > 128) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_sync: kernels larger than 128 taps are not supported");
   if (lds > 48 * 1024) {   // (above the default dynamic-LDS limit: 11 x 11 kernels and larger)
@@ -283,6 +283,8 @@ extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, cons
       flags[dev] = true;
     }
   }
+  hipLaunchKernelGGL(pack_fingerprint_kernel, dim3(fblocks), dim3(kFpThreads), 0, (hipStream_t)stream, fs, ws_counter(workspace), ws_slots(workspace), fblocks);
+  if (int rc = check_launch("bt_pack_sync (fingerprint)")) return rc;
   hipLaunchKernelGGL(pack_dirty_kernel, dim3(pblocks), dim3(256), lds, (hipStream_t)stream, pk);
   return check_launch("bt_pack_sync (pack)");
 }

@@ -36,6 +36,7 @@ class FamilyConvLayer(FusedBayesLayer):
     _kind, _wname = "conv", "kernel"
     _nd, _transposed = 2, False
     _sync_kl = False     # (forward() takes the KL from kl_loss())
+    _output_stage = False  # the launch's output is re-arranged afterwards: nothing folds into it (fuse.py skips these layers)
 
     def _setup(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups, output_padding, prior_mean, prior_variance,
                posterior_mu_init, posterior_rho_init, bias, tuple_inits):
@@ -164,6 +165,8 @@ class FamilyConvLayer(FusedBayesLayer):
 
     # ------------------------------------------------------------------ forward
     def forward(self, input, return_kl=True):
+        if self.post_scale is not None or self.post_shift is not None or self.post_relu or self.post_pool:
+            raise RuntimeError(f"{type(self).__name__} has no fused output stage: post_scale / post_shift / post_relu / post_pool must stay unset")
         if self.dnn_to_bnn_flag:
             return_kl = False
         ctx = mc.current()

@@ -25,12 +25,14 @@ _warned = [False]
 import os as _os
 _NO_SEG_CACHE = bool(_os.environ.get("BT_NO_SEG_CACHE"))   # A/B knob of the eager path's host time (tools/profile_eager.py)
 BT_FUSED_KL = bool(_os.environ.get("BT_FUSED_KL"))         # A/B knob: inference forwards sweep their own KL instead of the pack check
+MAX_TAPS = 128     # kernel positions (kh * kw of the Conv2d launch) the fused kernels and bt_pack_sync support (kMaxTaps)
 
 
 class FusedBayesLayer(BaseVariationalLayer_):
     _kind = "linear"     # or "conv"
     _flip = False
     _wname = "weight"    # parameter suffix: mu_weight / mu_kernel
+    _output_stage = True  # forward() applies post_scale / post_shift / post_relu / post_pool (what bayesian_torch_amd.fuse folds into)
 
     # ------------------------------------------------------------------ construction
     def _build(self, wshape, bias, eps_bias_last=False, n_out=None):
@@ -170,6 +172,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
         taps = 1
         for d in smu.shape[2:]:
             taps *= d
+        if taps > MAX_TAPS:      # refused here, before any launch: a failed model-level check would leave the other layers' state half-written
+            raise NotImplementedError(f"{type(self).__name__}: a kernel of {taps} taps exceeds the {MAX_TAPS}-tap limit of the fused kernels")
         key = (mu.data_ptr(), rho.data_ptr(), tuple(smu.shape), mu.device)
         force = self._pack_force
         if self._pack is None or self._pack[0] != key:

@@ -85,3 +85,68 @@ def test_family_layers_train_and_convert():
     assert o.shape == (3, 6, 10, 10)
     (o.mean() + kl).backward()
     assert torch.isfinite(up.mu_kernel.grad).all() and float(up.rho_kernel.grad.abs().sum()) > 0
+
+
+FAMILY = ["Conv3dReparameterization", "Conv3dFlipout", "ConvTranspose1dReparameterization", "ConvTranspose1dFlipout",
+          "ConvTranspose2dReparameterization", "ConvTranspose2dFlipout", "ConvTranspose3dReparameterization", "ConvTranspose3dFlipout"]
+
+
+def _family_layer(cls, ci=8, co=4):
+    import bayesian_torch_amd.layers as L
+    if cls == "Conv3dReparameterization":
+        return L.Conv3dReparameterization(ci, co, 3, 0.0, 1.0, 0.0, -3.0)
+    return getattr(L, cls)(ci, co, 3)
+
+
+@pytest.mark.parametrize("cls", FAMILY)
+def test_fold_passes_skip_layers_without_an_output_stage(cls):
+    """The family layers re-arrange the launch's output after it: nothing may fold into it. fold_batchnorm / fold_relu leave the
+    BatchNorm and the ReLU in place, fold_pair / fold_maxpool refuse, and a post_* field set by hand makes forward() refuse rather
+    than drop the op."""
+    import torch.nn as nn
+    from bayesian_torch_amd.fuse import fold_batchnorm, fold_maxpool, fold_pair, fold_relu
+    layer = _family_layer(cls)
+    bn, relu = nn.BatchNorm2d(4), nn.ReLU()
+    model = nn.Sequential(layer, bn, relu).eval()
+    assert fold_batchnorm(model) == 0 and fold_relu(model) == 0
+    assert model[1] is bn and model[2] is relu
+    assert layer.post_scale is None and layer.post_shift is None and not layer.post_relu and not layer.post_pool
+    model = nn.Sequential(_family_layer(cls), nn.ReLU())
+    assert fold_relu(model) == 0 and type(model[1]) is nn.ReLU
+    with pytest.raises(TypeError):
+        fold_pair(layer, bn, relu=True)
+    with pytest.raises(TypeError):
+        fold_maxpool(layer, nn.MaxPool2d(3, 2, 1))
+    nd = 3 if "3d" in cls else 1 if "1d" in cls else 2
+    x = torch.zeros((1, 8) + (5,) * nd)
+    for field, value in (("post_relu", True), ("post_pool", True), ("post_scale", torch.ones(4)), ("post_shift", torch.zeros(4))):
+        fresh = _family_layer(cls)
+        setattr(fresh, field, value)
+        with pytest.raises(RuntimeError, match="no fused output stage"):
+            fresh(x)
+
+
+def test_fold_relu_pairs_only_inside_sequential():
+    """A ReLU registered right after a Bayesian layer in a custom module may be applied anywhere by its forward() (here: before the
+    layer, and shared): fold_relu leaves it alone. Inside a Sequential the registration order is the order of application: Conv1d,
+    a layer with an output stage, takes its ReLU."""
+    import torch.nn as nn
+    import bayesian_torch_amd.layers as L
+    from bayesian_torch_amd.fuse import fold_relu
+
+    class Block(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.fc = L.LinearReparameterization(6, 6)
+            self.act = nn.ReLU()
+
+        def forward(self, x):
+            return self.fc(self.act(x), return_kl=False) + self.act(x)
+
+    blk = Block()
+    assert fold_relu(blk) == 0 and type(blk.act) is nn.ReLU and not blk.fc.post_relu
+    outer = nn.Sequential(Block(), nn.ReLU())     # (a Sequential whose layer before the ReLU is not a Bayesian layer)
+    assert fold_relu(outer) == 0 and type(outer[0].act) is nn.ReLU and type(outer[1]) is nn.ReLU
+    for cls in ("Conv1dReparameterization", "Conv1dFlipout"):
+        seq = nn.Sequential(getattr(L, cls)(4, 8, 3), nn.ReLU())
+        assert fold_relu(seq) == 1 and seq[0].post_relu and isinstance(seq[1], nn.Identity)
