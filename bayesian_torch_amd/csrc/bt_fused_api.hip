@@ -4,10 +4,11 @@
 #include "bt_fused_fwd.h"
 
 namespace bt {
-int launch_reparam(bool linear, FwdArgs& a, hipStream_t stream);
-int launch_reparam_inj(bool linear, FwdArgs& a, hipStream_t stream);
-int launch_flipout(bool linear, FwdArgs& a, hipStream_t stream);
-int launch_flipout_inj(bool linear, FwdArgs& a, hipStream_t stream);
+// Each launches the layer and, on BT_OK, leaves the plan that ran (tile geometry, grid) in `ran`.
+int launch_reparam(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
+int launch_reparam_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
+int launch_flipout(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
+int launch_flipout_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 
 static unsigned long long* g_dbg = nullptr;
 static thread_local long long g_launch_info[16] = {};
@@ -107,10 +108,11 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
   if (!all_inj && !none_inj) return bad("inject all draws of the layer (eps_w, eps_b when biased, both sign tensors for Flipout) or none");
   if (inj && a.ep_pool) return set_error(BT_ERR_UNSUPPORTED, "fused max-pool: not available with injected draws");
   int rc;
-  if (inj) rc = flip ? launch_flipout_inj(linear, a, (hipStream_t)stream) : launch_reparam_inj(linear, a, (hipStream_t)stream);
-  else rc = flip ? launch_flipout(linear, a, (hipStream_t)stream) : launch_reparam(linear, a, (hipStream_t)stream);
+  FwdArgs r;   // the plan that ran
+  if (inj) rc = flip ? launch_flipout_inj(linear, a, r, (hipStream_t)stream) : launch_reparam_inj(linear, a, r, (hipStream_t)stream);
+  else rc = flip ? launch_flipout(linear, a, r, (hipStream_t)stream) : launch_reparam(linear, a, r, (hipStream_t)stream);
   if (rc == BT_OK) {   // tile geometry of the launch just made (bt_last_launch_info)
-    const long long v[16] = {a.total_blocks, a.m_tiles, a.n_tiles, a.S, a.t_NI, a.t_R, a.t_Wt, a.pixel_major, a.row_taps, a.kl_slices, a.G, a.n_bt, a.n_rt, a.n_ct, a.do_kl, 0};
+    const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, r.do_kl, 0};
     for (int i = 0; i < 16; ++i) g_launch_info[i] = v[i];
   }
   if (rc == BT_OK && kl_after) {

@@ -84,6 +84,21 @@ struct FwdArgs {
   uint32_t inv_n_sg;
 };
 
+// Host: a launch of `total` workgroups (a 1-D grid) and the workgroups that sweep a slice of the weights for the fused KL;
+// false when the grid is empty or too large.
+inline bool set_grid(FwdArgs& a, long long total) {
+  if (total <= 0 || total > 0x7FFFFFFFll) return false;
+  a.total_blocks = (int)total;
+  a.kl_slices = total < 256 ? (int)total : 256;
+  return true;
+}
+
+// Host: the packed parameters the fast and split flavours read are present, 16-byte aligned, and every operand's byte
+// offsets fit 32 bits.
+inline bool packed_ok(const FwdArgs& a) {
+  return a.mu_pk && !((((uintptr_t)a.mu_pk | (uintptr_t)a.sig_pk) & 15u)) && a.w_elems < (1ll << 29) && a.x_elems < (1ll << 29);
+}
+
 // Blocks are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2). Give every XCD a CONTIGUOUS range of
 // the logical block order, which is n-tile-major: an XCD then works on few n-tiles for all samples and m-tiles, so
 // its (mu, rho) working set stays in its own L2. Bijective for any grid size (cdna_hip_programming.md, T1).

@@ -23,28 +23,17 @@ int contraction_mode() {
 }
 
 template <int BM, int NP, int NPW, int XM, int BN = 64>
-static int launch_split_cfg(FwdArgs& a, hipStream_t stream) {
+static int launch_split_cfg(const FwdArgs& a, hipStream_t stream) {
   constexpr int lds = split_lds_bytes<BN, BM, NP>();
   static_assert(lds <= 160 * 1024, "LDS budget of one CU");
-  auto kern = fused_split_kernel<BN, BM, NP, NPW, XM>;
-  static bool flags[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "fused forward (split): hipGetDevice failed");
-  if (!flags[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return set_error(BT_ERR_HIP_BASE, "fused forward (split): cannot raise the dynamic LDS limit");
-    flags[dev] = true;
-  }
   char nm[160];
   snprintf(nm, sizeof(nm), "fused_split_kernel<%d,%d,bf16x%d,%d terms,npw=%d,xm=%d>", BN, BM, NP, NP == 3 ? 6 : 3, NPW, XM);
-  note_kernel(nm);
-  split_fill_inverses(a);
-  hipLaunchKernelGGL(kern, dim3((unsigned)a.total_blocks), dim3(256 + 64 * NPW), lds, stream, a);
-  return check_launch("fused forward (split)");
+  return launch_kernel(fused_split_kernel<BN, BM, NP, NPW, XM>, nm, "fused forward (split)", dim3((unsigned)a.total_blocks), dim3(256 + 64 * NPW),
+                       lds, lds, stream, a);
 }
 
 template <int BM, int NPW>
-static int launch_split_xm(FwdArgs& a, int mode, int xm, hipStream_t stream) {
+static int launch_split_xm(const FwdArgs& a, int mode, int xm, hipStream_t stream) {
   if (mode == 2) return launch_split_cfg<BM, 2, NPW, 0>(a, stream);   // (the opt-in 3-term form keeps the generic fetch)
   if constexpr (BM == 128) {
     if (a.bn32) {   // 32-channel tiles of a launch that would leave CUs idle (launch_split_one); same K order, same bits
@@ -67,21 +56,10 @@ static int launch_split_xm(FwdArgs& a, int mode, int xm, hipStream_t stream) {
 // Layers with <= 4 input channels per group (the ResNet stems): bt_fused_split_quad.h. Whole-image 512-wide tiles, output through
 // the LDS-staged read-out (optionally with the fused 3x3 / stride-2 max-pool, power-of-two pooled widths).
 template <bool POOL, bool WALK = false>
-static int launch_quad_cfg(FwdArgs& a, int mode, hipStream_t stream) {
+static int launch_quad_cfg(const FwdArgs& a, hipStream_t stream) {
   constexpr int lds = split_lds_bytes<64, 512, 3>();
-  auto launch = [&](auto kern, const char* nm) -> int {
-    static bool flags[2][64] = {};   // (one set per instantiation)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "fused forward (split): hipGetDevice failed");
-    if (!flags[mode == 2][dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return set_error(BT_ERR_HIP_BASE, "fused forward (split): cannot raise the dynamic LDS limit");
-      flags[mode == 2][dev] = true;
-    }
-    note_kernel(nm);
-    split_fill_inverses(a);
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.total_blocks), dim3(512), lds, stream, a);
-    return check_launch("fused forward (split, quad)");
+  auto launch = [&](auto kern, const char* nm) {
+    return launch_kernel(kern, nm, "fused forward (split, quad)", dim3((unsigned)a.total_blocks), dim3(512), lds, lds, stream, a);
   };
   // (the opt-in two-piece form is not instantiated for the stems: they run the exact split in every split mode)
   if constexpr (WALK) return launch(fused_split_quad_kernel<3, true, false, true>, "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=1,walk>");
@@ -112,45 +90,18 @@ static int quad_spw(const FwdArgs& a, long long tiles) {
   return 0;
 }
 
-static int launch_quad(FwdArgs& a, int mode, hipStream_t stream) {
-  if (a.pixel_major || a.T > 64 || !a.out_vec4 || a.HoWo < 2 || a.Wo > 512) return 1;
-  int nh, nw, dys, dxs;
-  tap_window(a.KH, a.DH, a.SH, a.PH, a.H, a.Ho, false, &nh, &dys);
-  tap_window(a.KW, a.DW, a.SW, a.PW, a.W, a.Wo, false, &nw, &dxs);
-  constexpr long long XCAP = kQuadXBytes / 24;
-  const long long PWt = (long long)(a.Wo - 1) * (dxs ? a.SW : 1) + dxs + 1;
-  int NI, R;
-  long long tiles_per_sample;
-  if (a.HoWo <= 512) {   // whole images
-    const long long PHt = (long long)(a.Ho - 1) * (dys ? a.SH : 1) + dys + 1;
-    NI = 512 / a.HoWo, R = a.Ho;
-    if (NI > a.B) NI = a.B;
-    while (NI > 1 && NI * PHt * PWt > XCAP) --NI;
-    if (NI * PHt * PWt > XCAP) return 1;
-    tiles_per_sample = (a.B + NI - 1) / NI;
-  } else {               // a band of whole rows of one image (ImageNet stems: 112 x 112 outputs -> 4 rows per tile)
-    if (a.ep_pool) return 1;   // (the pooled read-out needs whole images: the caller pools in a separate pass)
-    NI = 1, R = 512 / a.Wo;
-    while (R > 1 && ((long long)(R - 1) * (dys ? a.SH : 1) + dys + 1) * PWt > XCAP) --R;
-    if (((long long)(R - 1) * (dys ? a.SH : 1) + dys + 1) * PWt > XCAP) return 1;
-    tiles_per_sample = (long long)a.B * ((a.Ho + R - 1) / R);
-  }
-  if ((double)a.M / ((double)tiles_per_sample * 512) < 0.75) return 1;   // the wide tile must be filled
-  if (a.ep_pool) {
-    const int Wp = a.ep_Wp;
-    if ((Wp & (Wp - 1)) != 0 || Wp < 4 || Wp > 16 || a.ep_res) return 1;
-  }
-  a.n_tiles = (a.Cog + 63) / 64;
-  a.t_NI = NI, a.t_R = R, a.t_Wt = a.Wo, a.n_bt = (a.B + NI - 1) / NI, a.n_rt = (a.Ho + R - 1) / R, a.n_ct = 1, a.m_tiles = a.n_bt * a.n_rt;
+// The flavour functions below work on their own copy of the arguments and, when they launch, hand the plan that ran to `ran`.
+// Each returns BT_OK when the launch was taken, 1 when the flavour does not apply, < 0 on error.
+static int launch_quad(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
+  if (!quad_geometry(a, 512, kQuadXBytes / 24)) return 1;
   const long long tiles = (long long)a.G * a.n_tiles * a.m_tiles;
   const int spw = quad_spw(a, tiles);
   a.spw = spw ? spw : 1, a.n_sg = (a.S + a.spw - 1) / a.spw;
-  const long long total = tiles * a.n_sg;
-  if (total <= 0 || total > 0x7FFFFFFFll) return 1;
-  a.total_blocks = (int)total;
-  a.kl_slices = total < 256 ? (int)total : 256;
-  if (spw) return launch_quad_cfg<true, true>(a, mode, stream);
-  return a.ep_pool ? launch_quad_cfg<true>(a, mode, stream) : launch_quad_cfg<false>(a, mode, stream);
+  if (!set_grid(a, tiles * a.n_sg)) return 1;
+  split_fill_inverses(a);
+  ran = a;
+  if (spw) return launch_quad_cfg<true, true>(a, stream);
+  return a.ep_pool ? launch_quad_cfg<true>(a, stream) : launch_quad_cfg<false>(a, stream);
 }
 
 // 1x1 / stride-1 convolutions with K <= 256 and many pixels (the bottleneck ResNets' expanding / reducing layers): the persistent
@@ -158,7 +109,7 @@ static int launch_quad(FwdArgs& a, int mode, hipStream_t stream) {
 // general kernel's, so a layer's results do not depend on which of the two serves it.
 static std::atomic<int> g_bn32{-2};   // -2: read BT_BN32 once; -1 automatic; 0 / 1 forced (bt_debug_force_bn32)
 static std::atomic<int> g_direct_off{0};
-static int launch_direct(FwdArgs& a, hipStream_t stream) {
+static int launch_direct(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   if (g_direct_off.load(std::memory_order_relaxed)) return 1;
   if (a.ep_pool) return 1;
   // a 1x1 kernel without padding (any stride), or any window over a 1x1 image whose ONE live tap sits on the pixel (ResNet18 / CIFAR
@@ -200,29 +151,19 @@ static int launch_direct(FwdArgs& a, hipStream_t stream) {
   if (!resident) spc = (spc + 7) & ~7;   // the 8 waves walk 512-pixel tiles together
   chunks = (nsub + spc - 1) / spc;
   const long long total = pairs * chunks;
-  if (total <= 0 || total > 0x7FFFFFFFll) return 1;
+  if (!set_grid(a, total)) return 1;
   a.m_tiles = (int)chunks, a.t_NI = spc, a.t_R = 1, a.t_Wt = 64, a.n_bt = (int)chunks, a.n_rt = a.n_ct = 1;
-  a.total_blocks = (int)total;
-  a.kl_slices = total < 256 ? (int)total : 256;
   a.inv_n_tiles = inv_u32(a.n_tiles, total), a.inv_m_tiles = inv_u32(a.m_tiles, total), a.inv_S = inv_u32(a.S, total);
   a.inv_rw = inv_u32(a.HoWo, (long long)a.M + 64 * 8 * 2);   // pixel index -> (image, output position)
   a.inv_wt = inv_u32(a.Wo, a.HoWo);                          // output position -> (row, column): strided layers
-  const int lds = direct_lds_bytes(a.Cig);
-  auto launch = [&](auto kern, const char* nm, bool* flags, int max_lds) -> int {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "fused forward (split, direct): hipGetDevice failed");
-    if (!flags[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess)
-        return set_error(BT_ERR_HIP_BASE, "fused forward (split, direct): cannot raise the dynamic LDS limit");
-      flags[dev] = true;
-    }
-    note_kernel(nm);
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.total_blocks), dim3(kDirectThreads), lds, stream, a);
-    return check_launch("fused forward (split, direct)");
+  ran = a;
+  // (the LDS limit is raised to the largest launch of each variant: K = 256 resident, any K streamed)
+  auto launch = [&](auto kern, const char* nm, int max_lds) {
+    return launch_kernel(kern, nm, "fused forward (split, direct)", dim3((unsigned)a.total_blocks), dim3(kDirectThreads), direct_lds_bytes(a.Cig),
+                         max_lds, stream, a);
   };
-  static bool fr[64] = {}, fs[64] = {};
-  if (resident) return launch(fused_split_direct_kernel<true>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,resident W>", fr, direct_lds_bytes(kDirectMaxK));
-  return launch(fused_split_direct_kernel<false>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,streamed W>", fs, direct_lds_bytes(kDirectMaxK + 1));
+  if (resident) return launch(fused_split_direct_kernel<true>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,resident W>", direct_lds_bytes(kDirectMaxK));
+  return launch(fused_split_direct_kernel<false>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,streamed W>", direct_lds_bytes(kDirectMaxK + 1));
 }
 
 // Layers whose output map is one pixel and whose batch is small (Linear, CIFAR-sized layer4, the classifier head): the split-K kernel of
@@ -261,7 +202,7 @@ long long skinny_scratch_bytes(const bt_conv2d_geom& g, int S) {
   return skinny_plan(g.B, g.Ci, g.H, g.W, g.Co, g.kh, g.kw, g.ph, g.pw, g.dh, g.dw, g.groups, Ho, Wo, S, &p) ? p.scratch : 0;
 }
 static std::atomic<int> g_skinny_off{-1};
-static int launch_skinny(FwdArgs& a, hipStream_t stream) {
+static int launch_skinny(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   int off = g_skinny_off.load(std::memory_order_relaxed);
   if (off < 0) {   // env BT_NO_SKINNY=1: measurement knob (tools/trace_layers.py), like the test hook below
     const char* e = getenv("BT_NO_SKINNY");
@@ -276,39 +217,31 @@ static int launch_skinny(FwdArgs& a, hipStream_t stream) {
   a.sk_ks = p.ks, a.sk_cpt = p.cpt, a.sk_nsl = p.nsl, a.sk_kh0 = p.kh0, a.sk_nh = p.nh, a.sk_kw0 = p.kw0, a.sk_nw = p.nw;
   a.n_tiles = p.n_tiles, a.m_tiles = p.m_tiles;
   a.t_NI = kSkinnyCols, a.t_R = 1, a.t_Wt = 1, a.n_bt = p.m_tiles, a.n_rt = a.n_ct = 1;
-  a.total_blocks = (int)(p.tiles * p.nsl);
-  a.kl_slices = a.total_blocks < 256 ? a.total_blocks : 256;   // (spread over every workgroup the sweep lengthened all of them: 50 -> 62 us on ResNet18 layer4)
+  // every workgroup of the split-K grid (skinny_plan bounds it); the KL sweep keeps 256 slices (spread over every workgroup it
+  // lengthened all of them: 50 -> 62 us on ResNet18 layer4)
+  if (!set_grid(a, p.tiles * p.nsl)) return 1;
   a.x_vec = (a.HW == 1 && ((((uintptr_t)a.x) & 15u) == 0) && (a.x_sample_stride & 3) == 0 && (a.Ci & 3) == 0) ? 1 : 0;
-  const int lds = skinny_lds_bytes(p.ks);
-  static bool flags[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "fused forward (split, skinny): hipGetDevice failed");
-  if (!flags[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fused_split_skinny_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, skinny_lds_bytes(128)) != hipSuccess)
-      return set_error(BT_ERR_HIP_BASE, "fused forward (split, skinny): cannot raise the dynamic LDS limit");
-    flags[dev] = true;
-  }
-  note_kernel(p.ks == 128 ? "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 128>" : "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 64>");
-  hipLaunchKernelGGL(fused_split_skinny_kernel, dim3((unsigned)a.total_blocks), dim3(kSkinnyThreads), lds, stream, a);
-  return check_launch("fused forward (split, skinny)");
+  ran = a;
+  return launch_kernel(fused_split_skinny_kernel,
+                       p.ks == 128 ? "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 128>" : "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 64>",
+                       "fused forward (split, skinny)", dim3((unsigned)a.total_blocks), dim3(kSkinnyThreads), skinny_lds_bytes(p.ks), skinny_lds_bytes(128),
+                       stream, a);
 }
 
-// Returns BT_OK when the launch was taken, 1 when this flavour does not apply (the caller runs the fp32 kernels), < 0 on error.
-static int launch_split_one(FwdArgs& a, hipStream_t stream) {
+// The stems', split-K, direct and general split kernels for one tile kind (the caller runs the fp32 kernels when none applies).
+static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   const int mode = contraction_mode();
   if (mode == 1) return 1;
   // Reparameterization, on-chip draws, packed parameters, 32-bit byte offsets
-  if (!a.mu_pk || (((uintptr_t)a.mu_pk | (uintptr_t)a.sig_pk) & 15u) || a.w_elems >= (1ll << 29) || a.x_elems >= (1ll << 29)) return 1;
-  if (a.Cig <= 4) return launch_quad(a, mode, stream);   // the stems
+  if (!packed_ok(a)) return 1;
+  if (a.Cig <= 4) return launch_quad(a, ran, stream);   // the stems
   // whole channel octets, at most 9 taps, no fused pooling
   if ((a.Cig & 7) || a.ep_pool) return 1;
   if (mode != 2) {   // (the flavours with a single live tap per slice / layer take any window size)
-    FwdArgs k = a;
-    const int rck = launch_skinny(k, stream);
-    if (rck <= 0) { a = k; return rck; }
-    FwdArgs d = a;
-    const int rcd = launch_direct(d, stream);
-    if (rcd <= 0) { a = d; return rcd; }
+    const int rck = launch_skinny(a, ran, stream);
+    if (rck <= 0) return rck;
+    const int rcd = launch_direct(a, ran, stream);
+    if (rcd <= 0) return rcd;
   }
   if (a.T > 9) return 1;
   const int Mdom = a.pixel_major ? a.B : a.M;
@@ -319,18 +252,9 @@ static int launch_split_one(FwdArgs& a, hipStream_t stream) {
   const int live256 = Mdom >= 256 ? split_geometry<256>(b256) : 0;
   const int live128 = split_geometry<128>(b128);
   const long long per = (long long)a.G * a.n_tiles * a.S;
-  // Cost of a launch in column-equivalents: rounds of 256 workgroups x (the tile's columns, but never less than the weight
-  // synthesis of a stage costs the producers, + the prologue / output stage of a workgroup). Tiles that waste more than a
-  // quarter of their columns are not considered.
-  auto cost = [&](int live, int BM, const FwdArgs& b) -> double {
-    if (!live) return 1e30;
-    const double eff = (double)a.M / ((double)b.m_tiles * BM);
-    if (eff < 0.75) return 1e30;
-    const double rounds = (double)((per * b.m_tiles + 255) / 256);
-    const int synth = BM == 128 ? 128 : 256;   // the producers' floor: the 128-wide tile has 8 producer waves, the others 4
-    return rounds * ((BM > synth ? BM : synth) + 96);
-  };
-  const double c512 = cost(live512, 512, b512), c256 = cost(live256, 256, b256), c128 = cost(live128, 128, b128);
+  // the producers' synthesis floor: the 128-wide tile has 8 producer waves, the others 4
+  const double c512 = split_tile_cost(b512, live512, 512, 256, 96), c256 = split_tile_cost(b256, live256, 256, 256, 96),
+               c128 = split_tile_cost(b128, live128, 128, 128, 96);
   int bm = 0;
   static const int force_bm = [] { const char* e = getenv("BT_FORCE_BM"); return e ? atoi(e) : 0; }();   // measurement knob: prefer this tile width where it is eligible
   if (force_bm == 512 && c512 < 1e30) bm = 512;
@@ -356,12 +280,8 @@ static int launch_split_one(FwdArgs& a, hipStream_t stream) {
     const long long wgs64 = per * a.m_tiles;
     a.bn32 = bn32_env >= 0 ? (bn32_env ? 1 : 0) : (2 * wgs64 <= 256 ? 1 : 0);
   }
-  long long per_t = per;
-  if (a.bn32) a.n_tiles = (a.Cog + 31) / 32, per_t = (long long)a.G * a.n_tiles * a.S;
-  const long long total = per_t * a.m_tiles;
-  if (total <= 0 || total > 0x7FFFFFFFll) return 1;
-  a.total_blocks = (int)total;
-  a.kl_slices = total < 256 ? (int)total : 256;
+  if (a.bn32) a.n_tiles = (a.Cog + 31) / 32;
+  if (!set_grid(a, (long long)a.G * a.n_tiles * a.S * a.m_tiles)) return 1;
   // x fetch mode (bt_fused_split.h): tiny input planes are read as 16-byte vectors
   const bool xal = (((uintptr_t)a.x) & 15u) == 0 && (a.x_sample_stride & 3) == 0;
   int xm = 0;
@@ -371,6 +291,8 @@ static int launch_split_one(FwdArgs& a, hipStream_t stream) {
   else if (xal && bm == 128 && !a.pixel_major && a.H == 2 && a.W == 2 && split_plane_flat(a)) xm = 2;   // whole 2x2 planes (a strided 3x3 down to 1x1 maps)
   else if (xal && bm != 512 && a.row_taps && a.H == 2 && a.W == 2 && a.KW == 3 && a.PW == 1 && a.SW == 1 && a.DW == 1) xm = 2;   // a row tile's patch is the whole 2x2 plane
   else if (xal && a.pixel_major && a.H == 2 && a.W == 2 && a.KH == 3 && a.KW == 3 && a.PH == 1 && a.PW == 1 && a.SH == 1 && a.SW == 1 && a.DH == 1 && a.DW == 1) xm = 2;
+  split_fill_inverses(a);
+  ran = a;
   if (bm == 512) return launch_split_xm<512, 4>(a, mode, xm, stream);
   if (bm == 256) return launch_split_xm<256, 8>(a, mode, xm, stream);
   return launch_split_xm<128, 8>(a, mode, xm, stream);
@@ -379,27 +301,22 @@ static int launch_split_one(FwdArgs& a, hipStream_t stream) {
 // Pixel-major tiles (2..4-pixel outputs) prune the padding taps per pixel: the first choice. When their patch does not fit (a
 // stride-2 3x3 from 4x4 to 2x2 maps: up to 9 input pixels per output pixel and image), tiles of whole images -- every active
 // tap once for all pixels -- usually do, and beat the fp32 kernels (165 -> 104 us on ResNet18's layer3.0.conv1).
-int launch_split(FwdArgs& a, hipStream_t stream) {
-  FwdArgs t = a;
+int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   // Two-row maps with a stride-1 window (ResNet18 / CIFAR layer3: 3x3 on 2x2): tiles of (images x ONE output row) before the
   // pixel-major ones. A row's pixels share 6 of the 9 taps: 3 MFMA steps and 6 weight draws per octet for 2 pixels instead of
   // 2 x (2 steps, 4 draws), and half the workgroups. The choice is geometric (never a matter of S or of the tile width), so
   // the tap pairing -- the K order -- of a layer stays the same for every launch split.
   if (a.pixel_major && a.Ho == 2 && a.Wo >= 2 && a.SH == 1 && a.KH == 3 && a.PH == 1 && a.DH == 1 && !a.ep_pool) {
+    FwdArgs t = a;
     t.pixel_major = 0, t.out_vec4 = 0, t.row_taps = 1;
-    const int rcr = launch_split_one(t, stream);
-    if (rcr <= 0) { a = t; return rcr; }
-    t = a;
+    const int rc = launch_split_one(t, ran, stream);
+    if (rc <= 0) return rc;
   }
-  int rc = launch_split_one(t, stream);
-  if (rc == 1 && a.pixel_major) {
-    t = a;
-    t.pixel_major = 0;
-    t.out_vec4 = 0;   // 2..4-pixel rows: the scalar output stage
-    rc = launch_split_one(t, stream);
-  }
-  if (rc <= 0) a = t;   // the plan that ran (bt_last_launch_info reads it)
-  return rc;
+  const int rc = launch_split_one(a, ran, stream);
+  if (rc != 1 || !a.pixel_major) return rc;
+  a.pixel_major = 0;
+  a.out_vec4 = 0;   // 2..4-pixel rows: the scalar output stage
+  return launch_split_one(a, ran, stream);
 }
 
 }  // namespace bt

@@ -146,4 +146,49 @@ static int split_geometry(FwdArgs& a) {
   return NI * R * Wt;
 }
 
+// Cost of a launch of BM-wide tiles (b: split_geometry's plan, live: its return) in column-equivalents: rounds of 256 workgroups x
+// (the tile's columns, but never less than the weight synthesis of a stage costs the producers (synth), + the prologue / output
+// stage of a workgroup (fixed)). Tiles that do not fit or waste more than a quarter of their columns cost 1e30.
+static double split_tile_cost(const FwdArgs& b, int live, int BM, int synth, int fixed) {
+  if (!live) return 1e30;
+  const double eff = (double)b.M / ((double)b.m_tiles * BM);
+  if (eff < 0.75) return 1e30;
+  const double rounds = (double)(((long long)b.G * b.n_tiles * b.S * b.m_tiles + 255) / 256);
+  return rounds * ((BM > synth ? BM : synth) + fixed);
+}
+
+// Tiles of the stems' quad flavour (bt_fused_split_quad.h): BM columns of whole images, or of a band of whole rows of one image,
+// whose patch fits xcap pixels. Fills the tile fields; false when the layer has no such tile.
+static bool quad_geometry(FwdArgs& a, int BM, long long xcap) {
+  if (a.pixel_major || a.T > 64 || !a.out_vec4 || a.HoWo < 2 || a.Wo > BM) return false;
+  int nh, nw, dys, dxs;
+  tap_window(a.KH, a.DH, a.SH, a.PH, a.H, a.Ho, false, &nh, &dys);
+  tap_window(a.KW, a.DW, a.SW, a.PW, a.W, a.Wo, false, &nw, &dxs);
+  const long long PWt = (long long)(a.Wo - 1) * (dxs ? a.SW : 1) + dxs + 1;
+  auto rows_px = [&](int R) { return ((long long)(R - 1) * (dys ? a.SH : 1) + dys + 1) * PWt; };
+  int NI, R;
+  long long tiles_per_sample;
+  if (a.HoWo <= BM) {   // whole images
+    NI = BM / a.HoWo, R = a.Ho;
+    if (NI > a.B) NI = a.B;
+    while (NI > 1 && NI * rows_px(R) > xcap) --NI;
+    if (NI * rows_px(R) > xcap) return false;
+    tiles_per_sample = (a.B + NI - 1) / NI;
+  } else {              // a band of whole rows of one image (ImageNet stems: 112 x 112 outputs -> 4 rows per 512-wide tile)
+    if (a.ep_pool) return false;   // (the pooled read-out needs whole images: the caller pools in a separate pass)
+    NI = 1, R = BM / a.Wo;
+    while (R > 1 && rows_px(R) > xcap) --R;
+    if (rows_px(R) > xcap) return false;
+    tiles_per_sample = (long long)a.B * ((a.Ho + R - 1) / R);
+  }
+  if ((double)a.M / ((double)tiles_per_sample * BM) < 0.75) return false;   // the wide tile must be filled
+  if (a.ep_pool) {
+    const int Wp = a.ep_Wp;
+    if ((Wp & (Wp - 1)) != 0 || Wp < 4 || Wp > 16 || a.ep_res) return false;
+  }
+  a.n_tiles = (a.Cog + 63) / 64;
+  a.t_NI = NI, a.t_R = R, a.t_Wt = a.Wo, a.n_bt = (a.B + NI - 1) / NI, a.n_rt = (a.Ho + R - 1) / R, a.n_ct = 1, a.m_tiles = a.n_bt * a.n_rt;
+  return true;
+}
+
 }  // namespace bt

@@ -279,14 +279,6 @@ __global__ __launch_bounds__(1024) void poison_lds_kernel(unsigned* sink) {
 }  // namespace bt
 extern "C" int bt_debug_poison_lds(void* scratch_word, bt_stream_t stream) {
   using namespace bt;
-  static bool flags[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "bt_debug_poison_lds: hipGetDevice failed");
-  if (!flags[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(poison_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return set_error(BT_ERR_HIP_BASE, "bt_debug_poison_lds: cannot raise the dynamic LDS limit");
-    flags[dev] = true;
-  }
-  hipLaunchKernelGGL(poison_lds_kernel, dim3(1024), dim3(1024), 160 * 1024, (hipStream_t)stream, (unsigned*)scratch_word);
-  return check_launch("bt_debug_poison_lds");
+  return launch_kernel(poison_lds_kernel, nullptr, "bt_debug_poison_lds", dim3(1024), dim3(1024), 160 * 1024, 160 * 1024, (hipStream_t)stream,
+                       (unsigned*)scratch_word);
 }

@@ -273,20 +273,11 @@ extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, cons
   // fingerprint and dirty flag, so a refusal after it would leave the packs stale against fingerprints that say they are current.
   const size_t lds = (size_t)max_taps * (kPackCh + 1) * sizeof(float2);
   if (max_taps > 128) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_sync: kernels larger than 128 taps are not supported");
-  if (lds > 48 * 1024) {   // (above the default dynamic-LDS limit: 11 x 11 kernels and larger)
-    static bool flags[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(BT_ERR_HIP_BASE, "bt_pack_sync: hipGetDevice failed");
-    if (!flags[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(pack_dirty_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * (kPackCh + 1) * (int)sizeof(float2)) != hipSuccess)
-        return set_error(BT_ERR_HIP_BASE, "bt_pack_sync: cannot raise the dynamic LDS limit");
-      flags[dev] = true;
-    }
-  }
+  const int lds_limit = 128 * (kPackCh + 1) * (int)sizeof(float2);   // (above the default dynamic-LDS limit: 11 x 11 kernels and larger)
+  if (int rc = raise_lds_limit(reinterpret_cast<const void*>(pack_dirty_kernel), lds_limit, "bt_pack_sync")) return rc;
   hipLaunchKernelGGL(pack_fingerprint_kernel, dim3(fblocks), dim3(kFpThreads), 0, (hipStream_t)stream, fs, ws_counter(workspace), ws_slots(workspace), fblocks);
   if (int rc = check_launch("bt_pack_sync (fingerprint)")) return rc;
-  hipLaunchKernelGGL(pack_dirty_kernel, dim3(pblocks), dim3(256), lds, (hipStream_t)stream, pk);
-  return check_launch("bt_pack_sync (pack)");
+  return launch_kernel(pack_dirty_kernel, nullptr, "bt_pack_sync (pack)", dim3(pblocks), dim3(256), (int)lds, lds_limit, (hipStream_t)stream, pk);
 }
 
 extern "C" int bt_pack_sync(int32_t n_segments, const bt_pack_seg* segs, void* workspace, size_t workspace_bytes, bt_stream_t stream) {

@@ -190,8 +190,9 @@ def test_family_on_chip_draws_match_fp64_oracle(rid, cls, ctor, xshape, want):
 
 
 def test_family_table_reaches_every_flavour():
-    """Every row lands on the flavour it was chosen for (one S = 1 forward each), and the table reaches them all."""
-    from bayesian_torch_amd import rng
+    """Every row lands on the flavour it was chosen for (one S = 1 forward each), and the table reaches them all. The launch
+    info reports the plan that ran: one workgroup per (group, channel tile, sample, pixel tile), several for the split-K flavour."""
+    from bayesian_torch_amd import _lib, rng
     rng.set_mode("philox")
     rng.manual_seed(99)
     seen = {}
@@ -199,9 +200,15 @@ def test_family_table_reaches_every_flavour():
         layer = _make(cls, ctor, 1)
         with torch.no_grad():
             layer(torch.randn(xshape).cuda(), return_kl=False)
-        name = layer._last["kernel"]
-        print(f"{rid:24s} -> {flavour(name):6s} {name}")
+        name, li = layer._last["kernel"], _lib.last_launch_info()
+        print(f"{rid:24s} -> {flavour(name):6s} {name} {li}")
         assert flavour(name) == want, (rid, name, want)
+        grid = li["groups"] * li["n_tiles"] * li["S"] * li["m_tiles"]
+        assert li["workgroups"] > 0 and grid > 0, (rid, name, li)
+        if want == "skinny":
+            assert li["workgroups"] % grid == 0, (rid, name, li)
+        else:
+            assert li["workgroups"] == grid, (rid, name, li)
         seen.setdefault(want, []).append(rid)
     assert set(seen) == set(FLAVOURS), seen
     classes = {r[1] for r in ROWS}

@@ -24,7 +24,7 @@ GEOMS = {
     "groups 2, 3x2 kernel, stride (2,1)": (32, 48, (3, 2), (2, 1), (1, 0), 1, 2, 16, 9, 8, 1, True),
     "K = 4608 (512x512 3x3 on 4x4)": (512, 64, (3, 3), 1, 1, 1, 1, 4, 4, 32, 1, False),
     "layer4 512x512 3x3 on 1x1 maps (128 tile, 1 of 9 taps, xm=1)": (512, 512, (3, 3), 1, 1, 1, 1, 1, 1, 128, 2, False),
-    "layer3 256x256 3x3 on 2x2 maps (pixel-major, 4 of 9 taps, xm=2)": (256, 256, (3, 3), 1, 1, 1, 1, 2, 2, 128, 2, False),
+    "layer3 256x256 3x3 on 2x2 maps (row tiles, 6 of 9 taps, xm=2)": (256, 256, (3, 3), 1, 1, 1, 1, 2, 2, 128, 2, False),
     "layer3.0.conv1 128->256 3x3 s2 4x4->2x2 (pixel-major, generic fetch)": (128, 256, (3, 3), 2, 1, 1, 1, 4, 4, 128, 2, True),
     "layer4.0.downsample 256->512 1x1 s2 2x2->1x1": (256, 512, (1, 1), 2, 0, 1, 1, 2, 2, 128, 2, False),
     "1x1 maps, partial batch tile (B = 120)": (64, 96, (3, 3), 1, 1, 1, 1, 1, 1, 120, 1, True),
@@ -37,6 +37,19 @@ GEOMS = {
 
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+# the tile a case's label names, as bt_last_launch_info reports its automatic-mode launch (2x2 maps: row tiles for
+# Reparameterization; Flipout's pixel-major patch of 128 images does not fit, so whole images)
+LABELLED_TILES = {"layer3 256x256 3x3 on 2x2 maps (row tiles, 6 of 9 taps, xm=2)": dict(row_tiles=1, pixel_major=0),
+                  "flip layer3 256x256 3x3 on 2x2 maps (128 tile of whole images)": dict(row_tiles=0, pixel_major=0, t_R=2, t_Wt=2)}
+
+
+def _check_labelled_tile(name, kn):
+    from bayesian_torch_amd import _lib
+    want = LABELLED_TILES.get(name, {})
+    li = _lib.last_launch_info()
+    assert {k: li[k] for k in want} == want, (name, kn, li)
 
 
 def _case(name):
@@ -76,6 +89,7 @@ def test_split_kernel_vs_c_oracle_and_fp32_kernel(name):
             pytest.skip("not eligible for the split flavour at this size: " + kn)
     # (1x1 layers with K <= 256: the direct kernel; narrow one-pixel heads: the split-K kernel)
     assert ("fused_split_kernel" in kn or "fused_split_direct_kernel" in kn or "fused_split_skinny_kernel" in kn) and "6 terms" in kn, kn
+    _check_labelled_tile(name, kn)
     out32, kn32 = _run(mu, rho, mb, rb, x, conv, S, 1)
     assert "split" not in kn32, kn32
     dev = torch.device("cuda")
@@ -276,7 +290,7 @@ FLIP_GEOMS = {
     "flip 1x1 bottleneck 64->256 8x8 (one tap: octet pairs)": (64, 256, (1, 1), 1, 0, 1, 1, 8, 8, 64, 2, True),
     "flip row bands 16x32 3x3 28x28, ragged channels": (16, 40, (3, 3), 1, 1, 1, 1, 28, 28, 4, 1, True),
     "flip W % 4 != 0 (generic fetch) 24x64 3x3 6x6": (24, 64, (3, 3), 1, 1, 1, 1, 6, 6, 64, 2, True),
-    "flip layer3 256x256 3x3 on 2x2 maps (pixel-major 128 tile, xm=2)": (256, 256, (3, 3), 1, 1, 1, 1, 2, 2, 128, 2, False),
+    "flip layer3 256x256 3x3 on 2x2 maps (128 tile of whole images)": (256, 256, (3, 3), 1, 1, 1, 1, 2, 2, 128, 2, False),
     "flip layer4 512x512 3x3 on 1x1 maps (128 tile, one tap, xm=1)": (512, 512, (3, 3), 1, 1, 1, 1, 1, 1, 128, 2, True),
     "flip layer3.0.conv1 128->256 3x3 s2 4x4->2x2 (pixel-major, generic fetch)": (128, 256, (3, 3), 2, 1, 1, 1, 4, 4, 128, 2, True),
     "flip layer4.0.downsample 256->512 1x1 s2 2x2->1x1 (one tap)": (256, 512, (1, 1), 2, 0, 1, 1, 2, 2, 128, 2, False),
@@ -320,6 +334,7 @@ def test_split_flipout_vs_c_oracle_and_fp32_kernel(name):
         # 4x the pixels it writes: such patches may not fit the 301 pixels the two weight images leave
         pytest.skip("not eligible for the split Flipout: " + kn)
     assert "fused_split_kernel" in kn and "flip" in kn, kn
+    _check_labelled_tile(name, kn)
     out32, _, kn32 = _run_flip(mu, rho, mb, rb, x, conv, S, 1)
     assert "split" not in kn32 and "flip" in kn32, kn32
     dev = torch.device("cuda")
@@ -455,7 +470,7 @@ print(digest(False, 64, 64, 3, 1, 1, 8, 128, 2), digest(False, 64, 128, 1, 2, 0,
 
 POISON_CASES = ["layer1 64x64 3x3 8x8 (512 tile, 9 taps)", "odd octet count, one tap", "9 octets, partial channel tile, bias",
                 "downsample 64->128 1x1 s2 (one tap: octet pairs)", "1x1 maps, partial batch tile (B = 120)", "groups 2, 3x2 kernel, stride (2,1)",
-                "layer3 256x256 3x3 on 2x2 maps (pixel-major, 4 of 9 taps, xm=2)", "14x14 maps 3x3 (W % 4 != 0: whole planes fetched flat)",
+                "layer3 256x256 3x3 on 2x2 maps (row tiles, 6 of 9 taps, xm=2)", "14x14 maps 3x3 (W % 4 != 0: whole planes fetched flat)",
                 "28x28 -> 14x14 1x1 s2 (every second column, XM 4)", "row bands 64x64 3x3 56x56"]
 
 
