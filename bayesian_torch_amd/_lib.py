@@ -17,6 +17,7 @@ PACK_MAX_SEGMENTS = 64
 KL_RHO_IS_SIGMA = 1
 KL_PRIOR_LAPLACE = 2
 PRIOR_NORMAL, PRIOR_LAPLACE = 0, 1
+DRAWS_EPS_PACKED = 1   # bt_rng.flags: eps_w holds [S] packed images (bt_pack_eps)
 
 _f32p = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -24,7 +25,7 @@ _vp = C.c_void_p
 
 class bt_rng(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("call_base_dev", _vp), ("call", C.c_uint32), ("layer_id", C.c_uint32),
-                ("sample0", C.c_uint32), ("reserved", C.c_uint32)]
+                ("sample0", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class bt_params(C.Structure):
@@ -84,6 +85,7 @@ _PROTOS = {
     "bt_pack_sync": (C.c_int, [C.c_int32, C.POINTER(bt_pack_seg), _vp, C.c_size_t, _vp]),
     "bt_pack_sync_kl": (C.c_int, [C.c_int32, C.POINTER(bt_pack_seg), C.POINTER(bt_pack_kl), _vp, C.c_size_t, _vp]),
     "bt_pack_params": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "bt_pack_eps": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "bt_rng_normal_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "bt_rng_sign_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, _vp, _vp]),
     "bt_rng_philox_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

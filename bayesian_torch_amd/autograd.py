@@ -73,7 +73,8 @@ class FusedForward(torch.autograd.Function):
                                   eps_w=o.get("eps_w"), eps_b=o.get("eps_b"), sign_in=o.get("sign_in"), sign_out=o.get("sign_out"),
                                   packed=o.get("packed"), workspace_owner=o.get("workspace_owner", ("layer", o["layer_id"])), call_base=o.get("call_base"),
                                   priors=None if (klo is None or stub) else tuple(klo[:4]), want_kl=klo is not None and not stub,
-                                  prior_type="normal" if klo is None else klo[4])
+                                  prior_type="normal" if klo is None else klo[4],
+                                  inject_path="general")      # (rng.set_inject_path covers inference; a training forward keeps its kernel)
         if stub:      # the VALUE comes from one launch over the whole model (KLValue, get_kl_loss); this output only routes its gradient here
             kl = out.new_empty(())
         ctx.o = o

@@ -9,6 +9,8 @@ int launch_reparam(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stre
 int launch_reparam_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
+int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);   // bt_fused_split.hip: 0 taken, 1 not applicable, < 0 error
+int contraction_mode();
 
 static unsigned long long* g_dbg = nullptr;
 static thread_local long long g_launch_info[16] = {};
@@ -41,6 +43,20 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
   if (!flip && (d->sign_in || d->sign_out)) return bad("sign tensors are Flipout-only");
   if (ep && ((ep->scale == nullptr) != (ep->shift == nullptr))) return bad("epilogue scale and shift must both be given or both be NULL");
   if (ep && ep->residual_sample_stride < 0) return bad("negative residual_sample_stride");
+  // packed draws (bt_pack_eps): the split-precision kernels' injected instantiations, or nothing
+  if (d->rng.flags & ~BT_DRAWS_EPS_PACKED) return bad("unknown bt_rng.flags bit");
+  const bool eps_packed = (d->rng.flags & BT_DRAWS_EPS_PACKED) != 0;
+  if (eps_packed) {
+    auto unsupported = [&](const char* what) {
+      snprintf(msg, sizeof(msg), "%s: BT_DRAWS_EPS_PACKED: %s", who, what);
+      return set_error(BT_ERR_UNSUPPORTED, msg);
+    };
+    if (!d->eps_w) return bad("BT_DRAWS_EPS_PACKED without eps_w");
+    if (flip || d->sign_in || d->sign_out) return unsupported("Flipout / sign tensors are not served (inject the natural layout)");
+    if (!p->mu_packed || !p->sigma_packed) return bad("BT_DRAWS_EPS_PACKED needs mu_packed / sigma_packed");
+    if (!al16(d->eps_w)) return bad("BT_DRAWS_EPS_PACKED: eps_w must be 16-byte aligned");
+    if (contraction_mode() != 0) return unsupported("the contraction is forced to f32 / bf16x2 (bt_set_contraction, BT_CONTRACTION): only the exact split reads packed draws");
+  }
 
   const int Ho = (g.H + 2 * g.ph - g.dh * (g.kh - 1) - 1) / g.sh + 1;
   const int Wo = (g.W + 2 * g.pw - g.dw * (g.kw - 1) - 1) / g.sw + 1;
@@ -106,10 +122,16 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
   const bool all_inj = inj && (!p->mu_b || d->eps_b) && (!flip || (d->sign_in && d->sign_out));
   const bool none_inj = !d->eps_w && !d->eps_b && !d->sign_in && !d->sign_out;
   if (!all_inj && !none_inj) return bad("inject all draws of the layer (eps_w, eps_b when biased, both sign tensors for Flipout) or none");
-  if (inj && a.ep_pool) return set_error(BT_ERR_UNSUPPORTED, "fused max-pool: not available with injected draws");
+  if (inj && a.ep_pool && !eps_packed) return set_error(BT_ERR_UNSUPPORTED, "fused max-pool: not available with injected draws");
   int rc;
   FwdArgs r;   // the plan that ran
-  if (inj) rc = flip ? launch_flipout_inj(linear, a, r, (hipStream_t)stream) : launch_reparam_inj(linear, a, r, (hipStream_t)stream);
+  if (eps_packed) {   // the split chain alone; it launches nothing when it declines
+    rc = launch_split(a, r, (hipStream_t)stream);
+    if (rc == 1) {
+      snprintf(msg, sizeof(msg), "%s: BT_DRAWS_EPS_PACKED: no split-precision flavour takes this launch (inject the natural layout)", who);
+      return set_error(BT_ERR_UNSUPPORTED, msg);
+    }
+  } else if (inj) rc = flip ? launch_flipout_inj(linear, a, r, (hipStream_t)stream) : launch_reparam_inj(linear, a, r, (hipStream_t)stream);
   else rc = flip ? launch_flipout(linear, a, r, (hipStream_t)stream) : launch_reparam(linear, a, r, (hipStream_t)stream);
   if (rc == BT_OK) {   // tile geometry of the launch just made (bt_last_launch_info)
     const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, r.do_kl, 0};

@@ -80,7 +80,7 @@ static int launch_cfg(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   static_assert(lds <= 160 * 1024, "LDS budget of one CU");
   a.n_tiles = (a.Cog + BN - 1) / BN;
   bool fast = false;
-  if constexpr (!INJ) fast = fast_geometry<BM, LINEAR, FLIP>(a);  // injected draws are the parity/debug mode: always the general kernel
+  if constexpr (!INJ) fast = fast_geometry<BM, LINEAR, FLIP>(a);  // draws injected in the NATURAL layout: always the general kernel (packed ones, BT_DRAWS_EPS_PACKED, never come here: bt_fused_split_inj.hip)
   if (a.ep_pool && !(fast && TRANS && !FLIP && BM >= 128 && a.x_rows && a.out_vec4 && !a.pixel_major && a.t_R == a.Ho && a.t_Wt == a.Wo))
     return set_error(BT_ERR_UNSUPPORTED, "fused max-pool: this launch's tiles do not hold whole output images");
   if (!fast) {  // general kernel: BM consecutive (b, ho, wo), or pixel-major

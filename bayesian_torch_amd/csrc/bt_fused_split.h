@@ -99,8 +99,14 @@ __device__ __forceinline__ int div_small(int n, int d) { return d == 1 ? n : d =
 // issues the 6 terms of x*mu, flips the sign bits of its x fragments in registers (-(h+m+l) = -h-m-l: the split of -v is the
 // negated split of v), and issues the 6 terms of (x o s_in)*(sigma*eps) into the second accumulator set. 4 consumer waves of
 // 32 channels x BM/2 pixels each (2 x 2), BM = 256 or 128. s_out meets the second set in the read-out.
-template <int BN, int BM, int NP, int NPW, int XM, bool FLIP = false>
+//
+// INJ (Reparameterization, bt_fused_split_inj.hip): the draws are READ -- a.eps_w holds [S] images in the layout of mu_packed
+// (bt_pack_eps), so a unit's four draws are one more 16-byte load at the offset of its two parameter loads, issued with them (one
+// stage ahead), and a.eps_b [S][Co] the bias draws. Everything behind the draw is the on-chip code: the same eps bits give the same
+// output bits.
+template <int BN, int BM, int NP, int NPW, int XM, bool FLIP = false, bool INJ = false>
 __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdArgs a) {
+  static_assert(!(FLIP && INJ), "injected draws: Reparameterization only");
   static_assert((BN == 64 && (BM == 512 || BM == 256 || BM == 128)) || (BN == 32 && BM == 128 && !FLIP), "tile shapes of this flavour");
   static_assert(!FLIP || ((BM == 256 || BM == 128) && NP == 3), "Flipout: the 64 x 256 / 64 x 128 tiles, exact split");
   constexpr int kProducers = 64 * NPW, kThreadsAll = 256 + kProducers;
@@ -261,6 +267,9 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   const __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.mu_pk), 0, pk_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sig_pk), 0, pk_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)(a.x_elems * 4), 0x00020000);
+  // INJ: this sample's image of the packed draws (a wave-uniform base: the descriptor stays in SGPRs)
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_ep =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
   auto ldf = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0)); };
   auto ldf4 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0)); };
 
@@ -410,6 +419,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     const int wave_u0 = __builtin_amdgcn_readfirstlane(ptid & ~63);
     if (stamp0) dbg_[213] = __builtin_amdgcn_s_memtime();
     float4 mu[UMAX], rs[UMAX];
+    [[maybe_unused]] float4 epl[INJ ? UMAX : 1];  // INJ: the units' draws, loaded with their parameters
     auto load_w = [&](int st) {
       const int oct0 = st * NO;
 #pragma unroll
@@ -418,6 +428,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           const bool in = l_off[i] >= 0 && oct0 + u_ol[i] < G8 && e_off[i] != (kOOB >> 2);
           const uint32_t sb = guard_off(in, 4u * (e_off[i] + (uint32_t)(8 * oct0)));
           mu[i] = ldf4(r_mu, sb), rs[i] = ldf4(r_rs, sb);
+          if constexpr (INJ) epl[i] = ldf4(r_ep, sb);  // masked units read 0.0
         }
       }
     };
@@ -625,8 +636,10 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         float ep[UMAX][4];
 #pragma unroll
         for (int i = 0; i < UMAX; ++i)
-          if (u_live[i])  // wave-uniform
-            philox_normal4(key_w, sample, (e_off[i] + (uint32_t)(8 * oct0)) >> 2, ep[i]);
+          if (u_live[i]) {  // wave-uniform
+            if constexpr (INJ) ep[i][0] = epl[i].x, ep[i][1] = epl[i].y, ep[i][2] = epl[i].z, ep[i][3] = epl[i].w;
+            else philox_normal4(key_w, sample, (e_off[i] + (uint32_t)(8 * oct0)) >> 2, ep[i]);
+          }
         if (pstamp && st == 3) dbg_[252] = __builtin_amdgcn_s_memtime();
         // ---- sampled weights -> pieces -> LDS ----
 #pragma unroll
@@ -669,12 +682,17 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       const int co_g = n0 + ptid;
       if (a.mu_b && co_g < a.Cog) {
         const int co = g * a.Cog + co_g;
-        RngKey kb = key_w;
-        kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-        float z[4];
-        philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-        const int sel = co & 3;
-        const float e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+        float e;
+        if constexpr (INJ) {
+          e = a.eps_b[(long long)s * a.Co + co];
+        } else {
+          RngKey kb = key_w;
+          kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
+          float z[4];
+          philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
+          const int sel = co & 3;
+          e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+        }
         const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
         bv = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
         if constexpr (FLIP) bias1[ptid] = dl;

@@ -10,6 +10,14 @@
 
 namespace bt {
 
+// The injected-draw instantiations of the four kernels (bt_fused_split_inj.hip). A launch that reaches this chain with a.eps_w set
+// carries PACKED draws (bt_pack_eps; bt::run sends the natural layout to the fp32 general kernel): the flavour functions below
+// choose flavour and geometry exactly as for on-chip draws and hand the launch to these.
+int launch_split_inj_cfg(const FwdArgs& a, int bm, int xm, hipStream_t stream);
+int launch_quad_inj(const FwdArgs& a, hipStream_t stream);
+int launch_direct_inj(const FwdArgs& a, bool resident, hipStream_t stream);
+int launch_skinny_inj(const FwdArgs& a, int ks, hipStream_t stream);
+
 // 0: automatic (6-term exact split where the launch is eligible), 1: fp32 MFMA only, 2: 3-term split (opt-in, ~1e-5 relative)
 static std::atomic<int> g_contraction{-1};
 int contraction_mode() {
@@ -71,6 +79,7 @@ static int launch_quad_cfg(const FwdArgs& a, hipStream_t stream) {
 // workgroup to every CU (at least kKlSlices workgroups: the fused KL sweep keeps its slices, so its sum is the one-sample path's).
 // BT_QUAD_SPW (measurement knob, read at every launch) caps it: 1 = the one-sample path.
 static int quad_spw(const FwdArgs& a, long long tiles) {
+  if (a.eps_w) return 0;   // injected draws: the one-sample path (bit-identical to the walk)
   if (!a.ep_pool || a.x_sample_stride != 0 || a.S < 2 || a.Ho != 16 || a.Wo != 16 || a.t_NI != 2 || a.ep_Hp != 8 || a.ep_Wp != 8) return 0;
   int nd[2] = {};
   tap_window(a.KH, a.DH, a.SH, a.PH, a.H, a.Ho, false, &nd[0], &nd[1]);
@@ -100,6 +109,7 @@ static int launch_quad(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   if (!set_grid(a, tiles * a.n_sg)) return 1;
   split_fill_inverses(a);
   ran = a;
+  if (a.eps_w) return launch_quad_inj(a, stream);
   if (spw) return launch_quad_cfg<true, true>(a, stream);
   return a.ep_pool ? launch_quad_cfg<true>(a, stream) : launch_quad_cfg<false>(a, stream);
 }
@@ -162,6 +172,7 @@ static int launch_direct(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
     return launch_kernel(kern, nm, "fused forward (split, direct)", dim3((unsigned)a.total_blocks), dim3(kDirectThreads), direct_lds_bytes(a.Cig),
                          max_lds, stream, a);
   };
+  if (a.eps_w) return launch_direct_inj(a, resident, stream);
   if (resident) return launch(fused_split_direct_kernel<true>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,resident W>", direct_lds_bytes(kDirectMaxK));
   return launch(fused_split_direct_kernel<false>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,streamed W>", direct_lds_bytes(kDirectMaxK + 1));
 }
@@ -222,7 +233,8 @@ static int launch_skinny(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   if (!set_grid(a, p.tiles * p.nsl)) return 1;
   a.x_vec = (a.HW == 1 && ((((uintptr_t)a.x) & 15u) == 0) && (a.x_sample_stride & 3) == 0 && (a.Ci & 3) == 0) ? 1 : 0;
   ran = a;
-  return launch_kernel(fused_split_skinny_kernel,
+  if (a.eps_w) return launch_skinny_inj(a, p.ks, stream);
+  return launch_kernel(fused_split_skinny_kernel<false>,
                        p.ks == 128 ? "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 128>" : "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 64>",
                        "fused forward (split, skinny)", dim3((unsigned)a.total_blocks), dim3(kSkinnyThreads), skinny_lds_bytes(p.ks), skinny_lds_bytes(128),
                        stream, a);
@@ -232,8 +244,10 @@ static int launch_skinny(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
 static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   const int mode = contraction_mode();
   if (mode == 1) return 1;
-  // Reparameterization, on-chip draws, packed parameters, 32-bit byte offsets
+  // Reparameterization, on-chip draws or PACKED injected ones, packed parameters, 32-bit byte offsets
   if (!packed_ok(a)) return 1;
+  const bool inj = a.eps_w != nullptr;
+  if (inj && mode == 2) return 1;   // (the opt-in 3-term form has no injected instantiation)
   if (a.Cig <= 4) return launch_quad(a, ran, stream);   // the stems
   // whole channel octets, at most 9 taps, no fused pooling
   if ((a.Cig & 7) || a.ep_pool) return 1;
@@ -293,6 +307,7 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   else if (xal && a.pixel_major && a.H == 2 && a.W == 2 && a.KH == 3 && a.KW == 3 && a.PH == 1 && a.PW == 1 && a.SH == 1 && a.SW == 1 && a.DH == 1 && a.DW == 1) xm = 2;
   split_fill_inverses(a);
   ran = a;
+  if (inj) return launch_split_inj_cfg(a, bm, xm, stream);
   if (bm == 512) return launch_split_xm<512, 4>(a, mode, xm, stream);
   if (bm == 256) return launch_split_xm<256, 8>(a, mode, xm, stream);
   return launch_split_xm<128, 8>(a, mode, xm, stream);

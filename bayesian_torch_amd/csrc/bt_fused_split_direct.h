@@ -33,7 +33,9 @@ constexpr int kDirectWStep = 2 * 3 * 64 * 16;  // bytes of one K16 step of the w
 constexpr int kDirectChunk = 8;                // K16 steps per streamed weight chunk
 inline int direct_lds_bytes(int Cig) { return (Cig <= kDirectMaxK ? (Cig >> 4) : 2 * kDirectChunk) * kDirectWStep + 64 * 16 + 64; }
 
-template <bool RESIDENT>
+// INJ (bt_fused_split_inj.hip): the draws are read -- a.eps_w as [S] images in the layout of mu_packed (bt_pack_eps), one 16-byte
+// load per unit issued with its two parameter loads; a.eps_b [S][Co].
+template <bool RESIDENT, bool INJ = false>
 __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(const FwdArgs a) {
   constexpr int BN = 64, NP = 3, W_STEP = kDirectWStep, W_HALF = NP * BN * 16, W_PIECE = BN * 16;
   constexpr int TN = 2, TM = 2;  // a wave: 64 channels x 64 pixels
@@ -114,6 +116,12 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
   const int pk_bytes = a.Co * a.T * Cig * 4;
   const __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.mu_pk), 0, pk_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sig_pk), 0, pk_bytes, 0x00020000);
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_ep =   // INJ: this sample's image of the packed draws
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
+  auto load_ep = [&](uint32_t sb, float (&ep)[4]) {   // rows past the tile's channels read 0.0
+    const float4 e = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_ep, (int)sb, 0, 0));
+    ep[0] = e.x, ep[1] = e.y, ep[2] = e.z, ep[3] = e.w;
+  };
   auto synth_one = [&](char* dst_img, int oct0, int it, int noct) {   // unit it * 512 + tid of the octets [oct0, oct0 + noct)
     const int u = it * kDirectThreads + tid;
     const int cq = u & 1, n = (u >> 1) & (BN - 1), ol = u >> 7;
@@ -127,7 +135,8 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
     const float4 mu = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_mu, (int)sb, 0, 0));
     const float4 rs = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, (int)sb, 0, 0));
     float ep[4];
-    philox_normal4(key_w, sample, eo >> 2, ep);
+    if constexpr (INJ) load_ep(sb, ep);
+    else philox_normal4(key_w, sample, eo >> 2, ep);
     const float m4[4] = {mu.x, mu.y, mu.z, mu.w}, s4[4] = {rs.x, rs.y, rs.z, rs.w};
     uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
@@ -143,6 +152,7 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
   // the x ring. All of it stays inside one chunk: nothing is carried around the loop.
   struct Unit {
     float4 mu, rs;
+    float ep[INJ ? 4 : 1];  // INJ: the unit's draws
     uint32_t eo;
     int lds;  // byte offset in the weight image
   };
@@ -158,11 +168,13 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
     t.lds = st * W_STEP + hf * W_HALF + (n ^ ((2 * st + hf) & 7)) * 16 + cq * 8;
     t.mu = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_mu, (int)sb, 0, 0));
     t.rs = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, (int)sb, 0, 0));
+    if constexpr (INJ) load_ep(sb, t.ep);
     return t;
   };
   auto unit_finish = [&](char* dst_img, const Unit& t) {
     float ep[4];
-    philox_normal4(key_w, sample, t.eo >> 2, ep);
+    if constexpr (INJ) ep[0] = t.ep[0], ep[1] = t.ep[1], ep[2] = t.ep[2], ep[3] = t.ep[3];
+    else philox_normal4(key_w, sample, t.eo >> 2, ep);
     const float m4[4] = {t.mu.x, t.mu.y, t.mu.z, t.mu.w}, s4[4] = {t.rs.x, t.rs.y, t.rs.z, t.rs.w};
     uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
@@ -189,12 +201,17 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
     const int co_g = n0 + tid;
     if (a.mu_b && co_g < a.Cog) {
       const int co = g * a.Cog + co_g;
-      RngKey kb = key_w;
-      kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-      float z[4];
-      philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-      const int sel = co & 3;
-      const float e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+      float e;
+      if constexpr (INJ) {
+        e = a.eps_b[(long long)s * a.Co + co];
+      } else {
+        RngKey kb = key_w;
+        kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
+        float z[4];
+        philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
+        const int sel = co & 3;
+        e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+      }
       bv = __fadd_rn(a.mu_b[co], __fmul_rn(softplus(a.rho_b[co]), e));
     }
     const bool cv = a.ep_scale && co_g < a.Cog;

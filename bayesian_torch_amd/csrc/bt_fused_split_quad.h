@@ -33,8 +33,11 @@ constexpr int quad_lds_bytes() { return 2 * split_w_bytes<64, 3, FLIP>() + (FLIP
 constexpr int kWalkRowBytes = 2 * 64 * 16 * 4;                 // one image row of each of the tile's 2 images, 64 channels
 constexpr int kWalkBytes = 2 * kWalkRowBytes + 2 * 3 * 64 * 4;  // [2 samples] shared rows + [2 samples] bias / scale / shift
 
-template <int NP, bool POOL, bool FLIP = false, bool WALK = false>
+// INJ (Reparameterization, one sample per workgroup; bt_fused_split_inj.hip): the draws are read -- a.eps_w as [S] images in the
+// layout of mu_packed (bt_pack_eps), one 16-byte load per unit issued with its two parameter loads; a.eps_b [S][Co].
+template <int NP, bool POOL, bool FLIP = false, bool WALK = false, bool INJ = false>
 __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) {
+  static_assert(!INJ || (!FLIP && !WALK), "injected draws: Reparameterization, the one-sample path");
   constexpr int BN = 64, BM = FLIP ? 256 : 512, kProducers = 256, kThreadsAll = 512, STEPS = kSplitSteps, TPS = 4 * STEPS;  // taps per stage
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32, NOP = FLIP ? 2 : 1;
   constexpr int PBQ = 8 * NP;  // bytes per pixel of the quad patch
@@ -156,6 +159,8 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
   const __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.mu_pk), 0, pk_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sig_pk), 0, pk_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)(a.x_elems * 4), 0x00020000);
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_ep =   // INJ: this sample's image of the packed draws
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
   auto ldf = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0)); };
   auto ldf4 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0)); };
 
@@ -279,6 +284,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     l_off[i] = st_ * W_STEP + hf * W_HALF + (n ^ ((2 * st_ + hf) & 7)) * 16 + sub * 8;
   }
   float4 mu[UMAX], rs[UMAX];
+  [[maybe_unused]] float4 epl[INJ ? UMAX : 1];  // INJ: the units' draws, loaded with their parameters
   uint32_t ue[UMAX];  // draw index of the unit in this stage, or OOB
   auto load_w = [&](int st) {
 #pragma unroll
@@ -288,6 +294,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       const int tap = taptab[ai < nA ? ai : 0].w;
       ue[i] = in ? (u_co[i] * (uint32_t)T + (uint32_t)tap) * 4u : (kOOB >> 2);
       mu[i] = ldf4(r_mu, in ? 4u * ue[i] : kOOB), rs[i] = ldf4(r_rs, in ? 4u * ue[i] : kOOB);
+      if constexpr (INJ) epl[i] = ldf4(r_ep, in ? 4u * ue[i] : kOOB);  // masked units read 0.0
     }
   };
   if (!FLIP && producer && NS > 0) load_w(0);  // stage 0's loads in flight under the patch fetch (Flipout: after it, as measured)
@@ -349,7 +356,10 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     auto draw_stage = [&](uint32_t smp, char* const Wt) {
       float ep[UMAX][4];
 #pragma unroll
-      for (int i = 0; i < UMAX; ++i) philox_normal4(key_w, smp, ue[i] >> 2, ep[i]);
+      for (int i = 0; i < UMAX; ++i) {
+        if constexpr (INJ) ep[i][0] = epl[i].x, ep[i][1] = epl[i].y, ep[i][2] = epl[i].z, ep[i][3] = epl[i].w;
+        else philox_normal4(key_w, smp, ue[i] >> 2, ep[i]);
+      }
 #pragma unroll
       for (int i = 0; i < UMAX; ++i) {
         const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
@@ -376,12 +386,17 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       const int co_g = n0 + ptid;
       if (a.mu_b && co_g < a.Cog) {
         const int co = g * a.Cog + co_g;
-        RngKey kb = key_w;
-        kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-        float z[4];
-        philox_normal4(kb, smp, (uint32_t)(co >> 2), z);
-        const int sel = co & 3;
-        const float e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+        float e;
+        if constexpr (INJ) {
+          e = a.eps_b[(long long)s * a.Co + co];
+        } else {
+          RngKey kb = key_w;
+          kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
+          float z[4];
+          philox_normal4(kb, smp, (uint32_t)(co >> 2), z);
+          const int sel = co & 3;
+          e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+        }
         const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
         bv = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
         if constexpr (FLIP) b1p[ptid] = dl;

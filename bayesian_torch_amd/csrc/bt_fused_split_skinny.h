@@ -29,6 +29,9 @@ constexpr int kSkinnyTicketSlot = 4000;             // tickets: the upper half o
 constexpr int kSkinnyMaxTiles = 8000;
 inline int skinny_lds_bytes(int ks) { return (ks >> 4) * kDirectWStep + 64 * 16 + 64; }
 
+// INJ (bt_fused_split_inj.hip): the draws are read -- a.eps_w as [S] images in the layout of mu_packed (bt_pack_eps), one 16-byte load
+// per unit issued at the top with its two parameter loads; a.eps_b [S][Co].
+template <bool INJ = false>
 __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(const FwdArgs a) {
   constexpr int BN = 64, NP = 3, W_STEP = kDirectWStep, W_HALF = NP * BN * 16, W_PIECE = BN * 16, TN = 2;
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
@@ -74,11 +77,14 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
   constexpr int UMAXS = 2 * BN * 16 / kSkinnyThreads;   // 8
   const int nunits = 2 * BN * (KS >> 3);
   float4 wmu[UMAXS], wrs[UMAXS];
+  [[maybe_unused]] float4 wep[INJ ? UMAXS : 1];
   uint32_t weo[UMAXS];
   {
     const int pk_bytes = a.Co * T * Cig * 4;
     const __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.mu_pk), 0, pk_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sig_pk), 0, pk_bytes, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_ep =   // INJ: this sample's image of the packed draws
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
 #pragma unroll
     for (int k = 0; k < UMAXS; ++k) {
       const int u = k * kSkinnyThreads + tid;
@@ -89,9 +95,11 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
       const uint32_t sb = rv ? 4u * weo[k] : 0x80000000u;   // rows past the tile's channels (and units past the slice) load zeros: w = 0 + 0 * eps
       wmu[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_mu, (int)sb, 0, 0));
       wrs[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_rs, (int)sb, 0, 0));
+      if constexpr (INJ) wep[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r_ep, (int)sb, 0, 0));   // masked units read 0.0
     }
   }
   float c_mub = 0.f, c_rhob = 0.f, c_sc = 1.f, c_sh = 0.f;
+  [[maybe_unused]] float c_epb = 0.f;
   bool c_bias = false;
   if (tid >= 64 && tid < 128) {
     const int co_g = n0 + tid - 64;
@@ -99,6 +107,9 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
     const int co = g * a.Cog + (in ? co_g : 0);
     c_bias = a.mu_b && in;
     if (c_bias) c_mub = a.mu_b[co], c_rhob = a.rho_b[co];
+    if constexpr (INJ) {
+      if (c_bias) c_epb = a.eps_b[(long long)s * a.Co + co];
+    }
     if (a.ep_scale && in) c_sc = a.ep_scale[co], c_sh = a.ep_shift[co];
   }
 
@@ -120,11 +131,12 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
     double acc = 0.0;
     long long i = lo + 4ll * tid;
     if (v4) {
+      constexpr int KLB = INJ ? 2 : 4;   // (INJ: two -- the units' draws are in flight as well; the same per-thread order of accumulation)
       while (i + 3 < hi) {   // four groups per trip, all 16 loads in flight before the first use
-        float4 m4[4], r4[4], p4[4], q4[4];
-        bool ok[4];
+        float4 m4[KLB], r4[KLB], p4[KLB], q4[KLB];
+        bool ok[KLB];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < KLB; ++u) {
           const long long iu = i + (long long)u * 4 * kSkinnyThreads;
           ok[u] = iu + 3 < hi;
           if (ok[u]) {
@@ -133,7 +145,7 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
           }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < KLB; ++u) {
           if (ok[u]) {
             const float t0 = kl_term(m4[u].x, softplus(r4[u].x), p4[u].x, q4[u].x) + kl_term(m4[u].y, softplus(r4[u].y), p4[u].y, q4[u].y);
             const float t1 = kl_term(m4[u].z, softplus(r4[u].z), p4[u].z, q4[u].z) + kl_term(m4[u].w, softplus(r4[u].w), p4[u].w, q4[u].w);
@@ -158,7 +170,8 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
   for (int k = 0; k < UMAXS; ++k) {
     if (k * kSkinnyThreads < nunits) {   // uniform
       float ep[4];
-      philox_normal4(key_w, sample, weo[k] >> 2, ep);
+      if constexpr (INJ) ep[0] = wep[k].x, ep[1] = wep[k].y, ep[2] = wep[k].z, ep[3] = wep[k].w;
+      else philox_normal4(key_w, sample, weo[k] >> 2, ep);
       const float m4[4] = {wmu[k].x, wmu[k].y, wmu[k].z, wmu[k].w}, s4[4] = {wrs[k].x, wrs[k].y, wrs[k].z, wrs[k].w};
       uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
@@ -284,13 +297,18 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
   if (tid >= 64 && tid < 128) {
     float bv = 0.f;
     if (c_bias) {
-      const int co = g * a.Cog + n0 + tid - 64;
-      RngKey kb = key_w;
-      kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-      float z[4];
-      philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-      const int sel = co & 3;
-      const float e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+      float e;
+      if constexpr (INJ) {
+        e = c_epb;
+      } else {
+        const int co = g * a.Cog + n0 + tid - 64;
+        RngKey kb = key_w;
+        kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
+        float z[4];
+        philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
+        const int sel = co & 3;
+        e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+      }
       bv = __fadd_rn(c_mub, __fmul_rn(softplus(c_rhob), e));
     }
     cst[tid - 64] = make_float4(bv, c_sc, c_sh, 0.f);

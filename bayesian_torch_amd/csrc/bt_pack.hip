@@ -213,7 +213,46 @@ __global__ __launch_bounds__(256) void pack_dirty_kernel(PackSegs sg) {
   }
 }
 
+// bt_pack_eps: eps_packed[r][t][c] <- eps[r][c][t], r = (sample, row) -- pack_dirty_kernel's transpose for a draw: a work item is
+// (r, chunk of 64 channels), its 64 x T natural floats one contiguous run read coalesced, transposed through LDS, written as T runs
+// of packed floats; the padding channels hold 0.0.
+__global__ __launch_bounds__(256) void pack_eps_kernel(const float* __restrict__ eps, float* __restrict__ out, long long rows, long long C, int T) {
+  extern __shared__ float etile[];   // [T][64 + 1]
+  const long long C4 = (C + 3) & ~3ll;
+  const long long cchunks = (C4 + kPackCh - 1) / kPackCh, items = rows * cchunks;
+  for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+    const long long r = it / cchunks, c0 = (it - r * cchunks) * kPackCh;
+    const int nc = (int)((C - c0) < kPackCh ? (C - c0 > 0 ? C - c0 : 0) : kPackCh);
+    const int nc4 = (int)((C4 - c0) < kPackCh ? (C4 - c0) : kPackCh);
+    const long long src0 = (r * C + c0) * T;
+    __syncthreads();   // (the previous item's tile has been written out)
+    for (int i = threadIdx.x; i < nc * T; i += 256) {
+      const int c = i / T, t = i - c * T;
+      etile[t * (kPackCh + 1) + c] = eps[src0 + i];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < T * nc4; j += 256) {
+      const int t = j / nc4, c = j - t * nc4;
+      out[(r * T + t) * C4 + c0 + c] = c < nc ? etile[t * (kPackCh + 1) + c] : 0.f;
+    }
+  }
+}
+
 }  // namespace bt
+
+extern "C" int bt_pack_eps(const float* eps_w, int32_t S, int64_t Co, int64_t Ci, int64_t taps, float* eps_packed, bt_stream_t stream) {
+  using namespace bt;
+  if (!eps_w || !eps_packed) return set_error(BT_ERR_BAD_ARG, "bt_pack_eps: null argument");
+  if (S <= 0 || Co <= 0 || Ci <= 0 || taps <= 0) return set_error(BT_ERR_BAD_ARG, "bt_pack_eps: non-positive dimension");
+  if (taps > 128) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_eps: kernels larger than 128 taps are not supported");
+  const long long rows = (long long)S * Co, C4 = (Ci + 3) & ~3ll;
+  if (rows >= (1ll << 40) / (taps * C4)) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_eps: draw too large");
+  long long blocks = rows * ((C4 + kPackCh - 1) / kPackCh);
+  if (blocks > 8192) blocks = 8192;   // (the rest in the kernel's item loop)
+  const int lds = (int)(taps * (kPackCh + 1) * sizeof(float));
+  return launch_kernel(pack_eps_kernel, nullptr, "bt_pack_eps", dim3((unsigned)blocks), dim3(256), lds, 128 * (kPackCh + 1) * (int)sizeof(float), (hipStream_t)stream,
+                       eps_w, eps_packed, rows, (long long)Ci, (int)taps);
+}
 
 extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, const bt_pack_kl* kls, void* workspace, size_t workspace_bytes,
                                bt_stream_t stream) {

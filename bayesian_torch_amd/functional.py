@@ -4,7 +4,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, rng
 
 
 def conv_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw):
@@ -36,7 +36,8 @@ def maxpool_3x3s2(x):
 def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=None, S=1, shared_x=True,
                    priors=None, eps_w=None, eps_b=None, sign_in=None, sign_out=None,
                    seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_kl=False, workspace_owner="functional",
-                   post_scale=None, post_shift=None, residual=None, relu=False, packed=None, pool=False, prior_type="normal"):
+                   post_scale=None, post_shift=None, residual=None, relu=False, packed=None, pool=False, prior_type="normal",
+                   inject_path=None, eps_pack_state=None):
     """x: [B, In] (conv=None) or [B, Ci, H, W]; when ``shared_x`` is False x holds S stacked batches
     ([S*B, ...]).  conv: dict(stride=(sh,sw), padding=(ph,pw), dilation=(dh,dw), groups=g) for Conv2d.
     priors: (prior_mu_w, prior_sigma_w, prior_mu_b, prior_sigma_b) -- required when want_kl.
@@ -44,6 +45,10 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     post_scale/post_shift [Co], residual ([S*B, ...] like out, or [B, ...] shared), relu: fused output stage
     (v*scale+shift, +residual, max(.,0)).  packed: (mu_packed, sigma_packed) from pack_params() -- selects the fast kernel.
     prior_type: "normal" | "laplace" (kl_div's branch; only matters when want_kl).
+    inject_path: "general" | "split" | None (= rng.get_inject_path()): with "split", an injected Reparameterization draw (eps_w given,
+    packed given) is re-laid by bt_pack_eps and read by the split-precision kernels; a launch they decline (BT_ERR_UNSUPPORTED,
+    nothing launched) runs as under "general".  eps_pack_state: a dict the caller owns (a layer keeps one: the buffer lives and dies
+    with it) holding the packed-draw buffer and the geometries that were declined, so that neither is made again on every call.
     Returns (out [S*B, ...], kl or None)."""
     x = _lib.dev_f32(x, "input")
     dev = x.device
@@ -86,7 +91,14 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     L = _lib.lib()
     # layers whose output map is one pixel may run split over K-slices that meet in scratch behind the workspace (include/bt_hip.h)
     gq = geom if conv is not None else _lib.bt_conv2d_geom(B, In, 1, 1, Co, 1, 1, 1, 1, 0, 0, 1, 1, 1)
-    scratch = int(L.bt_fused_scratch_bytes(C.byref(gq), S)) if (eps_w is None and not flip and packed is not None) else 0
+    # injected draws on the split-precision kernels: Reparameterization, packed parameters, a whole draw
+    split_inj = ((rng.get_inject_path() if inject_path is None else inject_path) == "split" and tens["eps_w"] is not None and not flip
+                 and packed is not None and tens["sign_in"] is None and tens["sign_out"] is None and tens["eps_w"].numel() == S * tens["mu_w"].numel()
+                 and (tens["mu_b"] is None) == (tens["eps_b"] is None))
+    geo_key = (B, S, bool(shared_x), tuple(x.shape[1:]), None if conv is None else (sh, sw, ph, pw, dh, dw, groups), bool(pool), residual is not None)
+    if split_inj and eps_pack_state is not None and geo_key in eps_pack_state.setdefault("declined", set()):
+        split_inj = False
+    scratch = int(L.bt_fused_scratch_bytes(C.byref(gq), S)) if ((eps_w is None or split_inj) and not flip and packed is not None) else 0
     if scratch:
         ws = _lib.workspace(workspace_owner, dev, scratch)
     if want_kl:
@@ -100,6 +112,19 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
                        _lib.PRIOR_LAPLACE if prior_type == "laplace" else _lib.PRIOR_NORMAL, 0)
     R = _lib.bt_rng(int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(call_base), int(call) & 0xFFFFFFFF, int(layer_id), int(sample0), 0)
     D = _lib.bt_draws(_lib.ptr(tens["eps_w"]), _lib.ptr(tens["eps_b"]), _lib.ptr(tens["sign_in"]), _lib.ptr(tens["sign_out"]), R)
+    D_nat = D
+    if split_inj:
+        Cig, taps = mu_w.shape[1], mu_w[0, 0].numel()
+        n_pk = S * Co * taps * ((Cig + 3) // 4 * 4)
+        eps_pk = None if eps_pack_state is None else eps_pack_state.get("buf")
+        if eps_pk is None or eps_pk.numel() < n_pk or eps_pk.device != dev:
+            eps_pk = torch.empty(n_pk, dtype=torch.float32, device=dev)
+            if eps_pack_state is not None:
+                eps_pack_state["buf"] = eps_pk
+        with _lib.on(dev):
+            _lib.check(L.bt_pack_eps(tens["eps_w"].data_ptr(), S, Co, Cig, taps, eps_pk.data_ptr(), _lib.stream_ptr(dev)))
+        Rp = _lib.bt_rng(R.seed, R.call_base_dev, R.call, R.layer_id, R.sample0, _lib.DRAWS_EPS_PACKED)
+        D = _lib.bt_draws(eps_pk.data_ptr(), _lib.ptr(tens["eps_b"]), None, None, Rp)
     E = None
     if tens["post_scale"] is not None or tens["residual"] is not None or relu or pool:
         res, rstride = tens["residual"], 0
@@ -111,18 +136,24 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
         if tens["post_scale"] is not None and (tens["post_scale"].numel() != Co or tens["post_shift"] is None or tens["post_shift"].numel() != Co):
             raise RuntimeError("post_scale / post_shift must both have Co elements")
         E = C.byref(_lib.bt_epilogue(_lib.ptr(tens["post_scale"]), _lib.ptr(tens["post_shift"]), _lib.ptr(res), rstride, 1 if relu else 0, 1 if pool else 0))
-    tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), C.byref(D), E, out.data_ptr(), _lib.ptr(kl), _lib.ptr(ws),
-                 ws.numel() if ws is not None else 0, _lib.stream_ptr(dev))
-    with _lib.on(dev):
+    def launch(draws):
+        tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), C.byref(draws), E, out.data_ptr(), _lib.ptr(kl), _lib.ptr(ws),
+                     ws.numel() if ws is not None else 0, _lib.stream_ptr(dev))
         if conv is None:
             fn = L.bt_flipout_linear_fwd if flip else L.bt_reparam_linear_fwd
-            _lib.check(fn(B, In, Co, S, *tail_args))
-        else:
-            fn = L.bt_flipout_conv2d_fwd if flip else L.bt_reparam_conv2d_fwd
-            rc = fn(C.byref(geom), S, *tail_args)
-            if pool and rc == _lib.ERR_UNSUPPORTED:
-                return None
-            _lib.check(rc)
+            return fn(B, In, Co, S, *tail_args)
+        fn = L.bt_flipout_conv2d_fwd if flip else L.bt_reparam_conv2d_fwd
+        return fn(C.byref(geom), S, *tail_args)
+
+    with _lib.on(dev):
+        rc = launch(D)
+        if split_inj and rc == _lib.ERR_UNSUPPORTED:      # nothing was launched: the natural layout on the general kernel, as under "general"
+            if eps_pack_state is not None:
+                eps_pack_state["declined"].add(geo_key)
+            rc = launch(D_nat)
+        if pool and rc == _lib.ERR_UNSUPPORTED:
+            return None
+        _lib.check(rc)
     return out, kl
 
 

@@ -65,6 +65,7 @@ class FusedBayesLayer(BaseVariationalLayer_):
         self.post_pool = False    # ... followed by MaxPool2d(3, 2, 1) (fuse.fold_maxpool: the ResNet stem)
         self.register_buffer("post_scale", None, persistent=False)
         self.register_buffer("post_shift", None, persistent=False)
+        self._eps_pack = {}       # packed copy of a supplied draw (rng.set_inject_path("split")): buffer + declined geometries, owned by the layer
         self.inject_draw = None   # test hook: dict(eps_w [S,*w], eps_b, sign_in, sign_out) consumed instead of a fresh draw (or a list of them)
         self.init_parameters()
         self.quant_prepare = False
@@ -119,6 +120,7 @@ class FusedBayesLayer(BaseVariationalLayer_):
     def __getstate__(self):     # (copy.deepcopy / pickle: the cached pack-check entry holds ctypes pointers and belongs to THIS object's tensors)
         d = self.__dict__.copy()
         d.pop("_seg_cache", None)
+        d["_eps_pack"] = {}
         return d
 
     def _param_versions(self):
@@ -324,7 +326,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
                                       sign_in=draw.get("sign_in"), sign_out=draw.get("sign_out"), seed=seed, call=call,
                                       layer_id=self._layer_id, sample0=sample0, call_base=call_base, want_kl=fwd_kl,
                                       workspace_owner=("layer", self._ws_id), post_scale=self.post_scale, post_shift=self.post_shift,
-                                      residual=residual, relu=self.post_relu, pool=self.post_pool, packed=(mu_pk, sg_pk), prior_type=kind)
+                                      residual=residual, relu=self.post_relu, pool=self.post_pool, packed=(mu_pk, sg_pk), prior_type=kind,
+                                      eps_pack_state=self._eps_pack)
             if kl_synced is not None:
                 kl = kl_synced
         conv_shape = tuple(out.shape[1:])     # shape of one sample's contraction output (sign_out's shape): before any fused pooling

@@ -14,9 +14,21 @@ Two modes (``set_mode``):
     reference's draw order (linear_variational.py:164-174, conv_flipout.py:385-402) -- and the
     kernels READ it.  ``layer.eps_*`` hold the last draw as in the reference.
 
+Where a supplied draw runs (``set_inject_path``; ``inject_draw`` and ``"torch"`` mode alike):
+
+``"general"`` (default)
+    the fp32 general kernel reads the draw in its natural layout.
+
+``"split"``
+    Reparameterization layers under ``torch.no_grad()``: the draw is re-laid into the packed parameters' layout
+    (``bt_pack_eps``) and read by the injected instantiations of the split-precision (bf16x3) kernels -- the kernels an
+    on-chip launch runs, so a replayed on-chip draw reproduces that launch's output bit for bit.  A launch no split
+    flavour takes (and every Flipout layer) runs as under ``"general"``.  Environment: ``BT_INJECT_PATH``, read once.
+
 The seed defaults to ``torch.initial_seed()``; ``call`` advances once per layer forward and
 restarts whenever the seed changes, so ``torch.manual_seed(s)`` makes a run reproducible.
 """
+import os
 import threading
 
 import torch
@@ -34,6 +46,26 @@ def set_mode(mode):
 
 def get_mode():
     return _mode[0]
+
+
+_INJECT_PATHS = ("general", "split")
+
+
+def _check_inject_path(path, what):
+    if path not in _INJECT_PATHS:
+        raise ValueError(f"{what} must be 'general' or 'split', got {path!r}")
+    return path
+
+
+_inject_path = [_check_inject_path(os.environ.get("BT_INJECT_PATH", "general"), "BT_INJECT_PATH")]
+
+
+def set_inject_path(path):
+    _inject_path[0] = _check_inject_path(path, "inject path")
+
+
+def get_inject_path():
+    return _inject_path[0]
 
 
 def new_layer_id():

@@ -57,8 +57,15 @@ typedef struct bt_rng {
   uint32_t call;                 /* advance once per forward call (a fresh draw per call) */
   uint32_t layer_id;             /* < 2^28: distinct per Bayesian layer of a model */
   uint32_t sample0;              /* global id of this call's first MC sample */
-  uint32_t reserved;
+  uint32_t flags;                /* BT_DRAWS_*: layout of the injected draws (0: the natural layouts of bt_draws) */
 } bt_rng;
+/* bt_draws.eps_w holds [S] packed images as written by bt_pack_eps (the layout of bt_params.mu_packed) instead of [S][Co*K];
+ * eps_b stays [S][Co]. Reparameterization only. The launch is offered to the split-precision (bf16x3) kernels alone, whose
+ * injected instantiations read a unit's four draws with one 16-byte load where the on-chip ones run Philox: the same draws give
+ * the same output bits as the on-chip launch. Needs mu_packed / sigma_packed; BT_ERR_UNSUPPORTED (nothing launched) with sign
+ * tensors, under bt_set_contraction(1 | 2) / BT_CONTRACTION=f32 | bf16x2, or when no split flavour takes the launch -- call again
+ * with the natural layout then. The fused max-pool is available on this path. */
+#define BT_DRAWS_EPS_PACKED 1u
 
 /* Variational parameters and priors of one layer. weight is [Co][K] row-major
  * (Linear: K = in_features; Conv2d: K = (Ci/groups)*kh*kw, i.e. the native
@@ -115,8 +122,8 @@ typedef struct bt_epilogue {
 /* Fused max-pool of the output stage's result -- the ResNet stem's conv -> (folded BN) -> ReLU -> MaxPool2d(3, 2, 1) as one
  * launch: out is [S][B][Co][Hp][Wp] with Hp = (Ho - 1) / 2 + 1, Wp = (Wo - 1) / 2 + 1, NaN-propagating like
  * torch.nn.functional.max_pool2d. No residual with it. The launch returns BT_ERR_UNSUPPORTED (nothing written) when it cannot
- * fuse -- tiles that do not hold whole output images (large feature maps), Flipout, injected draws, input rows that are not
- * 16-byte aligned (W % 4 != 0): pool separately then. */
+ * fuse -- tiles that do not hold whole output images (large feature maps), Flipout, injected draws in the natural layout (packed
+ * ones, BT_DRAWS_EPS_PACKED, pool on the stem kernel), input rows that are not 16-byte aligned (W % 4 != 0): pool separately then. */
 #define BT_POOL_NONE 0
 #define BT_POOL_MAX_3x3_S2_P1 1
 
@@ -187,6 +194,11 @@ int bt_kl_normal(int32_t n_segments, const float *const *mu, const float *const 
  * the kernels' own softplus, so a forward with or without the packed copies is bit-identical. */
 int bt_pack_params(const float *mu_w, const float *rho_w, int64_t Co, int64_t Ci, int64_t taps,
                    float *mu_packed, float *sigma_packed, bt_stream_t stream);
+
+/* Re-lays S draws of a weight tensor, eps_w [S][Co][Ci][taps] (Ci = in_channels / groups: the natural layout of bt_draws), into
+ * eps_packed [S][(co*taps + tap)*Ci4 + ci] -- per sample the layout of mu_packed, padding channels 0.0 -- for
+ * BT_DRAWS_EPS_PACKED launches. S * Co * taps * Ci4 floats. Stream-ordered, no host synchronisation, graph-capturable. */
+int bt_pack_eps(const float *eps_w, int32_t S, int64_t Co, int64_t Ci, int64_t taps, float *eps_packed, bt_stream_t stream);
 
 /* Keeps the packed copies of up to BT_PACK_MAX_SEGMENTS layers in step with their parameters, checked ON THE DEVICE in the
  * stream (two launches, no host synchronisation, graph-capturable): a 64-bit fingerprint of every layer's natural-layout
