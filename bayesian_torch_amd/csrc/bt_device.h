@@ -116,6 +116,15 @@ __device__ __forceinline__ float kl_term(float mu_q, float sigma_q, float mu_p, 
   return __fsub_rn(__fadd_rn(__fsub_rn(ln_fast(sigma_p), ln_fast(sigma_q)), q), 0.5f);
 }
 
+// The four terms of an aligned quad, as every KL sweep of the library forms them (the fused forwards' KlSlice, bt_fused_common.h, and
+// the pack check's fingerprint sweep, bt_pack.hip): added in fp32 in the pairs (x, y) and (z, w), the pairs added as doubles. ONE
+// definition, so the inference KL and the fused sweeps agree to the bit.
+__device__ __forceinline__ double kl_quad(const float4& m4, const float4& r4, const float4& p4, const float4& q4) {
+  const float t0 = kl_term(m4.x, softplus(r4.x), p4.x, q4.x) + kl_term(m4.y, softplus(r4.y), p4.y, q4.y);
+  const float t1 = kl_term(m4.z, softplus(r4.z), p4.z, q4.z) + kl_term(m4.w, softplus(r4.w), p4.w, q4.w);
+  return (double)t0 + (double)t1;
+}
+
 // One element of kl_div's 'laplace' branch (base_variational_layer.py:74-97): KL(N(mu_q, sigma_q^2) || Laplace(0, 1)) --
 // the reference hard-codes the prior's location 0 and scale 1 there, whatever prior tensors it is handed --
 //   log 2 - 0.5 log(2 pi sigma^2) - 0.5 + E|w|,   E|w| = sigma sqrt(2/pi) exp(-mu^2 / (2 sigma^2)) + mu (1 - 2 Phi(-mu/sigma)),

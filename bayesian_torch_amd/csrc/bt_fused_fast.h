@@ -13,6 +13,7 @@
 // Everything else (patches that do not fit LDS, injected draws, unaligned Linear, absent parameter packs) runs the general
 // kernel, which keeps the same order of accumulation: the two flavours agree bit for bit.
 #pragma once
+#include "bt_fused_common.h"
 #include "bt_fused_fwd.h"
 
 namespace bt {
@@ -85,29 +86,13 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
   const int m0 = b0;  // Linear: first row of the tile
   const uint32_t inv_rw = RW > 1 ? (uint32_t)((0x100000000ull + (unsigned)RW - 1) / (unsigned)RW) : 0u;  // exact for ml < 2^16
   const uint32_t inv_wt = t_Wt > 1 ? (uint32_t)((0x100000000ull + (unsigned)t_Wt - 1) / (unsigned)t_Wt) : 0u;
-  auto col_decode = [&](int ml, int& b, int& ho, int& wo) -> bool {  // tile column -> output coordinates; false: dead column
-    const int img = RW == 1 ? ml : (int)__umulhi((uint32_t)ml, inv_rw);
-    const int rem = ml - img * RW;
-    const int r = t_Wt == 1 ? rem : (int)__umulhi((uint32_t)rem, inv_wt);
-    b = b0 + img, ho = r0 + r, wo = w0 + (rem - r * t_Wt);
-    return ml < Mt && b < a.B && ho < a.Ho && wo < a.Wo;
-  };
+  const ColDecode cols = {b0, r0, w0, RW, Mt, t_Wt, inv_rw, inv_wt, a.B, a.Ho, a.Wo};  // tile column -> output coordinates
   const uint32_t sample = a.sample0 + (uint32_t)s;
   const int K = a.K, T = a.T, Cig = a.Cig;
 
-  RngKey key_w;
-  key_w.seed_lo = a.seed_lo;
-  key_w.seed_hi = a.seed_hi;
-  key_w.call = a.call + (a.call_base ? __builtin_nontemporal_load(a.call_base) : 0u);
-  key_w.layer_tensor = layer_tensor_word(a.layer_id, 0);
+  const RngKey key_w = weight_key(a);
   uint32_t skey_in = 0, skey_out = 0;
-  if (FLIP && !INJ) {
-    RngKey ks = key_w;
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 2);
-    skey_in = sign_stream_key(ks, sample);
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 3);
-    skey_out = sign_stream_key(ks, sample);
-  }
+  if (FLIP && !INJ) sign_keys(a, key_w, sample, &skey_in, &skey_out);
 
   // ---- active taps of this tile + their window (wave 0) ----------------------------------------------------------------
   if (wave == 0) {
@@ -234,7 +219,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
         const int cr = c0q + NT * u, c = cr < NQ ? cr : 0;
         const int row = c / QROW, m4 = c - row * QROW;
         int bq, hq, wq;
-        const bool mok = col_decode(4 * m4, bq, hq, wq);
+        const bool mok = cols.decode(4 * m4, bq, hq, wq);
         const int co_l = (row >> 5) * WTN + i * 32 + (row & 31);
         okq[u] = cr < NQ && mok && n0 + co_l < a.Cog;
         oidx[u] = okq[u] ? (uint32_t)(((bq * a.Co + g * a.Cog + n0 + co_l) * a.Ho + hq) * a.Wo + wq) : 0u;
@@ -582,32 +567,11 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
     }
     // bias draw + output-stage constants of this workgroup's channels
     if (ptid < BN) {
-      float b0 = 0.f, b1 = 0.f;
-      const int co_g = n0 + ptid;
-      if (a.mu_b && co_g < a.Cog) {
-        const int co = g * a.Cog + co_g;
-        float e;
-        if (INJ) {
-          e = a.eps_b[(long long)s * a.Co + co];
-        } else {
-          RngKey kb = key_w;
-          kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-          float z[4];
-          philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-          const int sel = co & 3;
-          e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
-        }
-        const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
-        b0 = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
-        b1 = dl;
-      }
-      bias0[ptid] = b0;
-      if (FLIP) bias1[ptid] = b1;
-      const bool cv = a.ep_scale && co_g < a.Cog;
-      const int cs = cv ? g * a.Cog + co_g : 0;
-      const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
-      osc[ptid] = cv ? sc : 1.f;
-      osh[ptid] = cv ? sh : 0.f;
+      const ChannelConsts c = channel_consts<FLIP, INJ>(a, key_w, s, g, n0 + ptid);
+      bias0[ptid] = c.bias0;
+      if (FLIP) bias1[ptid] = c.bias1;
+      osc[ptid] = c.scale;
+      osh[ptid] = c.shift;
     }
     __syncthreads();
     if (TRANS && a.out_vec4) {  // the consumers pass the output tile through LDS: same barriers ...
@@ -630,44 +594,14 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
       // KL: sweep this workgroup's slice of the weights while the producers fill stage 0, then publish one fp64 partial
       // PER WAVE right away -- before this workgroup has dirtied L2 with its outputs, so the agent-scope release that the
       // hand-off needs has almost nothing to write back -- and let the last-arriving wave finish in fixed slot order.
-      long long chunk = (a.w_elems + a.kl_slices - 1) / a.kl_slices;
-      chunk = (chunk + 3) & ~3ll;
-      const long long lo = (long long)blockIdx.x * chunk;
-      const long long hi = (lo + chunk < a.w_elems) ? lo + chunk : a.w_elems;
-      const bool v4 = ((((uintptr_t)a.mu_w | (uintptr_t)a.rho_w | (uintptr_t)a.pmu_w | (uintptr_t)a.psig_w) & 15u) == 0);
-      double kl_acc = 0.0;
-      long long i = lo + 4ll * ptid;
-      if (v4) {
-        for (; i + 3 < hi; i += 1024) {
-          const float4 m4 = *reinterpret_cast<const float4*>(a.mu_w + i), r4 = *reinterpret_cast<const float4*>(a.rho_w + i);
-          const float4 p4 = *reinterpret_cast<const float4*>(a.pmu_w + i), q4 = *reinterpret_cast<const float4*>(a.psig_w + i);
-          const float t0 = kl_term(m4.x, softplus(r4.x), p4.x, q4.x) + kl_term(m4.y, softplus(r4.y), p4.y, q4.y);
-          const float t1 = kl_term(m4.z, softplus(r4.z), p4.z, q4.z) + kl_term(m4.w, softplus(r4.w), p4.w, q4.w);
-          kl_acc += (double)t0 + (double)t1;
-        }
-      }
-      for (; i < hi; i += 1024)  // tail quad / unaligned bases
-        for (int j = 0; j < 4; ++j)
-          if (i + j < hi) kl_acc += (double)kl_term(a.mu_w[i + j], softplus(a.rho_w[i + j]), a.pmu_w[i + j], a.psig_w[i + j]);
-      const double wsum = wave_sum(kl_acc);
+      KlSlice<1024> kls;
+      kls.open(a, ptid);
+      const double wsum = kls.rest(a);
       const int nslots = 4 * a.kl_slices;
       int last = 0;
       if (lane == 0) last = publish_and_ticket_wt(a.slots, a.counter, (int)blockIdx.x * 4 + wave, wsum, (unsigned)nslots) ? 1 : 0;
-      if (__builtin_amdgcn_readfirstlane(last)) {  // this wave arrived last: every slot is published
-        double t = 0.0;
-        for (int q = lane; q < nslots; q += 64) t += __hip_atomic_load(&a.slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = wave_sum(t);
-        double bt_ = 0.0;
-        if (a.mu_b)
-          for (int c = lane; c < a.Co; c += 64) bt_ += (double)kl_term(a.mu_b[c], softplus(a.rho_b[c]), a.pmu_b[c], a.psig_b[c]);
-        bt_ = wave_sum(bt_);
-        if (lane == 0) {
-          float kl = (float)(t / (double)a.w_elems);
-          if (a.mu_b) kl += (float)(bt_ / (double)a.Co);
-          a.kl_out[0] = kl;
-          __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-        }
-      }
+      if (__builtin_amdgcn_readfirstlane(last))  // this wave arrived last: every slot is published
+        kl_close(a, kl_slot_sum(a, nslots, lane), lane);
     }
     // LDS column base of this lane's output pixel per 32-wide column group
     int colbase[TM];
@@ -678,7 +612,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
         colbase[j] = ml;
       } else {
         int b, ho, wo;
-        const bool live = col_decode(ml, b, ho, wo);
+        const bool live = cols.decode(ml, b, ho, wo);
         colbase[j] = live ? (b - b0) * PIMG + (ho - r0) * ps_h * PWt + (wo - w0) * ps_w : 0;
       }
     }
@@ -801,7 +735,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
             uint32_t oidx = 0;
             if constexpr (FLIP) {
               int bq, hq, wq;
-              const bool mok = col_decode(wm * WTM + j * 32 + 8 * q + 4 * lh, bq, hq, wq);
+              const bool mok = cols.decode(wm * WTM + j * 32 + 8 * q + 4 * lh, bq, hq, wq);
               const int co_l = wn * WTN + i * 32 + li;
               oidx = (mok && n0 + co_l < a.Cog) ? (uint32_t)(((bq * a.Co + g * a.Cog + n0 + co_l) * a.Ho + hq) * a.Wo + wq) : 0u;
             }
@@ -867,7 +801,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
       for (int j = 0; j < TM; ++j) {
         int b_col = 0, h_col = 0, w_col = 0;
         bool live_col = false;
-        if (!TRANS) live_col = col_decode(wm * WTM + j * 32 + li, b_col, h_col, w_col);  // lanes run along the tile columns
+        if (!TRANS) live_col = cols.decode(wm * WTM + j * 32 + li, b_col, h_col, w_col);  // lanes run along the tile columns
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
           uint32_t oi[16];
@@ -881,7 +815,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
             int bb = b_col, hh = h_col, ww = w_col;
             if (TRANS) {
               co_l = wn * WTN + i * 32 + li;
-              live = col_decode(wm * WTM + j * 32 + row, bb, hh, ww);
+              live = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);
             } else {
               co_l = wn * WTN + i * 32 + row;
               live = live_col;

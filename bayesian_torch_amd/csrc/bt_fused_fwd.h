@@ -26,7 +26,7 @@
 #pragma once
 #include <type_traits>
 
-#include "bt_api_internal.h"
+#include "bt_fused_common.h"
 
 namespace bt {
 
@@ -40,49 +40,6 @@ constexpr int kMaxTaps = 128;  // kh*kw supported by the tap table
 constexpr bool kStamps = BT_STAMPS != 0;
 constexpr int kThreads = 512;   // 4 consumer waves + 4 producer waves: one of each per SIMD
 constexpr int kProducers = 256;
-
-struct FwdArgs {
-  const float *x, *mu_w, *rho_w, *mu_b, *rho_b, *pmu_w, *psig_w, *pmu_b, *psig_b;
-  const float *mu_pk, *sig_pk;  // optional tap-major packed parameters (bt_params.mu_packed / sigma_packed): fast flavour only
-  const float *eps_w, *eps_b, *sign_in, *sign_out;
-  float* out;
-  float* kl_out;
-  double* slots;
-  unsigned* counter;
-  long long x_sample_stride, x_elems, out_elems, w_elems;
-  int B, Ci, H, W, Co, KH, KW, SH, SW, PH, PW, DH, DW, G;
-  int Ho, Wo, HoWo, M, K, Cig, Cog, S, T, HW;
-  int n_tiles, m_tiles, total_blocks;
-  int t_NI, t_R, t_Wt, n_bt, n_rt, n_ct;  // fast flavour: tile = t_NI images x t_R rows x t_Wt cols; tile grid per (n-tile, sample)
-  int patch_ok;                   // host: tiles are whole images (or pixel-major), so the x operand can be staged as a patch
-  int x_cvec;                     // host (fast flavour): x is 16-byte aligned per image -> tiny planes are staged as channel vectors
-  int x_rows;                     // host (fast flavour): stage the x patch as 16-byte row chunks written straight to LDS
-  int pixel_major, mt_per_pixel;  // m-tile = (one output pixel, BM images) instead of BM consecutive (b, ho, wo)
-  int w_vec, x_vec;               // float4 paths allowed (taps == 1, K % 4 == 0, 16-B aligned bases)
-  int do_kl, kl_slices;
-  uint32_t seed_lo, seed_hi, call, layer_id, sample0;
-  const uint32_t* call_base;  // device word added to `call` (fresh draws on graph replay), or null
-  const float *ep_scale, *ep_shift, *ep_res;  // fused output stage (bt_epilogue)
-  long long ep_res_stride;
-  int ep_relu;
-  int ep_pool, ep_Hp, ep_Wp;  // fused 3x3 / stride 2 / pad 1 max-pool of the output stage (fast flavour, whole-image tiles)
-  int out_vec4;  // spatial output stored as float4 along the pixel index (TRANS orientation; Ho*Wo % 4 == 0, aligned tensors)
-  int bn32;                 // general split kernel: 32-channel tiles (launch_split_one)
-  unsigned long long* dbg;  // diagnostic stamps (bt_debug_set_stamp_buffer); null in normal operation
-  // split flavour: ceil(2^32 / d) of the launch-uniform divisors (0: divide), so the tile decode is a few multiplies
-  uint32_t inv_m_tiles, inv_S, inv_n_tiles, inv_n_bt, inv_n_ct, inv_rw, inv_wt, inv_kw;
-  int x_flat;  // split flavour, XM 3: the patch is the whole input plane -- fetch it as one row of H*W pixels
-  int row_taps;  // split flavour: tiles = t_NI images x ONE output row; the active taps are those of the tile's row (2-row maps)
-  // skinny flavour (bt_fused_split_skinny.h): scratch slabs behind the workspace, tickets inside it, slice geometry
-  float* sk_scratch;
-  unsigned* sk_tickets;
-  long long sk_scratch_bytes;
-  int sk_nsl, sk_ks, sk_cpt;           // slices per tile, slice width (channels), slices per tap
-  int sk_kh0, sk_nh, sk_kw0, sk_nw;    // the rectangle of taps whose input pixel exists for the one output pixel
-  int d_tap;     // direct flavour: the ONE tap of the kernel window that meets data (0 for 1x1 kernels; the centre of a padded window over a 1x1 image)
-  int spw, n_sg;        // quad flavour, sample walk: samples per workgroup, sample groups = ceil(S / spw) (launch_quad)
-  uint32_t inv_n_sg;
-};
 
 // Host: a launch of `total` workgroups (a 1-D grid) and the workgroups that sweep a slice of the weights for the fused KL;
 // false when the grid is empty or too large.
@@ -189,19 +146,9 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   const uint32_t sample = a.sample0 + (uint32_t)s;
   const int K = a.K, T = a.T, Cig = a.Cig;
 
-  RngKey key_w;
-  key_w.seed_lo = a.seed_lo;
-  key_w.seed_hi = a.seed_hi;
-  key_w.call = a.call + (a.call_base ? __builtin_nontemporal_load(a.call_base) : 0u);
-  key_w.layer_tensor = layer_tensor_word(a.layer_id, 0);
-  uint32_t skey_in = 0, skey_out = 0;
-  if (FLIP) {
-    RngKey ks = key_w;
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 2);
-    if (!INJ) skey_in = sign_stream_key(ks, sample);
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 3);
-    if (!INJ) skey_out = sign_stream_key(ks, sample);
-  }
+  const RngKey key_w = weight_key(a);
+  uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams (injected: the signs are read)
+  if (FLIP && !INJ) sign_keys(a, key_w, sample, &skey_in, &skey_out);
 
   // ---- active taps of this tile (wave 0: ballot compaction, ascending tap order) ---------------------------------
   if (wave == 0) {
@@ -692,32 +639,11 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
     if (stamp) dbg_[127] = __builtin_amdgcn_s_memtime();
     // bias draw for this workgroup's output channels
     if (ptid < BN) {
-      float b0 = 0.f, b1 = 0.f;
-      const int co_g = n0 + ptid;
-      if (a.mu_b && co_g < a.Cog) {
-        const int co = g * a.Cog + co_g;
-        float e;
-        if (INJ) {
-          e = a.eps_b[(long long)s * a.Co + co];
-        } else {
-          RngKey kb = key_w;
-          kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-          float z[4];
-          philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-          const int sel = co & 3;
-          e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
-        }
-        const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
-        b0 = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
-        b1 = dl;
-      }
-      bias0[ptid] = b0;
-      if (FLIP) bias1[ptid] = b1;
-      const bool cv = a.ep_scale && co_g < a.Cog;
-      const int cs = cv ? g * a.Cog + co_g : 0;
-      const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
-      osc[ptid] = cv ? sc : 1.f;
-      osh[ptid] = cv ? sh : 0.f;
+      const ChannelConsts c = channel_consts<FLIP, INJ>(a, key_w, s, g, n0 + ptid);
+      bias0[ptid] = c.bias0;
+      if (FLIP) bias1[ptid] = c.bias1;
+      osc[ptid] = c.scale;
+      osh[ptid] = c.shift;
     }
     __syncthreads();
   } else {
@@ -725,6 +651,9 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
       // KL: sweep this workgroup's slice of the weights while the producers fill stage 0, then publish one fp64 partial
       // PER WAVE right away -- before this workgroup has dirtied L2 with its outputs, so the agent-scope release that the
       // hand-off needs has almost nothing to write back -- and let the last-arriving wave finish in fixed slot order.
+      // (This kernel's OWN copy of KlSlice<1024>::rest, bt_fused_common.h, statement for statement; kl_quad and kl_close are shared. With
+      // the shared sweep inlined, <64,128,2,reparam,conv,trans> ran 132.33 us against the parent's 131.73 ... 132.26 and <128,256,2,...>
+      // 277.39 against 277.06 ... 277.28, medians of three alternated kernel-trace runs: profiles/r07_shared_forward_pieces_ab.json.)
       long long chunk = (a.w_elems + a.kl_slices - 1) / a.kl_slices;
       chunk = (chunk + 3) & ~3ll;
       const long long lo = (long long)blockIdx.x * chunk;
@@ -736,9 +665,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
         for (; i + 3 < hi; i += 1024) {
           const float4 m4 = *reinterpret_cast<const float4*>(a.mu_w + i), r4 = *reinterpret_cast<const float4*>(a.rho_w + i);
           const float4 p4 = *reinterpret_cast<const float4*>(a.pmu_w + i), q4 = *reinterpret_cast<const float4*>(a.psig_w + i);
-          const float t0 = kl_term(m4.x, softplus(r4.x), p4.x, q4.x) + kl_term(m4.y, softplus(r4.y), p4.y, q4.y);
-          const float t1 = kl_term(m4.z, softplus(r4.z), p4.z, q4.z) + kl_term(m4.w, softplus(r4.w), p4.w, q4.w);
-          kl_acc += (double)t0 + (double)t1;
+          kl_acc += kl_quad(m4, r4, p4, q4);
         }
       }
       for (; i < hi; i += 1024)  // tail quad / unaligned bases
@@ -748,21 +675,8 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
       const int nslots = 4 * a.kl_slices;
       int last = 0;
       if (lane == 0) last = publish_and_ticket_wt(a.slots, a.counter, (int)blockIdx.x * 4 + wave, wsum, (unsigned)nslots) ? 1 : 0;
-      if (__builtin_amdgcn_readfirstlane(last)) {  // this wave arrived last: every slot is published
-        double t = 0.0;
-        for (int q = lane; q < nslots; q += 64) t += __hip_atomic_load(&a.slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = wave_sum(t);
-        double bt_ = 0.0;
-        if (a.mu_b)
-          for (int c = lane; c < a.Co; c += 64) bt_ += (double)kl_term(a.mu_b[c], softplus(a.rho_b[c]), a.pmu_b[c], a.psig_b[c]);
-        bt_ = wave_sum(bt_);
-        if (lane == 0) {
-          float kl = (float)(t / (double)a.w_elems);
-          if (a.mu_b) kl += (float)(bt_ / (double)a.Co);
-          a.kl_out[0] = kl;
-          __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-        }
-      }
+      if (__builtin_amdgcn_readfirstlane(last))  // this wave arrived last: every slot is published
+        kl_close(a, kl_slot_sum(a, nslots, lane), lane);
     }
     __syncthreads();
 

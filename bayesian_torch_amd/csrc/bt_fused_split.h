@@ -11,8 +11,9 @@
 // Each piece product is exact in fp32 (8 x 8 significant bits) and the MFMA accumulates in fp32, so the 6-term form
 // has the accuracy of the fp32 FMA chain at 6/16 of its matrix-pipe time, with the weight synthesis co-issuing.
 //
-// Same algorithm, same draw stream (tap-major Philox blocks, one block = 4 channels of one tap), same KL sweep and
-// output stage as bt_fused_fast.h; what changes is the K order and the LDS images.
+// Same algorithm, same draw stream (tap-major Philox blocks, one block = 4 channels of one tap) and output stage as
+// bt_fused_fast.h, and the KL sweep, keys and bias stage every forward kernel shares (bt_fused_common.h); what changes is the
+// K order and the LDS images.
 //   * K order (canonical, independent of the tile): channels in OCTETS of 8; an MFMA step covers two (octet, active tap)
 //     entries -- lanes 0-31 hold the 8 channels of the first, lanes 32-63 of the second. nA > 1: the octet's taps in
 //     pairs (a0,a1), (a2,a3) ...; an odd last tap runs with an empty second half. nA == 1: consecutive octets in pairs.
@@ -24,6 +25,7 @@
 //   * w tile: W[step][lane half][piece][row][8 channels] bf16 -- 16 consecutive rows cover all 64 banks.
 // Producers split every sampled weight and every staged activation once; consumers only read LDS and issue MFMAs.
 #pragma once
+#include "bt_fused_common.h"
 #include "bt_fused_fwd.h"
 
 namespace bt {
@@ -157,29 +159,13 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   const int b0 = bt * t_NI, r0 = rt * t_R, w0 = ct * t_Wt;
   const uint32_t inv_rw = RW > 1 ? (a.inv_rw ? a.inv_rw : inv32(RW)) : 0u;
   const uint32_t inv_wt = t_Wt > 1 ? (a.inv_wt ? a.inv_wt : inv32(t_Wt)) : 0u;
-  auto col_decode = [&](int ml, int& b, int& ho, int& wo) -> bool {  // tile column -> output coordinates; false: dead column
-    const int img = RW == 1 ? ml : (int)__umulhi((uint32_t)ml, inv_rw);
-    const int rem = ml - img * RW;
-    const int r = t_Wt == 1 ? rem : (int)__umulhi((uint32_t)rem, inv_wt);
-    b = b0 + img, ho = r0 + r, wo = w0 + (rem - r * t_Wt);
-    return ml < Mt && b < a.B && ho < a.Ho && wo < a.Wo;
-  };
+  const ColDecode cols = {b0, r0, w0, RW, Mt, t_Wt, inv_rw, inv_wt, a.B, a.Ho, a.Wo};  // tile column -> output coordinates
   const uint32_t sample = a.sample0 + (uint32_t)s;
   const int T = a.T, Cig = a.Cig;
 
-  RngKey key_w;
-  key_w.seed_lo = a.seed_lo;
-  key_w.seed_hi = a.seed_hi;
-  key_w.call = a.call + (a.call_base ? __builtin_nontemporal_load(a.call_base) : 0u);
-  key_w.layer_tensor = layer_tensor_word(a.layer_id, 0);
-  uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams (bt_fused_fwd.h)
-  if constexpr (FLIP) {
-    RngKey ks = key_w;
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 2);
-    skey_in = sign_stream_key(ks, sample);
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 3);
-    skey_out = sign_stream_key(ks, sample);
-  }
+  const RngKey key_w = weight_key(a);
+  uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams
+  if constexpr (FLIP) sign_keys(a, key_w, sample, &skey_in, &skey_out);
 
   // ---- active taps of this tile + their window. Every wave computes them (identical values: the table in LDS is written by
   // all waves alike, and a wave reads it behind its own writes), so no workgroup barrier opens the kernel. -------------------
@@ -293,7 +279,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     const float* const stage = smem + 4 * BN;
     const int m4 = t0 % QROW, row0 = t0 / QROW;
     int bq, hq, wq;
-    const bool mok = col_decode(4 * m4, bq, hq, wq);
+    const bool mok = cols.decode(4 * m4, bq, hq, wq);
     const int HoWo_ = a.Ho * a.Wo;
     const int co0 = pass * SROWS + row0;  // first channel (inside the tile) of this thread
     const uint32_t obase = mok ? (uint32_t)(((bq * a.Co + g * a.Cog + n0 + co0) * a.Ho + hq) * a.Wo + wq) : 0u;
@@ -347,7 +333,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     const float* const stage = smem + 4 * BN;
     const int c = t0 % BM, row0 = t0 / BM;
     int bq, hq, wq;
-    const bool mok = col_decode(c, bq, hq, wq);
+    const bool mok = cols.decode(c, bq, hq, wq);
     const int HoWo_ = a.Ho * a.Wo;
     const int co0 = pass * SROWS + row0;
     const uint32_t obase = mok ? (uint32_t)(((bq * a.Co + g * a.Cog + n0 + co0) * a.Ho + hq) * a.Wo + wq) : 0u;
@@ -678,33 +664,11 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     }
     // bias draw + output-stage constants of this workgroup's channels
     if (ptid < BN) {
-      float bv = 0.f;
-      const int co_g = n0 + ptid;
-      if (a.mu_b && co_g < a.Cog) {
-        const int co = g * a.Cog + co_g;
-        float e;
-        if constexpr (INJ) {
-          e = a.eps_b[(long long)s * a.Co + co];
-        } else {
-          RngKey kb = key_w;
-          kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-          float z[4];
-          philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-          const int sel = co & 3;
-          e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
-        }
-        const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
-        bv = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
-        if constexpr (FLIP) bias1[ptid] = dl;
-      } else if constexpr (FLIP) {
-        bias1[ptid] = 0.f;
-      }
-      bias0[ptid] = bv;
-      const bool cv = a.ep_scale && co_g < a.Cog;
-      const int cs = cv ? g * a.Cog + co_g : 0;
-      const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
-      osc[ptid] = cv ? sc : 1.f;
-      osh[ptid] = cv ? sh : 0.f;
+      const ChannelConsts c = channel_consts<FLIP, INJ>(a, key_w, s, g, n0 + ptid);
+      bias0[ptid] = c.bias0;
+      if constexpr (FLIP) bias1[ptid] = c.bias1;
+      osc[ptid] = c.scale;
+      osh[ptid] = c.shift;
     }
     __syncthreads();
     if (a.out_vec4 || stage_cols) {  // the consumers pass the output tile through LDS: same barriers and a share of the read-out
@@ -723,60 +687,20 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     // stage's MFMAs: in the layers with many parameters the consumers wait for the producers anyway, in the MFMA-bound layers
     // a slice is a group or two. Same per-thread order of accumulation as one uninterrupted sweep; the partial is published
     // with write-through stores (publish_and_ticket_wt: no L2 write-back, so publishing late costs nothing extra).
-    long long kl_i = 0, kl_hi = 0;
-    double kl_acc = 0.0;
-    bool kl_v4 = false;
-    if (kl_block) {
-      long long chunk = (a.w_elems + a.kl_slices - 1) / a.kl_slices;
-      chunk = (chunk + 3) & ~3ll;
-      const long long lo = (long long)blockIdx.x * chunk;
-      kl_hi = (lo + chunk < a.w_elems) ? lo + chunk : a.w_elems;
-      kl_v4 = ((((uintptr_t)a.mu_w | (uintptr_t)a.rho_w | (uintptr_t)a.pmu_w | (uintptr_t)a.psig_w) & 15u) == 0);
-      kl_i = lo + 4ll * ptid;
-    }
-    auto kl_terms = [&](const float4& m4, const float4& r4, const float4& p4, const float4& q4) {
-      const float t0 = kl_term(m4.x, softplus(r4.x), p4.x, q4.x) + kl_term(m4.y, softplus(r4.y), p4.y, q4.y);
-      const float t1 = kl_term(m4.z, softplus(r4.z), p4.z, q4.z) + kl_term(m4.w, softplus(r4.w), p4.w, q4.w);
-      kl_acc += (double)t0 + (double)t1;
-      kl_i += 1024;
-    };
-    auto kl_group = [&]() {  // -> false when this thread has no whole float4 group left
-      if (!(kl_v4 && kl_i + 3 < kl_hi)) return false;
-      const float4 m4 = *reinterpret_cast<const float4*>(a.mu_w + kl_i), r4 = *reinterpret_cast<const float4*>(a.rho_w + kl_i);
-      const float4 p4 = *reinterpret_cast<const float4*>(a.pmu_w + kl_i), q4 = *reinterpret_cast<const float4*>(a.psig_w + kl_i);
-      kl_terms(m4, r4, p4, q4);
-      return true;
-    };
+    KlSlice<1024> kls;
+    if (kl_block) kls.open(a, ptid);
     auto kl_finish = [&]() {
-      while (kl_group()) {}
-      for (; kl_i < kl_hi; kl_i += 1024)  // tail quad / unaligned bases
-        for (int j = 0; j < 4; ++j)
-          if (kl_i + j < kl_hi) kl_acc += (double)kl_term(a.mu_w[kl_i + j], softplus(a.rho_w[kl_i + j]), a.pmu_w[kl_i + j], a.psig_w[kl_i + j]);
-      const double wsum = wave_sum(kl_acc);
+      const double wsum = kls.rest(a);
       // every consumer wave stores its partial write-through and drains the store; the workgroup's ONE ticket is taken by
       // thread 0 behind the next workgroup barrier (kl_ticket below): 256 adds on the counter instead of 1024
       if (lane == 0) __hip_atomic_store(&a.slots[(int)blockIdx.x * 4 + wave], wsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     auto kl_ticket = [&]() {  // thread 0's wave, after the barrier that follows kl_finish in every consumer wave
-      const int nslots = 4 * a.kl_slices;
       int last = 0;
       if (lane == 0) last = (__hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)a.kl_slices - 1u) ? 1 : 0;
-      if (__builtin_amdgcn_readfirstlane(last)) {  // this workgroup arrived last: every slot is published
-        double t = 0.0;
-        for (int q = lane; q < nslots; q += 64) t += __hip_atomic_load(&a.slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = wave_sum(t);
-        double bt_ = 0.0;
-        if (a.mu_b)
-          for (int c = lane; c < a.Co; c += 64) bt_ += (double)kl_term(a.mu_b[c], softplus(a.rho_b[c]), a.pmu_b[c], a.psig_b[c]);
-        bt_ = wave_sum(bt_);
-        if (lane == 0) {
-          float kl = (float)(t / (double)a.w_elems);
-          if (a.mu_b) kl += (float)(bt_ / (double)a.Co);
-          a.kl_out[0] = kl;
-          __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-        }
-      }
+      if (__builtin_amdgcn_readfirstlane(last))  // this workgroup arrived last: every slot is published
+        kl_close(a, kl_slot_sum(a, 4 * a.kl_slices, lane), lane);
     };
     // Byte address (inside an x buffer) of this lane's operand fragment for every (column group, step): the (octet, tap) entry
     // of (step, lane half) applied to the lane's output pixel -- or the shared zero pixel when that tap falls into the padding
@@ -788,7 +712,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
         int b, ho, wo;
-        live[j] = col_decode(wm * WTM + j * 32 + li, b, ho, wo);
+        live[j] = cols.decode(wm * WTM + j * 32 + li, b, ho, wo);
         pimg[j] = (b - b0) * PIMG, pyb[j] = (ho - r0) * ps_h, pxb[j] = (wo - w0) * ps_w;
       }
 #pragma unroll
@@ -898,8 +822,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         }
       }
       if (cstamp && st < 60) dbg_[2 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
-      if (kl_block) kl_group();   // (fetching the group one stage ahead was tried in round 3: the 16 registers it holds across the MFMA loop spill on
-                                  //  the 256-wide tiles -- layer3 +5..19 % -- and layer4's 128-wide launches did not move: dropped)
+      if (kl_block) kls.group(a);   // (fetching the group one stage ahead was tried in round 3: the 16 registers it holds across the MFMA loop spill on
+                                    //  the 256-wide tiles -- layer3 +5..19 % -- and layer4's 128-wide launches did not move: dropped)
       __syncthreads();
     }
     if (kl_block) kl_finish();
@@ -987,7 +911,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           for (int r2 = 0; r2 < 8; ++r2) {
             const int r = 2 * r2, row = (r & 3) + 8 * (r >> 2) + 4 * lh;   // even
             int bb, hh, ww;
-            live[r2] = col_decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (ww == 0; column + 1 is the same image's second pixel)
+            live[r2] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (ww == 0; column + 1 is the same image's second pixel)
             base[r2] = live[r2] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo + hh * a.Wo + ww) : 0u;
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
@@ -1021,7 +945,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           for (int q = 0; q < 4; ++q) {
             const int row = 8 * q + 4 * lh;   // a multiple of 4
             int bb, hh, ww;
-            live[q] = col_decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (pixel 0 of image bb)
+            live[q] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (pixel 0 of image bb)
             base[q] = live[q] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo) : 0u;
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
@@ -1056,7 +980,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         for (int r = 0; r < 16; ++r) {
           const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
           int bb, hh, ww;
-          live[r] = col_decode(wm * WTM + j * 32 + row, bb, hh, ww);
+          live[r] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);
           base[r] = live[r] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo + hh * a.Wo + ww) : 0u;  // channel n0 of this pixel
 #pragma unroll
           for (int i = 0; i < TN; ++i) {

@@ -23,6 +23,7 @@
 // Canonical K order, term order, draw stream and output-stage arithmetic are those of bt_fused_split.h (one active tap: consecutive
 // octets in pairs), so the results are bit-identical to the general kernel's (tests/test_gpu_round3.py).
 #pragma once
+#include "bt_fused_common.h"
 #include "bt_fused_split.h"
 
 namespace bt {
@@ -59,53 +60,17 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
   const uint32_t sample = a.sample0 + (uint32_t)s;
   const int Cig = a.Cig, HW = a.HW, HWo = a.HoWo;
 
-  RngKey key_w;
-  key_w.seed_lo = a.seed_lo;
-  key_w.seed_hi = a.seed_hi;
-  key_w.call = a.call + (a.call_base ? __builtin_nontemporal_load(a.call_base) : 0u);
-  key_w.layer_tensor = layer_tensor_word(a.layer_id, 0);
+  const RngKey key_w = weight_key(a);
 
   // ---- KL: the first kl_slices workgroups sweep a slice of the natural-layout parameters each (all 8 waves), before anything else
   const bool kl_block = a.do_kl && (int)blockIdx.x < a.kl_slices;
   if (kl_block) {
-    long long chunk_e = (a.w_elems + a.kl_slices - 1) / a.kl_slices;
-    chunk_e = (chunk_e + 3) & ~3ll;
-    const long long lo = (long long)blockIdx.x * chunk_e;
-    const long long hi = (lo + chunk_e < a.w_elems) ? lo + chunk_e : a.w_elems;
-    const bool v4 = ((((uintptr_t)a.mu_w | (uintptr_t)a.rho_w | (uintptr_t)a.pmu_w | (uintptr_t)a.psig_w) & 15u) == 0);
-    double acc = 0.0;
-    long long i = lo + 4ll * tid;
-    if (v4) {
-      // four groups per trip, all 16 loads in flight before the first use (ResNet18 / CIFAR layer4: 18 groups per thread -- one at a time
-      // that is 18 exposed memory round trips, ~45 K cycles, at the head of a 100 K-cycle workgroup); same per-thread order of accumulation
-      while (i + 3 < hi) {
-        float4 m4[4], r4[4], p4[4], q4[4];
-        bool ok[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const long long iu = i + (long long)u * 4 * kDirectThreads;
-          ok[u] = iu + 3 < hi;
-          if (ok[u]) {
-            m4[u] = *reinterpret_cast<const float4*>(a.mu_w + iu), r4[u] = *reinterpret_cast<const float4*>(a.rho_w + iu);
-            p4[u] = *reinterpret_cast<const float4*>(a.pmu_w + iu), q4[u] = *reinterpret_cast<const float4*>(a.psig_w + iu);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (ok[u]) {
-            const float t0 = kl_term(m4[u].x, softplus(r4[u].x), p4[u].x, q4[u].x) + kl_term(m4[u].y, softplus(r4[u].y), p4[u].y, q4[u].y);
-            const float t1 = kl_term(m4[u].z, softplus(r4[u].z), p4[u].z, q4[u].z) + kl_term(m4[u].w, softplus(r4[u].w), p4[u].w, q4[u].w);
-            acc += (double)t0 + (double)t1;
-            i += 4 * kDirectThreads;
-          }
-        }
-      }
-    }
-    for (; i < hi; i += 4 * kDirectThreads)  // tail quad / unaligned bases
-      for (int j = 0; j < 4; ++j)
-        if (i + j < hi) acc += (double)kl_term(a.mu_w[i + j], softplus(a.rho_w[i + j]), a.pmu_w[i + j], a.psig_w[i + j]);
-    const double wsum = wave_sum(acc);
-    // write-through partial per wave, drained; ONE ticket per workgroup behind the barrier below (bt_fused_split.h, kl_finish / kl_ticket)
+    // four groups per trip, all 16 loads in flight before the first use (ResNet18 / CIFAR layer4: 18 groups per thread -- one at a time
+    // that is 18 exposed memory round trips, ~45 K cycles, at the head of a 100 K-cycle workgroup)
+    KlSlice<4 * kDirectThreads> kls;
+    kls.open(a, tid);
+    const double wsum = kls.rest_batched<4>(a);
+    // write-through partial per wave, drained; ONE ticket per workgroup behind the barrier below (the general split kernel's hand-off)
     if (lane == 0) __hip_atomic_store(&a.slots[(int)blockIdx.x * 8 + wave], wsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
@@ -197,48 +162,15 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
   }
   // bias draw + output-stage constants of the tile's channels
   if (tid < BN) {
-    float bv = 0.f;
-    const int co_g = n0 + tid;
-    if (a.mu_b && co_g < a.Cog) {
-      const int co = g * a.Cog + co_g;
-      float e;
-      if constexpr (INJ) {
-        e = a.eps_b[(long long)s * a.Co + co];
-      } else {
-        RngKey kb = key_w;
-        kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-        float z[4];
-        philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-        const int sel = co & 3;
-        e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
-      }
-      bv = __fadd_rn(a.mu_b[co], __fmul_rn(softplus(a.rho_b[co]), e));
-    }
-    const bool cv = a.ep_scale && co_g < a.Cog;
-    const int cs = cv ? g * a.Cog + co_g : 0;
-    const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
-    cst[tid] = make_float4(bv, cv ? sc : 1.f, cv ? sh : 0.f, 0.f);
+    const ChannelConsts c = channel_consts<false, INJ>(a, key_w, s, g, n0 + tid);
+    cst[tid] = make_float4(c.bias0, c.scale, c.shift, 0.f);
   }
   __syncthreads();  // weights and constants staged; every wave's KL partial published
   if (kl_block && wave == 0) {
-    const int nslots = 8 * a.kl_slices;
     int last = 0;
     if (lane == 0) last = (__hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)a.kl_slices - 1u) ? 1 : 0;
-    if (__builtin_amdgcn_readfirstlane(last)) {  // this workgroup arrived last: every slot is published
-      double t = 0.0;
-      for (int q = lane; q < nslots; q += 64) t += __hip_atomic_load(&a.slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      t = wave_sum(t);
-      double bt_ = 0.0;
-      if (a.mu_b)
-        for (int c = lane; c < a.Co; c += 64) bt_ += (double)kl_term(a.mu_b[c], softplus(a.rho_b[c]), a.pmu_b[c], a.psig_b[c]);
-      bt_ = wave_sum(bt_);
-      if (lane == 0) {
-        float kl = (float)(t / (double)a.w_elems);
-        if (a.mu_b) kl += (float)(bt_ / (double)a.Co);
-        a.kl_out[0] = kl;
-        __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-      }
-    }
+    if (__builtin_amdgcn_readfirstlane(last))  // this workgroup arrived last: every slot is published
+      kl_close(a, kl_slot_sum(a, 8 * a.kl_slices, lane), lane);
   }
 
   // ---- steady state: every wave for itself -----------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 //   * W: as in bt_fused_split.h; a weight unit (row, tap) fills half a 16-byte slot. A stage is 5 steps = 20 taps; 49 taps
 //     = 3 stages over the same staged patch (W double-buffered).
 #pragma once
+#include "bt_fused_common.h"
 #include "bt_fused_split.h"
 
 namespace bt {
@@ -92,29 +93,13 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
   const int b0 = bt * t_NI, r0 = rt * t_R, w0 = ct * t_Wt;
   const uint32_t inv_rw = RW > 1 ? (a.inv_rw ? a.inv_rw : inv32(RW)) : 0u;
   const uint32_t inv_wt = t_Wt > 1 ? (a.inv_wt ? a.inv_wt : inv32(t_Wt)) : 0u;
-  auto col_decode = [&](int ml, int& b, int& ho, int& wo) -> bool {
-    const int img = RW == 1 ? ml : (int)__umulhi((uint32_t)ml, inv_rw);
-    const int rem = ml - img * RW;
-    const int r = t_Wt == 1 ? rem : (int)__umulhi((uint32_t)rem, inv_wt);
-    b = b0 + img, ho = r0 + r, wo = w0 + (rem - r * t_Wt);
-    return ml < Mt && b < a.B && ho < a.Ho && wo < a.Wo;
-  };
+  const ColDecode cols = {b0, r0, w0, RW, Mt, t_Wt, inv_rw, inv_wt, a.B, a.Ho, a.Wo};
   const uint32_t sample = a.sample0 + (uint32_t)s;
   const int T = a.T, Cig = a.Cig;  // Cig <= 4: the packed tensors hold one quad per (row, tap)
 
-  RngKey key_w;
-  key_w.seed_lo = a.seed_lo;
-  key_w.seed_hi = a.seed_hi;
-  key_w.call = a.call + (a.call_base ? __builtin_nontemporal_load(a.call_base) : 0u);
-  key_w.layer_tensor = layer_tensor_word(a.layer_id, 0);
-  uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams (bt_fused_fwd.h)
-  if constexpr (FLIP) {
-    RngKey ks = key_w;
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 2);
-    skey_in = sign_stream_key(ks, sample);
-    ks.layer_tensor = layer_tensor_word(a.layer_id, 3);
-    skey_out = sign_stream_key(ks, sample);
-  }
+  const RngKey key_w = weight_key(a);
+  uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams
+  if constexpr (FLIP) sign_keys(a, key_w, sample, &skey_in, &skey_out);
 
   if (wave == 0) {  // active taps + their window
     bool act = false;
@@ -187,7 +172,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
         const int cr = c0q + kThreadsAll * u, c = cr < NQD ? cr : 0;
         const int row = c / QROW, m4 = c - row * QROW;
         int bq, hq, wq;
-        const bool mok = col_decode(4 * m4, bq, hq, wq);
+        const bool mok = cols.decode(4 * m4, bq, hq, wq);
         okq[u] = cr < NQD && mok && n0 + row < a.Cog;
         oidx[u] = okq[u] ? (uint32_t)(((bq * a.Co + g * a.Cog + n0 + row) * a.Ho + hq) * a.Wo + wq) : 0u;
         v[u] = *reinterpret_cast<const float4*>(stage + row * SROW + 4 * m4);
@@ -252,7 +237,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     float* const stage = smem + 4 * BN;
     const int m4 = t0 % QROW, row0 = t0 / QROW;
     int bq, hq, wq;
-    const bool mok = col_decode(4 * m4, bq, hq, wq);
+    const bool mok = cols.decode(4 * m4, bq, hq, wq);
     const int HoWo_ = a.Ho * a.Wo;
     const uint32_t obase = mok ? (uint32_t)(((bq * a.Co + g * a.Cog + n0 + row0) * a.Ho + hq) * a.Wo + wq) : 0u;
 #pragma unroll
@@ -380,35 +365,13 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
         }
       }
     };
-    // bias draw + output-stage constants of sample smp (threads ptid < BN)
-    auto bias_consts = [&](uint32_t smp, float* const b0p, float* const b1p, float* const scp, float* const shp) {
-      float bv = 0.f;
-      const int co_g = n0 + ptid;
-      if (a.mu_b && co_g < a.Cog) {
-        const int co = g * a.Cog + co_g;
-        float e;
-        if constexpr (INJ) {
-          e = a.eps_b[(long long)s * a.Co + co];
-        } else {
-          RngKey kb = key_w;
-          kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-          float z[4];
-          philox_normal4(kb, smp, (uint32_t)(co >> 2), z);
-          const int sel = co & 3;
-          e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
-        }
-        const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
-        bv = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
-        if constexpr (FLIP) b1p[ptid] = dl;
-      } else if constexpr (FLIP) {
-        b1p[ptid] = 0.f;
-      }
-      b0p[ptid] = bv;
-      const bool cv = a.ep_scale && co_g < a.Cog;
-      const int cs = cv ? g * a.Cog + co_g : 0;
-      const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
-      scp[ptid] = cv ? sc : 1.f;
-      shp[ptid] = cv ? sh : 0.f;
+    // bias draw + output-stage constants of the launch's sample sk (threads ptid < BN)
+    auto bias_consts = [&](int sk, float* const b0p, float* const b1p, float* const scp, float* const shp) {
+      const ChannelConsts c = channel_consts<FLIP, INJ>(a, key_w, sk, g, n0 + ptid);
+      b0p[ptid] = c.bias0;
+      if constexpr (FLIP) b1p[ptid] = c.bias1;
+      scp[ptid] = c.scale;
+      shp[ptid] = c.shift;
     };
     if constexpr (WALK) {
       // stage stream of the samples sample .. sample + nsw - 1, back to back: G counts the stages (W buffer G & 1); a sample's
@@ -424,7 +387,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
             if (st + 1 < NS) load_w(st + 1);
             else if (k + 1 < nsw) load_w(0);  // the next sample's stage 0: no bubble at the sample boundary
           }
-          if (st == 0 && ptid < BN) bias_consts(smp, cs_, cs_, cs_ + BN, cs_ + 2 * BN);
+          if (st == 0 && ptid < BN) bias_consts(s + k, cs_, cs_, cs_ + BN, cs_ + 2 * BN);
           __syncthreads();
         }
       }
@@ -438,7 +401,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       }
       __syncthreads();
     }
-    if (ptid < BN) bias_consts(sample, bias0, bias1, osc, osh);
+    if (ptid < BN) bias_consts(s, bias0, bias1, osc, osh);
     __syncthreads();
     __syncthreads();
     if constexpr (FLIP) {
@@ -450,62 +413,25 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
     }
   } else {
     // =================================================== CONSUMERS ===========================================================
-    long long kl_i = 0, kl_hi = 0;
-    double kl_acc = 0.0;
-    bool kl_v4 = false;
-    if (kl_block) {
-      long long chunk = (a.w_elems + a.kl_slices - 1) / a.kl_slices;
-      chunk = (chunk + 3) & ~3ll;
-      const long long lo = (long long)blockIdx.x * chunk;
-      kl_hi = (lo + chunk < a.w_elems) ? lo + chunk : a.w_elems;
-      kl_v4 = ((((uintptr_t)a.mu_w | (uintptr_t)a.rho_w | (uintptr_t)a.pmu_w | (uintptr_t)a.psig_w) & 15u) == 0);
-      kl_i = lo + 4ll * ptid;
-    }
-    auto kl_group = [&]() {
-      if (!(kl_v4 && kl_i + 3 < kl_hi)) return false;
-      const float4 m4 = *reinterpret_cast<const float4*>(a.mu_w + kl_i), r4 = *reinterpret_cast<const float4*>(a.rho_w + kl_i);
-      const float4 p4 = *reinterpret_cast<const float4*>(a.pmu_w + kl_i), q4 = *reinterpret_cast<const float4*>(a.psig_w + kl_i);
-      const float t0 = kl_term(m4.x, softplus(r4.x), p4.x, q4.x) + kl_term(m4.y, softplus(r4.y), p4.y, q4.y);
-      const float t1 = kl_term(m4.z, softplus(r4.z), p4.z, q4.z) + kl_term(m4.w, softplus(r4.w), p4.w, q4.w);
-      kl_acc += (double)t0 + (double)t1;
-      kl_i += 1024;
-      return true;
-    };
-    auto kl_finish = [&]() {
-      while (kl_group()) {}
-      for (; kl_i < kl_hi; kl_i += 1024)
-        for (int j = 0; j < 4; ++j)
-          if (kl_i + j < kl_hi) kl_acc += (double)kl_term(a.mu_w[kl_i + j], softplus(a.rho_w[kl_i + j]), a.pmu_w[kl_i + j], a.psig_w[kl_i + j]);
-      const double wsum = wave_sum(kl_acc);
+    KlSlice<1024> kls;
+    if (kl_block) kls.open(a, ptid);
+    auto kl_finish = [&]() {  // a slot per consumer wave, drained; ONE ticket per workgroup behind the next barrier
+      const double wsum = kls.rest(a);
       if (lane == 0) __hip_atomic_store(&a.slots[(int)blockIdx.x * 4 + wave], wsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
     auto kl_ticket = [&]() {
-      const int nslots = 4 * a.kl_slices;
       int last = 0;
       if (lane == 0) last = (__hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)a.kl_slices - 1u) ? 1 : 0;
-      if (__builtin_amdgcn_readfirstlane(last)) {
-        double t = 0.0;
-        for (int q = lane; q < nslots; q += 64) t += __hip_atomic_load(&a.slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = wave_sum(t);
-        double bt_ = 0.0;
-        if (a.mu_b)
-          for (int c = lane; c < a.Co; c += 64) bt_ += (double)kl_term(a.mu_b[c], softplus(a.rho_b[c]), a.pmu_b[c], a.psig_b[c]);
-        bt_ = wave_sum(bt_);
-        if (lane == 0) {
-          float kl = (float)(t / (double)a.w_elems);
-          if (a.mu_b) kl += (float)(bt_ / (double)a.Co);
-          a.kl_out[0] = kl;
-          __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
+      if (__builtin_amdgcn_readfirstlane(last))
+        kl_close(a, kl_slot_sum(a, 4 * a.kl_slices, lane), lane);
     };
     int colq[TM];  // byte offset of this lane's output pixel inside the patch, per 32-wide column group
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
       const int ml = wm * WTM + j * 32 + li;
       int b, ho, wo;
-      const bool live = col_decode(ml, b, ho, wo);
+      const bool live = cols.decode(ml, b, ho, wo);
       colq[j] = live ? ((b - b0) * PIMG + (ho - r0) * ps_h * PWt + (wo - w0) * ps_w) * PBQ : 0;
     }
     int wlq[STEPS];
@@ -642,10 +568,10 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
             }
             if (kl_block) {
               if (k + 1 == nsw) kl_finish();
-              else kl_group();
+              else kls.group(a);
             }
           } else if (kl_block) {
-            kl_group();
+            kls.group(a);
           }
           __syncthreads();
         }
@@ -700,7 +626,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       if (stamp0) dbg_[2 + 2 * st] = __builtin_amdgcn_s_memtime();
       run_stage(st, wbuf + (st & 1) * W_BYTES);
       if (stamp0) dbg_[2 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
-      if (kl_block) kl_group();
+      if (kl_block) kls.group(a);
       __syncthreads();
     }
     if (kl_block) kl_finish();

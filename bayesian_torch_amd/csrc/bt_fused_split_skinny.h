@@ -19,6 +19,7 @@
 // workgroup), the parameter / x / KL traffic of 4 workgroups per CU through one 64 B/clk L1 path and a second round of workgroups
 // (1024 ... 2048 for 768 slots) cost what the shorter chains save (60 vs 53 ... 60 us; 140 vs 71 with four live taps). DESIGN.md 4.0b.
 #pragma once
+#include "bt_fused_common.h"
 #include "bt_fused_split.h"
 
 namespace bt {
@@ -113,6 +114,10 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
     if (a.ep_scale && in) c_sc = a.ep_scale[co], c_sh = a.ep_shift[co];
   }
 
+  // The key setup, the KL sweep and its close below are this kernel's OWN copies of weight_key, KlSlice::rest_batched and kl_close
+  // (bt_fused_common.h), statement for statement: the on-chip instantiation sits at the 168-VGPR cap of three workgroups per CU, and
+  // with any one of the three inlined from the shared header the register allocator spills a ninth VGPR (36 -> 40 bytes of scratch).
+  // The quad pairing (kl_quad) and the bias draw (bias_eps) are the shared ones.
   RngKey key_w;
   key_w.seed_lo = a.seed_lo;
   key_w.seed_hi = a.seed_hi;
@@ -147,9 +152,7 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
 #pragma unroll
         for (int u = 0; u < KLB; ++u) {
           if (ok[u]) {
-            const float t0 = kl_term(m4[u].x, softplus(r4[u].x), p4[u].x, q4[u].x) + kl_term(m4[u].y, softplus(r4[u].y), p4[u].y, q4[u].y);
-            const float t1 = kl_term(m4[u].z, softplus(r4[u].z), p4[u].z, q4[u].z) + kl_term(m4[u].w, softplus(r4[u].w), p4[u].w, q4[u].w);
-            acc += (double)t0 + (double)t1;
+            acc += kl_quad(m4[u], r4[u], p4[u], q4[u]);
             i += 4 * kSkinnyThreads;
           }
         }
@@ -301,13 +304,7 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
       if constexpr (INJ) {
         e = c_epb;
       } else {
-        const int co = g * a.Cog + n0 + tid - 64;
-        RngKey kb = key_w;
-        kb.layer_tensor = layer_tensor_word(a.layer_id, 1);
-        float z[4];
-        philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
-        const int sel = co & 3;
-        e = sel == 0 ? z[0] : sel == 1 ? z[1] : sel == 2 ? z[2] : z[3];
+        e = bias_eps(key_w, a.layer_id, sample, g * a.Cog + n0 + tid - 64);
       }
       bv = __fadd_rn(c_mub, __fmul_rn(softplus(c_rhob), e));
     }

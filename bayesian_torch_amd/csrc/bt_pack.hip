@@ -64,14 +64,6 @@ __device__ __forceinline__ unsigned long long fp_mix(unsigned long long i, float
   return h;
 }
 
-// One element's KL term, as the fused forwards' sweep forms it (bt_fused_split.h, kl_terms): the four terms of an aligned quad are
-// added in fp32 in pairs, and the pairs go into the double accumulator.
-__device__ __forceinline__ double kl_quad(const float4& m, const float4& r, const float4& p, const float4& q) {
-  const float t0 = kl_term(m.x, softplus(r.x), p.x, q.x) + kl_term(m.y, softplus(r.y), p.y, q.y);
-  const float t1 = kl_term(m.z, softplus(r.z), p.z, q.z) + kl_term(m.w, softplus(r.w), p.w, q.w);
-  return (double)t0 + (double)t1;
-}
-
 template <bool KL>
 __device__ __forceinline__ void fp_sweep(const FpSegs& sg, int seg, int nb, int lb, unsigned long long& acc, double& kacc) {
   const long long n = sg.n[seg];
