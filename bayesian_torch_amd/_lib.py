@@ -18,6 +18,12 @@ KL_RHO_IS_SIGMA = 1
 KL_PRIOR_LAPLACE = 2
 PRIOR_NORMAL, PRIOR_LAPLACE = 0, 1
 DRAWS_EPS_PACKED = 1   # bt_rng.flags: eps_w holds [S] packed images (bt_pack_eps)
+DRAWS_SIGNS_PACKED = 2  # bt_rng.flags: sign_in / sign_out hold [S] byte images (bt_pack_signs); Flipout, with DRAWS_EPS_PACKED
+
+
+def signs_packed_stride(n):
+    """BT_SIGNS_PACKED_STRIDE: bytes of one sample's image of n signs."""
+    return (int(n) + 15) // 16 * 16
 
 _f32p = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -86,6 +92,7 @@ _PROTOS = {
     "bt_pack_sync_kl": (C.c_int, [C.c_int32, C.POINTER(bt_pack_seg), C.POINTER(bt_pack_kl), _vp, C.c_size_t, _vp]),
     "bt_pack_params": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "bt_pack_eps": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
+    "bt_pack_signs": (C.c_int, [_vp, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "bt_rng_normal_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "bt_rng_sign_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, _vp, _vp]),
     "bt_rng_philox_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

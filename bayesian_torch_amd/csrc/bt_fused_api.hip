@@ -10,6 +10,7 @@ int launch_reparam_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t 
 int launch_flipout(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);   // bt_fused_split.hip: 0 taken, 1 not applicable, < 0 error
+int launch_split_flip(FwdArgs a, FwdArgs& ran, hipStream_t stream);   // bt_fused_split_flip.hip: likewise
 int contraction_mode();
 
 static unsigned long long* g_dbg = nullptr;
@@ -43,18 +44,22 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
   if (!flip && (d->sign_in || d->sign_out)) return bad("sign tensors are Flipout-only");
   if (ep && ((ep->scale == nullptr) != (ep->shift == nullptr))) return bad("epilogue scale and shift must both be given or both be NULL");
   if (ep && ep->residual_sample_stride < 0) return bad("negative residual_sample_stride");
-  // packed draws (bt_pack_eps): the split-precision kernels' injected instantiations, or nothing
-  if (d->rng.flags & ~BT_DRAWS_EPS_PACKED) return bad("unknown bt_rng.flags bit");
-  const bool eps_packed = (d->rng.flags & BT_DRAWS_EPS_PACKED) != 0;
+  // packed draws (bt_pack_eps, bt_pack_signs): the split-precision kernels' injected instantiations, or nothing
+  if (d->rng.flags & ~(BT_DRAWS_EPS_PACKED | BT_DRAWS_SIGNS_PACKED)) return bad("unknown bt_rng.flags bit");
+  const bool eps_packed = (d->rng.flags & BT_DRAWS_EPS_PACKED) != 0, signs_packed = (d->rng.flags & BT_DRAWS_SIGNS_PACKED) != 0;
+  if (signs_packed && (!eps_packed || !flip)) return bad("bt_rng.flags: BT_DRAWS_SIGNS_PACKED goes with BT_DRAWS_EPS_PACKED, on a Flipout entry point");
   if (eps_packed) {
     auto unsupported = [&](const char* what) {
       snprintf(msg, sizeof(msg), "%s: BT_DRAWS_EPS_PACKED: %s", who, what);
       return set_error(BT_ERR_UNSUPPORTED, msg);
     };
     if (!d->eps_w) return bad("BT_DRAWS_EPS_PACKED without eps_w");
-    if (flip || d->sign_in || d->sign_out) return unsupported("Flipout / sign tensors are not served (inject the natural layout)");
+    if (!signs_packed && (flip || d->sign_in || d->sign_out))
+      return unsupported("Flipout needs its sign tensors packed too (bt_pack_signs, BT_DRAWS_SIGNS_PACKED), or inject the natural layout");
+    if (signs_packed && (!d->sign_in || !d->sign_out)) return bad("BT_DRAWS_SIGNS_PACKED without sign_in / sign_out");
     if (!p->mu_packed || !p->sigma_packed) return bad("BT_DRAWS_EPS_PACKED needs mu_packed / sigma_packed");
     if (!al16(d->eps_w)) return bad("BT_DRAWS_EPS_PACKED: eps_w must be 16-byte aligned");
+    if (signs_packed && (!al16(d->sign_in) || !al16(d->sign_out))) return bad("BT_DRAWS_SIGNS_PACKED: sign_in / sign_out must be 16-byte aligned");
     if (contraction_mode() != 0) return unsupported("the contraction is forced to f32 / bf16x2 (bt_set_contraction, BT_CONTRACTION): only the exact split reads packed draws");
   }
 
@@ -126,7 +131,7 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
   int rc;
   FwdArgs r;   // the plan that ran
   if (eps_packed) {   // the split chain alone; it launches nothing when it declines
-    rc = launch_split(a, r, (hipStream_t)stream);
+    rc = flip ? launch_split_flip(a, r, (hipStream_t)stream) : launch_split(a, r, (hipStream_t)stream);
     if (rc == 1) {
       snprintf(msg, sizeof(msg), "%s: BT_DRAWS_EPS_PACKED: no split-precision flavour takes this launch (inject the natural layout)", who);
       return set_error(BT_ERR_UNSUPPORTED, msg);

@@ -106,9 +106,14 @@ __device__ __forceinline__ int div_small(int n, int d) { return d == 1 ? n : d =
 // (bt_pack_eps), so a unit's four draws are one more 16-byte load at the offset of its two parameter loads, issued with them (one
 // stage ahead), and a.eps_b [S][Co] the bias draws. Everything behind the draw is the on-chip code: the same eps bits give the same
 // output bits.
+//
+// FLIP && INJ (Flipout, bt_fused_split_flip_inj.hip; BT_DRAWS_EPS_PACKED | BT_DRAWS_SIGNS_PACKED): besides the draws, the two sign
+// streams are READ -- a.sign_in / a.sign_out hold [S] BYTE images (bt_pack_signs: one byte per element in the tensor's own order,
+// 0x00 = +1, 0x80 = -1, a sample's image a multiple of 16 bytes), indexed by exactly the numbers the hash streams take: the element's
+// offset in the sample's x, the output element's index. The s_in bytes of an x item are fetched with its x loads (one stage ahead;
+// where x moves as float4 its four signs are one dword), s_out in the read-out. byte << 24 is the fp32 sign mask.
 template <int BN, int BM, int NP, int NPW, int XM, bool FLIP = false, bool INJ = false>
 __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdArgs a) {
-  static_assert(!(FLIP && INJ), "injected draws: Reparameterization only");
   static_assert((BN == 64 && (BM == 512 || BM == 256 || BM == 128)) || (BN == 32 && BM == 128 && !FLIP), "tile shapes of this flavour");
   static_assert(!FLIP || ((BM == 256 || BM == 128) && NP == 3), "Flipout: the 64 x 256 / 64 x 128 tiles, exact split");
   constexpr int kProducers = 64 * NPW, kThreadsAll = 256 + kProducers;
@@ -258,6 +263,21 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
   auto ldf = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0)); };
   auto ldf4 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0)); };
+  // FLIP && INJ: this sample's sign images (per sample also when x is shared). The fp32 factor of a packed s_out byte: +-1.0.
+  constexpr bool SGN = FLIP && INJ;
+  [[maybe_unused]] const auto r_si = [&] {   // (nothing at all in the other instantiations)
+    if constexpr (SGN) {
+      const int si_bytes = (int)((a.x_elems + 15) & ~15ll);
+      return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.sign_in)) + (long long)s * si_bytes, 0, si_bytes, 0x00020000);
+    } else {
+      return 0;
+    }
+  }();
+  [[maybe_unused]] const auto so_s = [&] {
+    if constexpr (SGN) return reinterpret_cast<const unsigned char*>(a.sign_out) + (long long)s * (((long long)a.M * a.Co + 15) & ~15ll);
+    else return 0;
+  }();
+  [[maybe_unused]] auto so_f = [](uint32_t word, int k) -> float { return __uint_as_float(0x3F800000u | ((word << (24 - 8 * k)) & 0x80000000u)); };
 
   float* const bias0 = smem;
   float* const bias1 = smem + BN;  // Flipout: the sigma*eps part of the bias
@@ -301,10 +321,18 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           const float4 d = *reinterpret_cast<const float4*>(sp + (SROWS + rr) * SROW);
           const int co_l = okq[u] ? co0 + k * RSTEP : 0;
           const float sc = osc[co_l], sh = osh[co_l];
+          if constexpr (INJ) {  // the quad's four signs: one dword (oidx is a multiple of 4, the image 16-byte aligned)
+            const uint32_t sw = *reinterpret_cast<const uint32_t*>(so_s + oidx[u]);
+            v[u].x = __fadd_rn(__fmul_rn(__fadd_rn(v[u].x, __fmul_rn(d.x, so_f(sw, 0))), sc), sh);
+            v[u].y = __fadd_rn(__fmul_rn(__fadd_rn(v[u].y, __fmul_rn(d.y, so_f(sw, 1))), sc), sh);
+            v[u].z = __fadd_rn(__fmul_rn(__fadd_rn(v[u].z, __fmul_rn(d.z, so_f(sw, 2))), sc), sh);
+            v[u].w = __fadd_rn(__fmul_rn(__fadd_rn(v[u].w, __fmul_rn(d.w, so_f(sw, 3))), sc), sh);
+          } else {
           v[u].x = __fadd_rn(__fmul_rn(__fadd_rn(v[u].x, __fmul_rn(d.x, hash_sign(skey_out, oidx[u]))), sc), sh);
           v[u].y = __fadd_rn(__fmul_rn(__fadd_rn(v[u].y, __fmul_rn(d.y, hash_sign(skey_out, oidx[u] + 1u))), sc), sh);
           v[u].z = __fadd_rn(__fmul_rn(__fadd_rn(v[u].z, __fmul_rn(d.z, hash_sign(skey_out, oidx[u] + 2u))), sc), sh);
           v[u].w = __fadd_rn(__fmul_rn(__fadd_rn(v[u].w, __fmul_rn(d.w, hash_sign(skey_out, oidx[u] + 3u))), sc), sh);
+          }
         }
       }
       if (res_s) {
@@ -349,7 +377,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       if constexpr (FLIP) {
         const float d = sp[(SROWS + rr) * SROW];
         const int co_l = ok ? co0 + k * RSTEP : 0;
-        v = __fadd_rn(__fmul_rn(__fadd_rn(v, __fmul_rn(d, hash_sign(skey_out, oi))), osc[co_l]), osh[co_l]);
+        if constexpr (INJ) v = __fadd_rn(__fmul_rn(__fadd_rn(v, __fmul_rn(d, so_f((uint32_t)so_s[oi], 0))), osc[co_l]), osh[co_l]);
+        else v = __fadd_rn(__fmul_rn(__fadd_rn(v, __fmul_rn(d, hash_sign(skey_out, oi))), osc[co_l]), osh[co_l]);
       }
       if (res_s && ok) v = __fadd_rn(v, res_s[oi]);
       v = (relu && v < 0.f) ? 0.f : v;
@@ -505,6 +534,13 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     // One stage = loads (issued one stage AHEAD, into registers that the previous stage has just consumed) -> draws (pure
     // ALU: they run while the loads are in flight) -> sampled weights -> pieces -> LDS -> activations -> pieces -> LDS.
     float xv[PIT][XV];
+    // FLIP && INJ: the s_in bytes of the item's elements, loaded with them. XM 0: one byte per channel; XM 1: the 8 channels' bytes as
+    // two dwords; XM 2 / 3: one dword per channel (the float4's four pixels). The byte offset of a sign is its x byte offset / 4.
+    constexpr int XSG = !SGN ? 1 : XM == 0 ? 8 : XM == 3 ? 4 : 2;
+    static_assert(!SGN || XM <= 3, "supplied signs: the x fetch modes the Flipout flavour launches");
+    [[maybe_unused]] uint32_t sgv[SGN ? PIT : 1][XSG];
+    [[maybe_unused]] auto ldsg = [&](const auto& r, uint32_t byte_off) { return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0); };
+    [[maybe_unused]] auto ldsb = [&](const auto& r, uint32_t byte_off) { return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r, (int)byte_off, 0, 0); };
     auto load_x = [&](int st) {  // every item of stage st
       const int oct0 = st * NO;
 #pragma unroll
@@ -512,6 +548,21 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         if (i == 0 || wave_i0 + kProducers * i < n_items_w) {  // wave-uniform
           const int oc = oct0 + it_ol[i];
           const bool in = it_off[i] != (int)kOOB && oc < G8;  // octets past the end read zeros (their weights are zeros too)
+          if constexpr (SGN) {  // (masked items read byte 0x00: their x is zero)
+            const uint32_t e0b = (uint32_t)it_off[i] >> 2;
+            if constexpr (XM == 2) {
+#pragma unroll
+              for (int c = 0; c < 2; ++c) sgv[i][c] = ldsg(r_si, guard_off(in, e0b + (uint32_t)(4 * (8 * oc + c))));
+            } else if constexpr (XM == 1) {
+              sgv[i][0] = ldsg(r_si, guard_off(in, e0b + (uint32_t)(8 * oc))), sgv[i][1] = ldsg(r_si, guard_off(in, e0b + (uint32_t)(8 * oc + 4)));
+            } else if constexpr (XM == 3) {
+#pragma unroll
+              for (int c = 0; c < 4; ++c) sgv[i][c] = ldsg(r_si, guard_off(in, e0b + (uint32_t)((8 * oc + c) * a.HW)));
+            } else {
+#pragma unroll
+              for (int c = 0; c < 8; ++c) sgv[i][c] = ldsb(r_si, guard_off(in, e0b + (uint32_t)((8 * oc + c) * a.HW)));
+            }
+          }
           if constexpr (XM == 2) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -558,6 +609,18 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       if constexpr (NP == 3)
         *reinterpret_cast<uint4*>(dst + 32) = make_uint4(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]), pack_hi16(pl[5], pl[4]), pack_hi16(pl[7], pl[6]));
     };
+    // FLIP && INJ: the same with the pixel's sign bytes as loaded (XM 1: byte c of the two dwords; XM 0: one byte per channel)
+    [[maybe_unused]] auto store_px_sg = [&](char* dst, const float (&v)[8], const auto& sg) {
+      uint32_t ph[8], pm[8], pl[8], sb[8];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) split_pieces(v[c], ph[c], pm[c], pl[c]);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) sb[c] = XM == 1 ? (sg[c >> 2] << (24 - 8 * (c & 3))) & 0x80000000u : sg[c & (XSG - 1)] << 24;
+      *reinterpret_cast<uint4*>(dst + 16 * NP) = make_uint4(pack_hi16(sb[1], sb[0]), pack_hi16(sb[3], sb[2]), pack_hi16(sb[5], sb[4]), pack_hi16(sb[7], sb[6]));
+      *reinterpret_cast<uint4*>(dst) = make_uint4(pack_hi16(ph[1], ph[0]), pack_hi16(ph[3], ph[2]), pack_hi16(ph[5], ph[4]), pack_hi16(ph[7], ph[6]));
+      *reinterpret_cast<uint4*>(dst + 16) = make_uint4(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]), pack_hi16(pm[5], pm[4]), pack_hi16(pm[7], pm[6]));
+      *reinterpret_cast<uint4*>(dst + 32) = make_uint4(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]), pack_hi16(pl[5], pl[4]), pack_hi16(pl[7], pl[6]));
+    };
     auto store_x = [&](char* Xt, int st) {
 #pragma unroll
       for (int i = 0; i < PIT; ++i) {
@@ -574,7 +637,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
               *reinterpret_cast<uint32_t*>(dst + px * PB) = pack_hi16(h1, h0);
               *reinterpret_cast<uint32_t*>(dst + px * PB + 16) = pack_hi16(m1, m0_);
               if constexpr (NP == 3) *reinterpret_cast<uint32_t*>(dst + px * PB + 32) = pack_hi16(l1, l0);
-              if constexpr (FLIP) *reinterpret_cast<uint32_t*>(dst + px * PB + 16 * NP) = pack_hi16(sign_bit(e0 + 4u + (uint32_t)px), sign_bit(e0 + (uint32_t)px));
+              if constexpr (SGN) *reinterpret_cast<uint32_t*>(dst + px * PB + 16 * NP) = pack_hi16((sgv[i][1] << (24 - 8 * px)) & 0x80000000u, (sgv[i][0] << (24 - 8 * px)) & 0x80000000u);
+              else if constexpr (FLIP) *reinterpret_cast<uint32_t*>(dst + px * PB + 16 * NP) = pack_hi16(sign_bit(e0 + 4u + (uint32_t)px), sign_bit(e0 + (uint32_t)px));
             }
           } else if constexpr (XM == 3) {  // 4 pixels x 4 channels: half of each pixel's 16-byte slots
 #pragma unroll
@@ -588,7 +652,10 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
               if constexpr (FLIP) {
                 uint32_t sb[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) sb[c] = sign_bit(e0 + (uint32_t)(c * a.HW + px));
+                for (int c = 0; c < 4; ++c) {
+                  if constexpr (INJ) sb[c] = (sgv[i][c & (XSG - 1)] << (24 - 8 * px)) & 0x80000000u;   // byte px of the channel's dword
+                  else sb[c] = sign_bit(e0 + (uint32_t)(c * a.HW + px));
+                }
                 *reinterpret_cast<uint2*>(dst + px * PB + 16 * NP) = make_uint2(pack_hi16(sb[1], sb[0]), pack_hi16(sb[3], sb[2]));
               }
             }
@@ -602,7 +669,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
             }
           } else {
             const float v[8] = {xv[i][0], xv[i][1], xv[i][2], xv[i][3], xv[i][4], xv[i][5], xv[i][6], xv[i][7]};
-            store_px(dst, v, e0, XM == 1 ? 1u : (uint32_t)a.HW);
+            if constexpr (SGN) store_px_sg(dst, v, sgv[i]);
+            else store_px(dst, v, e0, XM == 1 ? 1u : (uint32_t)a.HW);
           }
         }
       }
@@ -894,7 +962,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       const int HoWo = a.Ho * a.Wo;
       auto outv = [&](int i, int j, int r, uint32_t oi) -> float {   // output-stage value of accumulator register r (before residual / ReLU)
         float v = __fadd_rn(acc[0][i][j][r], bsv[i]);
-        if constexpr (FLIP) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), hash_sign(skey_out, oi)));
+        if constexpr (SGN) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), so_f((uint32_t)so_s[oi], 0)));
+        else if constexpr (FLIP) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), hash_sign(skey_out, oi)));
         return __fadd_rn(__fmul_rn(v, scv[i]), shv[i]);
       };
       // In all three forms below the residual values of a column group are fetched in ONE batch before its first store: written

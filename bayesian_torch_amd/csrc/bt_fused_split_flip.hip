@@ -4,9 +4,16 @@
 
 namespace bt {
 
+// The instantiations that READ the draws and both sign streams (bt_fused_split_flip_inj.hip). A launch that reaches this chain with
+// a.eps_w set carries BT_DRAWS_EPS_PACKED | BT_DRAWS_SIGNS_PACKED (bt_fused_api.hip): flavour and geometry are chosen below exactly as
+// for on-chip draws, and the launch goes to the twin of the kernel they would have taken.
+int launch_split_flip_inj_cfg(const FwdArgs& a, int bm, int xm, hipStream_t stream);
+int launch_quad_flip_inj(const FwdArgs& a, hipStream_t stream);
+
 template <int BM, int NPW, int XM>
 static int launch_split_flip_cfg(const FwdArgs& a, hipStream_t stream) {
   constexpr int BN = 64, NP = 3;
+  if (a.eps_w) return launch_split_flip_inj_cfg(a, BM, XM, stream);
   constexpr int lds = split_lds_bytes<BN, BM, NP, true>();
   static_assert(lds <= 160 * 1024, "LDS budget of one CU");
   char nm[160];
@@ -21,6 +28,7 @@ template <bool POOL>
 static int launch_quad_flip_cfg(const FwdArgs& a, hipStream_t stream) {
   constexpr int lds = quad_lds_bytes<true>();
   static_assert(lds <= 160 * 1024, "LDS budget of one CU");
+  if (a.eps_w) return launch_quad_flip_inj(a, stream);
   return launch_kernel(fused_split_quad_kernel<3, POOL, true>,
                        POOL ? "fused_split_quad_kernel<64,256,bf16x3,2x6 terms,flip,pool=1>" : "fused_split_quad_kernel<64,256,bf16x3,2x6 terms,flip,pool=0>",
                        "fused forward (split, flipout, quad)", dim3((unsigned)a.total_blocks), dim3(512), lds, lds, stream, a);

@@ -36,9 +36,11 @@ constexpr int kWalkBytes = 2 * kWalkRowBytes + 2 * 3 * 64 * 4;  // [2 samples] s
 
 // INJ (Reparameterization, one sample per workgroup; bt_fused_split_inj.hip): the draws are read -- a.eps_w as [S] images in the
 // layout of mu_packed (bt_pack_eps), one 16-byte load per unit issued with its two parameter loads; a.eps_b [S][Co].
+// FLIP && INJ (bt_fused_split_flip_inj.hip): the sign streams are read too, from the byte images of bt_pack_signs (bt_fused_split.h):
+// the three s_in bytes of a patch pixel with its x loads, the four s_out bytes of an output quad as one dword in the join.
 template <int NP, bool POOL, bool FLIP = false, bool WALK = false, bool INJ = false>
 __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) {
-  static_assert(!INJ || (!FLIP && !WALK), "injected draws: Reparameterization, the one-sample path");
+  static_assert(!INJ || !WALK, "injected draws: the one-sample path");
   constexpr int BN = 64, BM = FLIP ? 256 : 512, kProducers = 256, kThreadsAll = 512, STEPS = kSplitSteps, TPS = 4 * STEPS;  // taps per stage
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32, NOP = FLIP ? 2 : 1;
   constexpr int PBQ = 8 * NP;  // bytes per pixel of the quad patch
@@ -148,6 +150,20 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
   auto ldf = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0)); };
   auto ldf4 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0)); };
+  constexpr bool SGN = FLIP && INJ;  // this sample's sign images (per sample also when x is shared)
+  [[maybe_unused]] const auto r_si = [&] {   // (nothing at all in the other instantiations)
+    if constexpr (SGN) {
+      const int si_bytes = (int)((a.x_elems + 15) & ~15ll);
+      return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.sign_in)) + (long long)s * si_bytes, 0, si_bytes, 0x00020000);
+    } else {
+      return 0;
+    }
+  }();
+  [[maybe_unused]] const auto so_s = [&] {
+    if constexpr (SGN) return reinterpret_cast<const unsigned char*>(a.sign_out) + (long long)s * (((long long)a.M * a.Co + 15) & ~15ll);
+    else return 0;
+  }();
+  [[maybe_unused]] auto so_f = [](uint32_t word, int k) -> float { return __uint_as_float(0x3F800000u | ((word << (24 - 8 * k)) & 0x80000000u)); };
 
   float* const bias0 = smem;
   float* const bias1 = smem + BN;  // Flipout: the sigma*eps part of the bias
@@ -248,10 +264,18 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       const float4 d = *reinterpret_cast<const float4*>(p0 + SROWS * SROW);
       const uint32_t oi = obase + (uint32_t)(k * RSTEP * HoWo_);
       const float sc = osc[row], sh = osh[row];
+      if constexpr (INJ) {  // (oi is a multiple of 4: whole rows with Wo % 4 == 0; dead columns and rows past Cog read the image's first dword)
+        const uint32_t sw = *reinterpret_cast<const uint32_t*>(so_s + ((mok && n0 + row < a.Cog) ? oi : 0u));
+        v.x = __fadd_rn(__fmul_rn(__fadd_rn(v.x, __fmul_rn(d.x, so_f(sw, 0))), sc), sh);
+        v.y = __fadd_rn(__fmul_rn(__fadd_rn(v.y, __fmul_rn(d.y, so_f(sw, 1))), sc), sh);
+        v.z = __fadd_rn(__fmul_rn(__fadd_rn(v.z, __fmul_rn(d.z, so_f(sw, 2))), sc), sh);
+        v.w = __fadd_rn(__fmul_rn(__fadd_rn(v.w, __fmul_rn(d.w, so_f(sw, 3))), sc), sh);
+      } else {
       v.x = __fadd_rn(__fmul_rn(__fadd_rn(v.x, __fmul_rn(d.x, hash_sign(skey_out, oi))), sc), sh);
       v.y = __fadd_rn(__fmul_rn(__fadd_rn(v.y, __fmul_rn(d.y, hash_sign(skey_out, oi + 1u))), sc), sh);
       v.z = __fadd_rn(__fmul_rn(__fadd_rn(v.z, __fmul_rn(d.z, hash_sign(skey_out, oi + 2u))), sc), sh);
       v.w = __fadd_rn(__fmul_rn(__fadd_rn(v.w, __fmul_rn(d.w, hash_sign(skey_out, oi + 3u))), sc), sh);
+      }
       *reinterpret_cast<float4*>(p0) = v;
     }
   };
@@ -295,6 +319,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
       float xv[XB][4];
       int pos_[XB];
       uint32_t xoff_[XB];
+      [[maybe_unused]] uint32_t sg[SGN ? XB : 1][3];  // FLIP && INJ: the s_in bytes of channels 0..2, loaded with the pixel
 #pragma unroll
       for (int k = 0; k < XB; ++k) {
         const int pos = tid + kThreadsAll * (i0 + k);
@@ -310,6 +335,11 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
         xoff_[k] = ok ? off : 0u;
 #pragma unroll
         for (int c = 0; c < 4; ++c) xv[k][c] = ldf(r_x, (ok && c < Cig) ? off + (uint32_t)(c * HWb) : kOOB);
+        if constexpr (SGN) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c)
+            sg[k][c] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(r_si, (int)((ok && c < Cig) ? (off >> 2) + (uint32_t)(c * a.HW) : kOOB), 0, 0);
+        }
       }
 #pragma unroll
       for (int k = 0; k < XB; ++k) {
@@ -320,8 +350,10 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
           if constexpr (FLIP) {  // s_in of channels 0..2 (hash of the element's offset in the sample's x) -> bits 16..18: the padding channel's lane
             uint32_t bits = 0;
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-              bits |= (__float_as_uint(hash_sign(skey_in, (xoff_[k] >> 2) + (uint32_t)(c * a.HW))) >> 31) << (16 + c);
+            for (int c = 0; c < 3; ++c) {
+              if constexpr (INJ) bits |= (sg[k][c] >> 7) << (16 + c);
+              else bits |= (__float_as_uint(hash_sign(skey_in, (xoff_[k] >> 2) + (uint32_t)(c * a.HW))) >> 31) << (16 + c);
+            }
             ph[3] = bits;
           }
           char* const dst = xq + pos_[k] * PBQ;

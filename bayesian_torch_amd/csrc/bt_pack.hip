@@ -230,7 +230,48 @@ __global__ __launch_bounds__(256) void pack_eps_kernel(const float* __restrict__
   }
 }
 
+// bt_pack_signs: out[s][i] <- 0x80 where signs[s][i] < 0, else 0x00; a thread writes one dword = four consecutive elements of a sample's
+// image (the image stride is a multiple of 16 bytes; bytes past n hold 0). Elements that are not exactly +1 / -1 -- zeros, NaNs,
+// anything else -- are counted: one vector atomic per wave that met one, on the word the host zeroed in front of this launch.
+__global__ __launch_bounds__(256) void pack_signs_kernel(const float* __restrict__ signs, uint32_t* __restrict__ out, long long n, long long words_per_sample,
+                                                         long long words, unsigned* __restrict__ not_pm1) {
+  unsigned bad = 0;
+  for (long long w = (long long)blockIdx.x * 256 + threadIdx.x; w < words; w += (long long)gridDim.x * 256) {
+    const long long smp = w / words_per_sample, e0 = 4 * (w - smp * words_per_sample);
+    const float* const src = signs + smp * n;
+    uint32_t word = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (e0 + k < n) {
+        const float v = src[e0 + k];
+        word |= (v < 0.f ? 0x80u : 0u) << (8 * k);
+        bad += (v == 1.f || v == -1.f) ? 0u : 1u;
+      }
+    }
+    out[w] = word;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(not_pm1, bad);
+}
+
 }  // namespace bt
+
+extern "C" int bt_pack_signs(const float* signs, int32_t S, int64_t n, uint8_t* signs_packed, uint32_t* not_pm1_count, bt_stream_t stream) {
+  using namespace bt;
+  if (!signs || !signs_packed || !not_pm1_count) return set_error(BT_ERR_BAD_ARG, "bt_pack_signs: null argument");
+  if (S <= 0 || n <= 0) return set_error(BT_ERR_BAD_ARG, "bt_pack_signs: non-positive dimension");
+  if ((((uintptr_t)signs_packed) & 15u) != 0) return set_error(BT_ERR_BAD_ARG, "bt_pack_signs: signs_packed must be 16-byte aligned");
+  if (n >= (1ll << 30)) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_signs: a sample of 2^30 elements or more exceeds the kernels' 32-bit offsets");
+  const long long wps = BT_SIGNS_PACKED_STRIDE(n) / 4, words = (long long)S * wps;
+  if (hipMemsetAsync(not_pm1_count, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
+    return set_error(BT_ERR_HIP_BASE, "bt_pack_signs: hipMemsetAsync failed");
+  long long blocks = (words + 255) / 256;
+  if (blocks > 4096) blocks = 4096;   // (the rest in the kernel's loop)
+  hipLaunchKernelGGL(pack_signs_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, signs, reinterpret_cast<uint32_t*>(signs_packed), (long long)n, wps,
+                     words, not_pm1_count);
+  return check_launch("bt_pack_signs");
+}
 
 extern "C" int bt_pack_eps(const float* eps_w, int32_t S, int64_t Co, int64_t Ci, int64_t taps, float* eps_packed, bt_stream_t stream) {
   using namespace bt;

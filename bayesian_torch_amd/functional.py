@@ -45,10 +45,14 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     post_scale/post_shift [Co], residual ([S*B, ...] like out, or [B, ...] shared), relu: fused output stage
     (v*scale+shift, +residual, max(.,0)).  packed: (mu_packed, sigma_packed) from pack_params() -- selects the fast kernel.
     prior_type: "normal" | "laplace" (kl_div's branch; only matters when want_kl).
-    inject_path: "general" | "split" | None (= rng.get_inject_path()): with "split", an injected Reparameterization draw (eps_w given,
-    packed given) is re-laid by bt_pack_eps and read by the split-precision kernels; a launch they decline (BT_ERR_UNSUPPORTED,
-    nothing launched) runs as under "general".  eps_pack_state: a dict the caller owns (a layer keeps one: the buffer lives and dies
-    with it) holding the packed-draw buffer and the geometries that were declined, so that neither is made again on every call.
+    inject_path: "general" | "split" | None (= rng.get_inject_path()): with "split", a whole injected draw (eps_w, eps_b exactly when
+    biased, for Flipout both sign tensors of the right sizes; packed given) is re-laid by bt_pack_eps (Flipout: + two bt_pack_signs)
+    and read by the split-precision kernels; a launch they decline (BT_ERR_UNSUPPORTED, nothing launched) runs as under "general".
+    Supplied Flipout signs on this path are +1 / -1: an exact 0 is read as +1 and counted (include/bt_hip.h).
+    eps_pack_state: a dict the caller owns (a layer keeps one: the buffers live and die with it) holding the packed-draw buffers
+    ("buf", Flipout: "sign_in_buf" / "sign_out_buf"), the geometries that were declined, so that neither is made again on every
+    call, and for Flipout "sign_count": an int32 device tensor [2] = the sign_in / sign_out elements of the last packed draw that were
+    not exactly +1 or -1 (reading it synchronises; nothing here does).
     Returns (out [S*B, ...], kl or None)."""
     x = _lib.dev_f32(x, "input")
     dev = x.device
@@ -91,10 +95,16 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     L = _lib.lib()
     # layers whose output map is one pixel may run split over K-slices that meet in scratch behind the workspace (include/bt_hip.h)
     gq = geom if conv is not None else _lib.bt_conv2d_geom(B, In, 1, 1, Co, 1, 1, 1, 1, 0, 0, 1, 1, 1)
-    # injected draws on the split-precision kernels: Reparameterization, packed parameters, a whole draw
-    split_inj = ((rng.get_inject_path() if inject_path is None else inject_path) == "split" and tens["eps_w"] is not None and not flip
-                 and packed is not None and tens["sign_in"] is None and tens["sign_out"] is None and tens["eps_w"].numel() == S * tens["mu_w"].numel()
+    # injected draws on the split-precision kernels: packed parameters, a whole draw (Flipout: with both sign tensors)
+    n_so = out.numel() // S if not pool else B * Co * Ho * Wo      # one sample's contraction output, before any fused pooling
+    split_inj = ((rng.get_inject_path() if inject_path is None else inject_path) == "split" and tens["eps_w"] is not None
+                 and packed is not None and tens["eps_w"].numel() == S * tens["mu_w"].numel()
                  and (tens["mu_b"] is None) == (tens["eps_b"] is None))
+    if split_inj and flip:
+        split_inj = (tens["sign_in"] is not None and tens["sign_out"] is not None and tens["sign_in"].numel() == S * x_elems
+                     and tens["sign_out"].numel() == S * n_so)
+    elif split_inj:
+        split_inj = tens["sign_in"] is None and tens["sign_out"] is None
     geo_key = (B, S, bool(shared_x), tuple(x.shape[1:]), None if conv is None else (sh, sw, ph, pw, dh, dw, groups), bool(pool), residual is not None)
     if split_inj and eps_pack_state is not None and geo_key in eps_pack_state.setdefault("declined", set()):
         split_inj = False
@@ -123,8 +133,22 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
                 eps_pack_state["buf"] = eps_pk
         with _lib.on(dev):
             _lib.check(L.bt_pack_eps(tens["eps_w"].data_ptr(), S, Co, Cig, taps, eps_pk.data_ptr(), _lib.stream_ptr(dev)))
-        Rp = _lib.bt_rng(R.seed, R.call_base_dev, R.call, R.layer_id, R.sample0, _lib.DRAWS_EPS_PACKED)
-        D = _lib.bt_draws(eps_pk.data_ptr(), _lib.ptr(tens["eps_b"]), None, None, Rp)
+        sg_pk = [None, None]
+        if flip:      # the two sign tensors as byte images; the pass leaves its count of elements that are not +-1 in the state's counter
+            st = {} if eps_pack_state is None else eps_pack_state
+            cnt = st.get("sign_count")
+            if cnt is None or cnt.device != dev:
+                cnt = st["sign_count"] = torch.zeros(2, dtype=torch.int32, device=dev)
+            for i, (key, n) in enumerate((("sign_in", x_elems), ("sign_out", n_so))):
+                nb = S * _lib.signs_packed_stride(n)
+                buf = st.get(key + "_buf")
+                if buf is None or buf.numel() < nb or buf.device != dev:
+                    buf = st[key + "_buf"] = torch.empty(nb, dtype=torch.uint8, device=dev)
+                with _lib.on(dev):
+                    _lib.check(L.bt_pack_signs(tens[key].data_ptr(), S, n, buf.data_ptr(), cnt.data_ptr() + 4 * i, _lib.stream_ptr(dev)))
+                sg_pk[i] = buf
+        Rp = _lib.bt_rng(R.seed, R.call_base_dev, R.call, R.layer_id, R.sample0, _lib.DRAWS_EPS_PACKED | (_lib.DRAWS_SIGNS_PACKED if flip else 0))
+        D = _lib.bt_draws(eps_pk.data_ptr(), _lib.ptr(tens["eps_b"]), _lib.ptr(sg_pk[0]), _lib.ptr(sg_pk[1]), Rp)
     E = None
     if tens["post_scale"] is not None or tens["residual"] is not None or relu or pool:
         res, rstride = tens["residual"], 0

@@ -66,6 +66,19 @@ typedef struct bt_rng {
  * tensors, under bt_set_contraction(1 | 2) / BT_CONTRACTION=f32 | bf16x2, or when no split flavour takes the launch -- call again
  * with the natural layout then. The fused max-pool is available on this path. */
 #define BT_DRAWS_EPS_PACKED 1u
+/* With BT_DRAWS_EPS_PACKED, on the Flipout entry points: bt_draws.sign_in / sign_out point at the [S] BYTE images written by
+ * bt_pack_signs (one byte per element, 0x00 = +1, 0x80 = -1, BT_SIGNS_PACKED_STRIDE(n) bytes per sample) instead of fp32 tensors,
+ * and the launch is offered to the split-precision Flipout kernels alone, whose injected instantiations read the weight draws, the
+ * bias draws (eps_b [S][Co], exactly when the layer has a bias) and both sign streams where the on-chip ones run Philox and the sign
+ * hash: the draw an on-chip launch made (bt_rng_normal_fill / bt_rng_sign_fill) gives the same output bits. Needs eps_w and both
+ * images, 16-byte aligned, and mu_packed / sigma_packed. CONTRACT FOR THE SIGNS ON THIS PATH: +1 or -1. A byte image has no third
+ * value: an exact 0 (torch's uniform_(-1, 1).sign() yields one with probability 2^-24 per element) is read as +1, and bt_pack_signs
+ * counts it; the natural-layout path keeps multiplying by whatever value it is given. BT_ERR_BAD_ARG without BT_DRAWS_EPS_PACKED or
+ * on a Reparameterization entry point; BT_ERR_UNSUPPORTED (nothing launched) under a forced f32 / bf16x2 contraction or when no
+ * split-precision Flipout flavour takes the geometry -- call again with the natural layouts then. BT_DRAWS_EPS_PACKED alone on a
+ * Flipout entry point stays BT_ERR_UNSUPPORTED. The fused max-pool is available on this path (the Flipout stem kernel). */
+#define BT_DRAWS_SIGNS_PACKED 2u
+#define BT_SIGNS_PACKED_STRIDE(n) ((((int64_t)(n)) + 15) & ~(int64_t)15) /* bytes of one sample's image of n signs */
 
 /* Variational parameters and priors of one layer. weight is [Co][K] row-major
  * (Linear: K = in_features; Conv2d: K = (Ci/groups)*kh*kw, i.e. the native
@@ -199,6 +212,16 @@ int bt_pack_params(const float *mu_w, const float *rho_w, int64_t Co, int64_t Ci
  * eps_packed [S][(co*taps + tap)*Ci4 + ci] -- per sample the layout of mu_packed, padding channels 0.0 -- for
  * BT_DRAWS_EPS_PACKED launches. S * Co * taps * Ci4 floats. Stream-ordered, no host synchronisation, graph-capturable. */
 int bt_pack_eps(const float *eps_w, int32_t S, int64_t Co, int64_t Ci, int64_t taps, float *eps_packed, bt_stream_t stream);
+
+/* Packs S Flipout sign tensors, signs [S][n] fp32 (sign_in: n = elements of one sample's x; sign_out: n = elements of one sample's
+ * contraction output, before any fused pooling), into signs_packed [S][BT_SIGNS_PACKED_STRIDE(n)] bytes for BT_DRAWS_SIGNS_PACKED
+ * launches: byte i of a sample's image is 0x80 when element i is negative, else 0x00, in the tensor's own element order (byte << 24
+ * is the fp32 sign mask, byte << 8 the bf16 one); the stride is n rounded up to 16 and the padding bytes are 0, so a kernel that
+ * fetches four consecutive elements as one float4 fetches their signs as one aligned dword at the same element index. signs_packed
+ * must be 16-byte aligned. *not_pm1_count (DEVICE word) <- the number of elements of THIS call that are not exactly +1 or -1 (an
+ * exact 0 or a NaN is packed as +1, any other value by its sign): set, not accumulated. Stream-ordered (a memset node and one
+ * launch), no host synchronisation, graph-capturable. */
+int bt_pack_signs(const float *signs, int32_t S, int64_t n, uint8_t *signs_packed, uint32_t *not_pm1_count, bt_stream_t stream);
 
 /* Keeps the packed copies of up to BT_PACK_MAX_SEGMENTS layers in step with their parameters, checked ON THE DEVICE in the
  * stream (two launches, no host synchronisation, graph-capturable): a 64-bit fingerprint of every layer's natural-layout

@@ -8,7 +8,10 @@ first run, materialised).  On the GPU box:
                                                   either path; torch's generator alone -> OUT/inject_split_model.json (--out OUT; default: the temporary directory)
     rocprofv3 --kernel-trace --stats --output-format csv -d out/trace -o inj -- python tools/perf_inject_split.py --trace
                                                   six on-chip forwards, then six replays on the path "split", in one trace: the inj
-                                                  instantiations beside their on-chip twins in inj_kernel_stats.csv"""
+                                                  instantiations beside their on-chip twins in inj_kernel_stats.csv
+    --flipout (with either form)                  the Flipout model: the draw holds both sign tensors, the path "split" packs them with
+                                                  bt_pack_signs and launches the flip,...,inj kernels; the "pack only" column is
+                                                  bt_pack_eps + the two bt_pack_signs per layer -> OUT/inject_split_flipout_model.json"""
 import json
 import os
 import sys
@@ -23,12 +26,13 @@ from bayesian_torch_amd.mc import mc_forward
 from bayesian_torch_amd.models.dnn_to_bnn import dnn_to_bnn
 PRIOR = {"prior_mu": 0.0, "prior_sigma": 1.0, "posterior_mu_init": 0.0, "posterior_rho_init": -3.0, "moped_enable": False, "moped_delta": 0.5, "type": "Reparameterization"}
 S, B = 8, 128
+FLIP = "--flipout" in sys.argv[1:]
 
 
 def model():
     torch.manual_seed(1)
     net = H.resnet18(10, 64)
-    dnn_to_bnn(net, dict(PRIOR))
+    dnn_to_bnn(net, dict(PRIOR, type="Flipout" if FLIP else "Reparameterization"))
     H.fill_bayes_params(net, 1)
     net = net.cuda().eval()
     x = torch.randn(B, 3, 32, 32, generator=torch.Generator().manual_seed(2)).cuda()
@@ -89,7 +93,14 @@ def measure():
             Co, Ci = w.shape[1], w.shape[2]
             T = w[0, 0, 0].numel()
             buf = m._eps_pack.get("buf")
+            if buf is None:      # (a layer whose launch was declined packs nothing)
+                continue
             L.bt_pack_eps(w.data_ptr(), S, Co, Ci, T, buf.data_ptr(), _lib.stream_ptr(w.device))
+            if FLIP:
+                cnt = m._eps_pack["sign_count"]
+                for i, key in enumerate(("sign_in", "sign_out")):
+                    t = d[key]
+                    L.bt_pack_signs(t.data_ptr(), S, t.numel() // S, m._eps_pack[key + "_buf"].data_ptr(), cnt.data_ptr() + 4 * i, _lib.stream_ptr(t.device))
 
 
     def torch_draws_only():
@@ -98,6 +109,9 @@ def measure():
             torch.empty((S,) + tuple(w.shape), device=w.device).normal_()
             if m.mu_bias is not None:
                 torch.empty((S, w.shape[0]), device=w.device).normal_()
+            if FLIP:
+                for shp in (m._last["x_shape"], m._last["out_shape"]):
+                    torch.empty((S,) + tuple(shp), device=w.device).uniform_(-1, 1).sign_()
 
 
     # correctness at the timed size
@@ -106,6 +120,9 @@ def measure():
     out_s, _ = mc_forward(net, x, S)
     res["split_kernels"] = [m._last["kernel"] for m in layers]
     res["split_equals_onchip_bits"] = bool(torch.equal(out_s, ref))
+    res["split_max_abs_diff_vs_onchip"] = float((out_s - ref).abs().max())
+    if FLIP:
+        res["sign_counts"] = [[int(v) for v in m._eps_pack["sign_count"].cpu()] if "sign_count" in m._eps_pack else None for m in layers]
     rng.set_inject_path("general")
     out_g, _ = mc_forward(net, x, S)
     res["general_kernels"] = [m._last["kernel"] for m in layers]
@@ -131,8 +148,9 @@ def measure():
     argv = sys.argv[1:]
     out_dir = argv[argv.index("--out") + 1] if "--out" in argv else tempfile.gettempdir()
     os.makedirs(out_dir, exist_ok=True)
-    json.dump(res, open(os.path.join(out_dir, "inject_split_model.json"), "w"), indent=1)
-    print("bits equal:", res["split_equals_onchip_bits"], "->", os.path.join(out_dir, "inject_split_model.json"))
+    name = "inject_split_flipout_model.json" if FLIP else "inject_split_model.json"
+    json.dump(res, open(os.path.join(out_dir, name), "w"), indent=1)
+    print("bits equal:", res["split_equals_onchip_bits"], "->", os.path.join(out_dir, name))
 
 
 if __name__ == "__main__":
