@@ -10,3 +10,6 @@ Everything numeric runs in libbtorch_hip.so (hand-written HIP, include/bt_hip.h)
 package does not load it -- the first kernel call does, and fails loudly if it is missing.
 """
 __version__ = "0.1.0"
+
+from . import precision  # noqa: E402,F401  (contraction arithmetic of the fused forwards: precision.contraction("bf16"))
+from .precision import contraction, get_contraction, set_contraction  # noqa: E402,F401

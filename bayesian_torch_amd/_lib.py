@@ -73,6 +73,7 @@ _PROTOS = {
     "bt_last_launch_info": (C.c_int, [C.POINTER(C.c_int64), C.c_int32]),
     "bt_fused_scratch_bytes": (C.c_size_t, [C.POINTER(bt_conv2d_geom), C.c_int32]),
     "bt_set_contraction": (C.c_int, [C.c_int]),
+    "bt_get_contraction": (C.c_int, []),
     "bt_conv2d_bwd_workspace": (C.c_size_t, [C.POINTER(bt_conv2d_geom), C.c_int32]),
     "bt_conv2d_bwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, C.c_int32, _vp, C.c_int64, _vp, C.POINTER(bt_params), C.POINTER(bt_draws),
                                 _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

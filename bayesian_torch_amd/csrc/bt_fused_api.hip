@@ -60,7 +60,7 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
     if (!p->mu_packed || !p->sigma_packed) return bad("BT_DRAWS_EPS_PACKED needs mu_packed / sigma_packed");
     if (!al16(d->eps_w)) return bad("BT_DRAWS_EPS_PACKED: eps_w must be 16-byte aligned");
     if (signs_packed && (!al16(d->sign_in) || !al16(d->sign_out))) return bad("BT_DRAWS_SIGNS_PACKED: sign_in / sign_out must be 16-byte aligned");
-    if (contraction_mode() != 0) return unsupported("the contraction is forced to f32 / bf16x2 (bt_set_contraction, BT_CONTRACTION): only the exact split reads packed draws");
+    if (contraction_mode() != 0) return unsupported("the contraction is forced to f32 / bf16x2 / bf16 (bt_set_contraction, BT_CONTRACTION): only the exact split reads packed draws");
   }
 
   const int Ho = (g.H + 2 * g.ph - g.dh * (g.kh - 1) - 1) / g.sh + 1;

@@ -45,8 +45,15 @@ constexpr int split_w_bytes() { return (FLIP ? 2 : 1) * kSplitSteps * 2 * NP * B
 template <int BM, int NP, bool FLIP = false>
 constexpr int split_x_bytes() { return split_xpo<BM, FLIP>() * (NP + (FLIP ? 1 : 0)) * 16; }
 constexpr int kSplitMiscBytes = kMaxTaps * 16 + 96 + 32 + 64;
+// The room behind the operand buffers' start that the output staging may use. NP = 1 (the bf16 mode): one piece per value shrinks the
+// operand buffers below what a 32-channel staging pass of the widest tiles needs, so the request is the larger of the two.
 template <int BN, int BM, int NP, bool FLIP = false>
-constexpr int split_lds_bytes() { return 2 * (split_w_bytes<BN, NP, FLIP>() + split_x_bytes<BM, NP, FLIP>()) + kSplitMiscBytes; }
+constexpr int split_stage_cap() {
+  constexpr int ops = 2 * (split_w_bytes<BN, NP, FLIP>() + split_x_bytes<BM, NP, FLIP>()), pass32 = (4 * BN + 32 * (BM + 4)) * 4;
+  return (NP == 1 && pass32 > ops) ? pass32 : ops;
+}
+template <int BN, int BM, int NP, bool FLIP = false>
+constexpr int split_lds_bytes() { return split_stage_cap<BN, BM, NP, FLIP>() + kSplitMiscBytes; }
 
 // fp32 -> bf16 pieces by truncation, as fp32 bit patterns whose upper halves are the pieces
 __device__ __forceinline__ void split_pieces(float v, uint32_t& h, uint32_t& m, uint32_t& l) {
@@ -73,6 +80,13 @@ __device__ __forceinline__ void split_pair(float a, float b, uint32_t& h, uint32
   h = pack_hi16(hb.y, hb.x), m = pack_hi16(mb.y, mb.x), l = pack_hi16(lb.y, lb.x);
 }
 
+// The bf16 mode's one piece: two fp32 values rounded to nearest even, packed (hi in the upper half) -- v_cvt_pk_bf16_f32
+__device__ __forceinline__ uint32_t rne_pair(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
 // n / d with the host's reciprocal (bt_fused_split_host.h: inv == 0 -> divide; d == 1 needs none)
 __device__ __forceinline__ int udiv_inv(int n, int d, uint32_t inv) {
   return inv ? (int)__umulhi((uint32_t)n, inv) : (d == 1 ? n : n / d);
@@ -81,7 +95,9 @@ __device__ __forceinline__ int udiv_inv(int n, int d, uint32_t inv) {
 __device__ __forceinline__ uint32_t inv32(int d) { return 0xFFFFFFFFu / (uint32_t)d + 1u; }
 __device__ __forceinline__ int div_small(int n, int d) { return d == 1 ? n : d == 2 ? n >> 1 : n / d; }  // n >= 0; strides are 1 or 2 in practice
 
-// NP: pieces per value (3: exact split, 6 product terms; 2: 3 terms). 4 consumer waves (64 x BM/4 each) + NPW producer waves
+// NP: pieces per value (3: exact split, 6 product terms; 2: 3 terms; 1: the bf16 mode -- every operand value rounded ONCE to nearest
+// even (rne_pair, not the truncation of split_pieces: one truncated piece is biased toward zero), one product term; same K order, tile
+// plan, draws and output stage, bt_fused_split_bf16.hip). 4 consumer waves (64 x BM/4 each) + NPW producer waves
 // (8 on the 128-wide tile of the small feature maps, where one draw serves few columns and the accumulators are small).
 // XM: how the x patch is fetched. A producer thread owns ITEMS f = ptid + kProducers i of the stage's NO octet planes (the same
 // ones in every stage, so their addresses are decoded once) and issues all their loads one stage ahead.
@@ -116,6 +132,7 @@ template <int BN, int BM, int NP, int NPW, int XM, bool FLIP = false, bool INJ =
 __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdArgs a) {
   static_assert((BN == 64 && (BM == 512 || BM == 256 || BM == 128)) || (BN == 32 && BM == 128 && !FLIP), "tile shapes of this flavour");
   static_assert(!FLIP || ((BM == 256 || BM == 128) && NP == 3), "Flipout: the 64 x 256 / 64 x 128 tiles, exact split");
+  static_assert(NP >= 1 && NP <= 3 && (NP != 1 || !INJ), "pieces per value; the bf16 mode draws on chip");
   constexpr int kProducers = 64 * NPW, kThreadsAll = 256 + kProducers;
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32;
   constexpr int NOP = FLIP ? 2 : 1;            // weight operands (images per stage) = accumulator sets
@@ -123,14 +140,15 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   constexpr int W_BYTES = split_w_bytes<BN, NP, FLIP>(), W_OP = W_BYTES / NOP, X_BYTES = split_x_bytes<BM, NP, FLIP>(), XPO = split_xpo<BM, FLIP>();
   constexpr int W_STEP = 2 * NP * BN * 16, W_HALF = NP * BN * 16, W_PIECE = BN * 16;
   // output staging: all BN channels in one pass when the operand buffers are large enough, else 32 at a time
-  constexpr int SROWS = ((4 * BN + NOP * BN * (BM + 4)) * 4 <= 2 * (W_BYTES + X_BYTES)) ? BN : 32, NPASS = BN / SROWS;
+  constexpr int STAGE_CAP = split_stage_cap<BN, BM, NP, FLIP>();  // (NP > 1: the operand buffers, 2 * (W_BYTES + X_BYTES))
+  constexpr int SROWS = ((4 * BN + NOP * BN * (BM + 4)) * 4 <= STAGE_CAP) ? BN : 32, NPASS = BN / SROWS;
   static_assert(!FLIP || NPASS == 1, "Flipout stages both accumulator sets in one pass");
 
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   char* const wbuf = smem_c;                  // [2][W_BYTES]
   char* const xbuf = smem_c + 2 * W_BYTES;    // [2][X_BYTES]
   float* const smem = reinterpret_cast<float*>(smem_c);
-  int4* const taptab = reinterpret_cast<int4*>(smem_c + 2 * (W_BYTES + X_BYTES));
+  int4* const taptab = reinterpret_cast<int4*>(smem_c + STAGE_CAP);
 
   unsigned long long* const dbg_ = kStamps ? a.dbg : nullptr;  // stage stamps: diagnostic build only (make STAMPS=1)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -595,6 +613,10 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       return __float_as_uint(hash_sign(skey_in, idx)) & 0x80000000u;
     };
     auto store_px = [&](char* dst, const float (&v)[8], uint32_t idx0, uint32_t cstride) {  // 8 channels of one pixel -> NP pieces x 16 bytes
+      if constexpr (NP == 1) {
+        *reinterpret_cast<uint4*>(dst) = make_uint4(rne_pair(v[0], v[1]), rne_pair(v[2], v[3]), rne_pair(v[4], v[5]), rne_pair(v[6], v[7]));
+        return;
+      }
       uint32_t ph[8], pm[8], pl[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c) split_pieces(v[c], ph[c], pm[c], pl[c]);
@@ -605,7 +627,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         *reinterpret_cast<uint4*>(dst + 16 * NP) = make_uint4(pack_hi16(sb[1], sb[0]), pack_hi16(sb[3], sb[2]), pack_hi16(sb[5], sb[4]), pack_hi16(sb[7], sb[6]));
       }
       *reinterpret_cast<uint4*>(dst) = make_uint4(pack_hi16(ph[1], ph[0]), pack_hi16(ph[3], ph[2]), pack_hi16(ph[5], ph[4]), pack_hi16(ph[7], ph[6]));
-      *reinterpret_cast<uint4*>(dst + 16) = make_uint4(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]), pack_hi16(pm[5], pm[4]), pack_hi16(pm[7], pm[6]));
+      if constexpr (NP >= 2)
+        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]), pack_hi16(pm[5], pm[4]), pack_hi16(pm[7], pm[6]));
       if constexpr (NP == 3)
         *reinterpret_cast<uint4*>(dst + 32) = make_uint4(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]), pack_hi16(pl[5], pl[4]), pack_hi16(pl[7], pl[6]));
     };
@@ -631,11 +654,15 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           if constexpr (XM == 2) {  // 2 channels x the plane's 4 pixels: one dword of each pixel's 16-byte slots
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
+              if constexpr (NP == 1) {
+                *reinterpret_cast<uint32_t*>(dst + px * PB) = rne_pair(xv[i][px], xv[i][4 + px]);
+                continue;
+              }
               uint32_t h0, m0_, l0, h1, m1, l1;
               split_pieces(xv[i][px], h0, m0_, l0);
               split_pieces(xv[i][4 + px], h1, m1, l1);
               *reinterpret_cast<uint32_t*>(dst + px * PB) = pack_hi16(h1, h0);
-              *reinterpret_cast<uint32_t*>(dst + px * PB + 16) = pack_hi16(m1, m0_);
+              if constexpr (NP >= 2) *reinterpret_cast<uint32_t*>(dst + px * PB + 16) = pack_hi16(m1, m0_);
               if constexpr (NP == 3) *reinterpret_cast<uint32_t*>(dst + px * PB + 32) = pack_hi16(l1, l0);
               if constexpr (SGN) *reinterpret_cast<uint32_t*>(dst + px * PB + 16 * NP) = pack_hi16((sgv[i][1] << (24 - 8 * px)) & 0x80000000u, (sgv[i][0] << (24 - 8 * px)) & 0x80000000u);
               else if constexpr (FLIP) *reinterpret_cast<uint32_t*>(dst + px * PB + 16 * NP) = pack_hi16(sign_bit(e0 + 4u + (uint32_t)px), sign_bit(e0 + (uint32_t)px));
@@ -643,11 +670,15 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           } else if constexpr (XM == 3) {  // 4 pixels x 4 channels: half of each pixel's 16-byte slots
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
+              if constexpr (NP == 1) {
+                *reinterpret_cast<uint2*>(dst + px * PB) = make_uint2(rne_pair(xv[i][px], xv[i][4 + px]), rne_pair(xv[i][8 + px], xv[i][12 + px]));
+                continue;
+              }
               uint32_t ph[4], pm[4], pl[4];
 #pragma unroll
               for (int c = 0; c < 4; ++c) split_pieces(xv[i][4 * c + px], ph[c], pm[c], pl[c]);
               *reinterpret_cast<uint2*>(dst + px * PB) = make_uint2(pack_hi16(ph[1], ph[0]), pack_hi16(ph[3], ph[2]));
-              *reinterpret_cast<uint2*>(dst + px * PB + 16) = make_uint2(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]));
+              if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + px * PB + 16) = make_uint2(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]));
               if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + px * PB + 32) = make_uint2(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]));
               if constexpr (FLIP) {
                 uint32_t sb[4];
@@ -700,6 +731,13 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         for (int i = 0; i < UMAX; ++i) {
           if (u_live[i]) {  // wave-uniform
             const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
+            if constexpr (NP == 1) {  // the sampled weight in fp32 as everywhere (same operations, same order), then rounded once
+              float w4[4];
+#pragma unroll
+              for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j]));
+              if (l_off[i] >= 0) *reinterpret_cast<uint2*>(Wt + l_off[i]) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
+              continue;
+            }
             uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)  // masked units loaded zeros: w = 0 + 0 * eps = 0.  Flipout: the mean alone
@@ -707,7 +745,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
             if (l_off[i] >= 0) {
               char* const dst = Wt + l_off[i];
               *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
-              *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+              if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
               if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
             }
             if constexpr (FLIP) {  // second image: the perturbation sigma * eps
@@ -875,8 +913,10 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
                 for (int i = 0; i < TN; ++i) {
                   // D[pixel][channel]: x is the A operand, W the B operand; terms in decreasing weight
                   acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
-                  acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
-                  acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                  if constexpr (NP >= 2) {
+                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
+                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                  }
                   if constexpr (NP == 3) {
                     acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][2], acc[o][i][j], 0, 0, 0);
                     acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
@@ -903,7 +943,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     // ---- output stage + store (bt_fused_fast.h: lane = one channel, registers 4q..4q+3 = 4 consecutive positions) ----
     if (a.out_vec4 || stage_cols) {
       constexpr int SROW = BM + 4;
-      static_assert((4 * BN + NOP * SROWS * SROW) * 4 <= 2 * (W_BYTES + X_BYTES), "output staging fits the operand buffers");
+      static_assert((4 * BN + NOP * SROWS * SROW) * 4 <= STAGE_CAP, "output staging fits the operand buffers");
       float* const stage = smem + 4 * BN;
       float bsv[TN], scv[TN], shv[TN], b1v[TN];
 #pragma unroll

@@ -18,13 +18,20 @@ int launch_quad_inj(const FwdArgs& a, hipStream_t stream);
 int launch_direct_inj(const FwdArgs& a, bool resident, hipStream_t stream);
 int launch_skinny_inj(const FwdArgs& a, int ks, hipStream_t stream);
 
-// 0: automatic (6-term exact split where the launch is eligible), 1: fp32 MFMA only, 2: 3-term split (opt-in, ~1e-5 relative)
+// The bf16 mode's instantiations (bt_fused_split_bf16.hip): Reparameterization with on-chip draws. The flavour functions choose
+// flavour and geometry exactly as in the automatic mode -- a launch's plan does not depend on the mode -- and hand the launch to these.
+int launch_split_bf16_cfg(const FwdArgs& a, int bm, int xm, hipStream_t stream);
+int launch_quad_bf16(const FwdArgs& a, hipStream_t stream);
+int launch_direct_bf16(const FwdArgs& a, bool resident, hipStream_t stream);
+
+// 0: automatic (6-term exact split where the launch is eligible), 1: fp32 MFMA only, 2: 3-term split (opt-in, ~1e-5 relative),
+// 3: bf16 (opt-in: operands rounded once to bf16, 1 term, where mode 0 runs the general split, stem or direct kernel; else as mode 0)
 static std::atomic<int> g_contraction{-1};
 int contraction_mode() {
   int m = g_contraction.load(std::memory_order_relaxed);
   if (m < 0) {
     const char* e = getenv("BT_CONTRACTION");
-    m = !e ? 0 : (!strcmp(e, "f32") ? 1 : !strcmp(e, "bf16x2") ? 2 : 0);
+    m = !e ? 0 : (!strcmp(e, "f32") ? 1 : !strcmp(e, "bf16x2") ? 2 : !strcmp(e, "bf16") ? 3 : 0);
     g_contraction.store(m, std::memory_order_relaxed);
   }
   return m;
@@ -78,8 +85,9 @@ static int launch_quad_cfg(const FwdArgs& a, hipStream_t stream) {
 // an input that every sample shares: the patch is staged once for a run of samples. The largest of 8 / 4 / 2 that still gives a
 // workgroup to every CU (at least kKlSlices workgroups: the fused KL sweep keeps its slices, so its sum is the one-sample path's).
 // BT_QUAD_SPW (measurement knob, read at every launch) caps it: 1 = the one-sample path.
-static int quad_spw(const FwdArgs& a, long long tiles) {
+static int quad_spw(const FwdArgs& a, long long tiles, int mode) {
   if (a.eps_w) return 0;   // injected draws: the one-sample path (bit-identical to the walk)
+  if (mode == 3) return 0;   // the bf16 mode: the walk is not instantiated (the one-sample path computes the same function)
   if (!a.ep_pool || a.x_sample_stride != 0 || a.S < 2 || a.Ho != 16 || a.Wo != 16 || a.t_NI != 2 || a.ep_Hp != 8 || a.ep_Wp != 8) return 0;
   int nd[2] = {};
   tap_window(a.KH, a.DH, a.SH, a.PH, a.H, a.Ho, false, &nd[0], &nd[1]);
@@ -101,15 +109,16 @@ static int quad_spw(const FwdArgs& a, long long tiles) {
 
 // The flavour functions below work on their own copy of the arguments and, when they launch, hand the plan that ran to `ran`.
 // Each returns BT_OK when the launch was taken, 1 when the flavour does not apply, < 0 on error.
-static int launch_quad(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
+static int launch_quad(FwdArgs a, FwdArgs& ran, int mode, hipStream_t stream) {
   if (!quad_geometry(a, 512, kQuadXBytes / 24)) return 1;
   const long long tiles = (long long)a.G * a.n_tiles * a.m_tiles;
-  const int spw = quad_spw(a, tiles);
+  const int spw = quad_spw(a, tiles, mode);
   a.spw = spw ? spw : 1, a.n_sg = (a.S + a.spw - 1) / a.spw;
   if (!set_grid(a, tiles * a.n_sg)) return 1;
   split_fill_inverses(a);
   ran = a;
   if (a.eps_w) return launch_quad_inj(a, stream);
+  if (mode == 3) return launch_quad_bf16(a, stream);
   if (spw) return launch_quad_cfg<true, true>(a, stream);
   return a.ep_pool ? launch_quad_cfg<true>(a, stream) : launch_quad_cfg<false>(a, stream);
 }
@@ -119,7 +128,7 @@ static int launch_quad(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
 // general kernel's, so a layer's results do not depend on which of the two serves it.
 static std::atomic<int> g_bn32{-2};   // -2: read BT_BN32 once; -1 automatic; 0 / 1 forced (bt_debug_force_bn32)
 static std::atomic<int> g_direct_off{0};
-static int launch_direct(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
+static int launch_direct(FwdArgs a, FwdArgs& ran, int mode, hipStream_t stream) {
   if (g_direct_off.load(std::memory_order_relaxed)) return 1;
   if (a.ep_pool) return 1;
   // a 1x1 kernel without padding (any stride), or any window over a 1x1 image whose ONE live tap sits on the pixel (ResNet18 / CIFAR
@@ -167,6 +176,7 @@ static int launch_direct(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   a.inv_rw = inv_u32(a.HoWo, (long long)a.M + 64 * 8 * 2);   // pixel index -> (image, output position)
   a.inv_wt = inv_u32(a.Wo, a.HoWo);                          // output position -> (row, column): strided layers
   ran = a;
+  if (mode == 3 && !a.eps_w) return launch_direct_bf16(a, resident, stream);
   // (the LDS limit is raised to the largest launch of each variant: K = 256 resident, any K streamed)
   auto launch = [&](auto kern, const char* nm, int max_lds) {
     return launch_kernel(kern, nm, "fused forward (split, direct)", dim3((unsigned)a.total_blocks), dim3(kDirectThreads), direct_lds_bytes(a.Cig),
@@ -247,14 +257,15 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   // Reparameterization, on-chip draws or PACKED injected ones, packed parameters, 32-bit byte offsets
   if (!packed_ok(a)) return 1;
   const bool inj = a.eps_w != nullptr;
-  if (inj && mode == 2) return 1;   // (the opt-in 3-term form has no injected instantiation)
-  if (a.Cig <= 4) return launch_quad(a, ran, stream);   // the stems
+  if (inj && mode >= 2) return 1;   // (the opt-in forms have no injected instantiation)
+  if (a.Cig <= 4) return launch_quad(a, ran, mode, stream);   // the stems
   // whole channel octets, at most 9 taps, no fused pooling
   if ((a.Cig & 7) || a.ep_pool) return 1;
   if (mode != 2) {   // (the flavours with a single live tap per slice / layer take any window size)
-    const int rck = launch_skinny(a, ran, stream);
+    // (the bf16 mode has no split-K instantiation: the direct / general kernels serve those launches)
+    const int rck = mode == 3 ? 1 : launch_skinny(a, ran, stream);
     if (rck <= 0) return rck;
-    const int rcd = launch_direct(a, ran, stream);
+    const int rcd = launch_direct(a, ran, mode, stream);
     if (rcd <= 0) return rcd;
   }
   if (a.T > 9) return 1;
@@ -308,6 +319,7 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   split_fill_inverses(a);
   ran = a;
   if (inj) return launch_split_inj_cfg(a, bm, xm, stream);
+  if (mode == 3) return launch_split_bf16_cfg(a, bm, xm, stream);
   if (bm == 512) return launch_split_xm<512, 4>(a, mode, xm, stream);
   if (bm == 256) return launch_split_xm<256, 8>(a, mode, xm, stream);
   return launch_split_xm<128, 8>(a, mode, xm, stream);
@@ -341,11 +353,14 @@ extern "C" void bt_debug_disable_direct(int off) { bt::g_direct_off.store(off ? 
 extern "C" void bt_debug_force_bn32(int v) { bt::g_bn32.store(v < 0 ? -1 : (v ? 1 : 0), std::memory_order_relaxed); }
 extern "C" void bt_debug_disable_skinny(int off) { bt::g_skinny_off.store(off ? 1 : 0, std::memory_order_relaxed); }
 
-// Contraction arithmetic of the fused forwards (process-wide knob; also env BT_CONTRACTION = f32 | bf16x3 | bf16x2):
-// 0 automatic -- exact bf16x3 split (6 product terms, fp32 accumulate) on the bf16 matrix pipe wherever the launch is eligible,
-// 1 fp32 MFMA everywhere (the bit-exact fp32 FMA chain), 2 bf16x2 split (3 terms; relative error ~1e-5, opt-in).
+// Contraction arithmetic of the fused forwards (process-wide knob, read at every launch; also env BT_CONTRACTION = f32 | bf16x3 |
+// bf16x2 | bf16): 0 automatic -- exact bf16x3 split (6 product terms, fp32 accumulate) on the bf16 matrix pipe wherever the launch is
+// eligible, 1 fp32 MFMA everywhere (the bit-exact fp32 FMA chain), 2 bf16x2 split (3 terms; relative error ~1e-5, opt-in), 3 bf16
+// (opt-in, inference: operands rounded once to bf16, 1 term, on the Reparameterization launches that mode 0 gives to the general
+// split, stem or direct kernel -- same plan; every other launch as in mode 0).
 extern "C" int bt_set_contraction(int mode) {
-  if (mode < 0 || mode > 2) return bt::set_error(BT_ERR_BAD_ARG, "bt_set_contraction: mode must be 0 (auto), 1 (f32) or 2 (bf16x2)");
+  if (mode < 0 || mode > 3) return bt::set_error(BT_ERR_BAD_ARG, "bt_set_contraction: mode must be 0 (auto), 1 (f32), 2 (bf16x2) or 3 (bf16)");
   bt::g_contraction.store(mode, std::memory_order_relaxed);
   return BT_OK;
 }
+extern "C" int bt_get_contraction(void) { return bt::contraction_mode(); }

@@ -32,13 +32,16 @@ constexpr int kDirectMaxK = 256;
 constexpr int kDirectThreads = 512;
 constexpr int kDirectWStep = 2 * 3 * 64 * 16;  // bytes of one K16 step of the weight image: [lane half][piece][row][8 ch] bf16
 constexpr int kDirectChunk = 8;                // K16 steps per streamed weight chunk
-inline int direct_lds_bytes(int Cig) { return (Cig <= kDirectMaxK ? (Cig >> 4) : 2 * kDirectChunk) * kDirectWStep + 64 * 16 + 64; }
+inline int direct_lds_bytes(int Cig, int np = 3) { return (Cig <= kDirectMaxK ? (Cig >> 4) : 2 * kDirectChunk) * (kDirectWStep / 3 * np) + 64 * 16 + 64; }
 
 // INJ (bt_fused_split_inj.hip): the draws are read -- a.eps_w as [S] images in the layout of mu_packed (bt_pack_eps), one 16-byte
 // load per unit issued with its two parameter loads; a.eps_b [S][Co].
-template <bool RESIDENT, bool INJ = false>
+// NP = 1 (bt_fused_split_bf16.hip): the bf16 mode of bt_fused_split.h -- the weight image holds one piece per value (a third of the
+// bytes), x is rounded to nearest even in registers, one MFMA per (channel half, pixel half) and K16 step. Same walk, same plan.
+template <bool RESIDENT, bool INJ = false, int NP = 3>
 __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(const FwdArgs a) {
-  constexpr int BN = 64, NP = 3, W_STEP = kDirectWStep, W_HALF = NP * BN * 16, W_PIECE = BN * 16;
+  static_assert(NP == 3 || (NP == 1 && !INJ), "the exact split, or the bf16 mode with on-chip draws");
+  constexpr int BN = 64, W_STEP = kDirectWStep / 3 * NP, W_HALF = NP * BN * 16, W_PIECE = BN * 16;
   constexpr int TN = 2, TM = 2;  // a wave: 64 channels x 64 pixels
   extern __shared__ __attribute__((aligned(16))) char smem_c[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
@@ -103,6 +106,13 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
     if constexpr (INJ) load_ep(sb, ep);
     else philox_normal4(key_w, sample, eo >> 2, ep);
     const float m4[4] = {mu.x, mu.y, mu.z, mu.w}, s4[4] = {rs.x, rs.y, rs.z, rs.w};
+    if constexpr (NP == 1) {  // the fp32 sampled weight, rounded once
+      float w4[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[j]));
+      if (in) *reinterpret_cast<uint2*>(dst) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
+      return;
+    }
     uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) split_pieces(__fadd_rn(m4[j], __fmul_rn(s4[j], ep[j])), wh[j], wm_[j], wl[j]);
@@ -141,6 +151,13 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
     if constexpr (INJ) ep[0] = t.ep[0], ep[1] = t.ep[1], ep[2] = t.ep[2], ep[3] = t.ep[3];
     else philox_normal4(key_w, sample, t.eo >> 2, ep);
     const float m4[4] = {t.mu.x, t.mu.y, t.mu.z, t.mu.w}, s4[4] = {t.rs.x, t.rs.y, t.rs.z, t.rs.w};
+    if constexpr (NP == 1) {
+      float w4[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[j]));
+      *reinterpret_cast<uint2*>(dst_img + t.lds) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
+      return;
+    }
     uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) split_pieces(__fadd_rn(m4[j], __fmul_rn(s4[j], ep[j])), wh[j], wm_[j], wl[j]);
@@ -248,6 +265,13 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
         for (int p = 0; p < NP; ++p) wf[i][p] = *reinterpret_cast<const bf16x8*>(wp + p * W_PIECE + i * 32 * 16);
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
+        if constexpr (NP == 1) {
+          const uint4 r4 = make_uint4(rne_pair(xr[u][j][0], xr[u][j][1]), rne_pair(xr[u][j][2], xr[u][j][3]), rne_pair(xr[u][j][4], xr[u][j][5]), rne_pair(xr[u][j][6], xr[u][j][7]));
+          const bf16x8 xb = __builtin_bit_cast(bf16x8, r4);
+#pragma unroll
+          for (int i = 0; i < TN; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][0], xb, acc[i][j], 0, 0, 0);
+          continue;
+        }
         uint32_t hq[4], mq[4], lq[4];
         if constexpr (RESIDENT) {
           uint32_t ph[8], pm[8], pl[8];
@@ -266,11 +290,13 @@ __global__ __launch_bounds__(kDirectThreads) void fused_split_direct_kernel(cons
         for (int i = 0; i < TN; ++i) {
           // D[channel][pixel]: the weights are the A operand, the pixels the B operand; the six terms in the general kernel's order
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][0], x0, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][1], x0, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][0], x1, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][2], x0, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][1], x1, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][0], x2, acc[i][j], 0, 0, 0);
+          if constexpr (NP == 3) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][1], x0, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][0], x1, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][2], x0, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][1], x1, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][0], x2, acc[i][j], 0, 0, 0);
+          }
         }
       }
     }

@@ -48,7 +48,10 @@ static int launch_quad_flip(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
 // consumers' registers at 32 x 128 per wave), or x 128 (the small feature maps: pixel-major tiles prune the padding taps per
 // pixel, 1x1 maps); the patch of one octet plane has to fit 301 pixels (two planes when a single tap is active).
 static int launch_split_flip_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
-  if (contraction_mode() != 0) return 1;   // f32: the fp32 kernels; bf16x2: Reparameterization only
+  {   // f32: the fp32 kernels; bf16x2: Reparameterization only. (The bf16 mode leaves Flipout as it is in the automatic mode.)
+    const int mode = contraction_mode();
+    if (mode == 1 || mode == 2) return 1;
+  }
   if (!packed_ok(a)) return 1;
   if (a.Cig <= 4) return launch_quad_flip(a, ran, stream);   // the stems
   if ((a.Cig & 7) || a.T > 9 || a.ep_pool) return 1;

@@ -6,7 +6,7 @@
 
 namespace bt {
 
-int contraction_mode();  // bt_fused_split.hip: 0 automatic, 1 fp32 MFMA only, 2 bf16x2 (opt-in)
+int contraction_mode();  // bt_fused_split.hip: 0 automatic, 1 fp32 MFMA only, 2 bf16x2 (opt-in), 3 bf16 (opt-in)
 
 // ceil(2^32 / d): __umulhi(n, .) == n / d for every dividend n with n * d < 2^32. 0 when that cannot be promised (or d == 1):
 // the kernel then divides.

@@ -44,11 +44,14 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
   constexpr int BN = 64, BM = FLIP ? 256 : 512, kProducers = 256, kThreadsAll = 512, STEPS = kSplitSteps, TPS = 4 * STEPS;  // taps per stage
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32, NOP = FLIP ? 2 : 1;
   constexpr int PBQ = 8 * NP;  // bytes per pixel of the quad patch
-  constexpr int W_BYTES = split_w_bytes<BN, NP, FLIP>(), W_OP = W_BYTES / NOP, XQ_BYTES = FLIP ? kQuadXBytesFlip : kQuadXBytes;
+  // (NP = 1, the bf16 mode of bt_fused_split.h: the buffers keep the exact split's strides -- the output staging needs their room -- and
+  //  hold one piece per value; the patch room is the same, so the launch's plan is the exact split's)
+  constexpr int W_BYTES = split_w_bytes<BN, NP == 1 ? 3 : NP, FLIP>(), W_OP = W_BYTES / NOP, XQ_BYTES = FLIP ? kQuadXBytesFlip : kQuadXBytes;
   constexpr int W_STEP = 2 * NP * BN * 16, W_HALF = NP * BN * 16, W_PIECE = BN * 16;
   // (the patch region holds XQ_BYTES / PBQ pixels: the host checks PCH against it)
   constexpr int SROWS = BN, SROW = BM + 4;
   static_assert(!FLIP || NP == 3, "Flipout: the exact split");
+  static_assert(NP != 1 || (!WALK && !INJ), "the bf16 mode: the one-sample path, on-chip draws");
   static_assert(!WALK || (POOL && !FLIP && CWM == 4 && TN == 2 && TM == 4), "the walk: Reparameterization, pooled, 4 x 128-pixel consumer waves");
   static_assert((4 * BN + NOP * SROWS * SROW) * 4 <= 2 * W_BYTES + XQ_BYTES, "output staging fits the operand buffers");
 
@@ -344,6 +347,10 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
 #pragma unroll
       for (int k = 0; k < XB; ++k) {
         if (pos_[k] < PCH) {
+          if constexpr (NP == 1) {  // one piece, rounded to nearest even
+            *reinterpret_cast<uint2*>(xq + pos_[k] * PBQ) = make_uint2(rne_pair(xv[k][0], xv[k][1]), rne_pair(xv[k][2], xv[k][3]));
+            continue;
+          }
           uint32_t ph[4], pm[4], pl[4];
 #pragma unroll
           for (int c = 0; c < 4; ++c) split_pieces(xv[k][c], ph[c], pm[c], pl[c]);
@@ -358,7 +365,7 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
           }
           char* const dst = xq + pos_[k] * PBQ;
           *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(ph[1], ph[0]), pack_hi16(ph[3], ph[2]));
-          *reinterpret_cast<uint2*>(dst + 8) = make_uint2(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]));
+          if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + 8) = make_uint2(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]));
           if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 16) = make_uint2(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]));
         }
       }
@@ -380,13 +387,20 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
 #pragma unroll
       for (int i = 0; i < UMAX; ++i) {
         const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
+        if constexpr (NP == 1) {  // the fp32 sampled weight, rounded once
+          float w4[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j]));
+          *reinterpret_cast<uint2*>(Wt + l_off[i]) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
+          continue;
+        }
         uint32_t wh[4], wm_[4], wl[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j)  // masked units (dead taps, rows past Cog) loaded zeros: w = 0 -- and the slot IS written
           split_pieces(FLIP ? m4[j] : __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j])), wh[j], wm_[j], wl[j]);
         char* const dst = Wt + l_off[i];
         *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
-        *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+        if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
         if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
         if constexpr (FLIP) {  // second image: the perturbation sigma * eps
 #pragma unroll
@@ -543,8 +557,10 @@ __global__ __launch_bounds__(512) void fused_split_quad_kernel(const FwdArgs a) 
 #pragma unroll
               for (int i = 0; i < TN; ++i) {
                 acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
-                acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
-                acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[1], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                if constexpr (NP >= 2) {
+                  acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
+                  acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[1], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                }
                 if constexpr (NP == 3) {
                   acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[q & 1][o][i][2], acc[o][i][j], 0, 0, 0);
                   acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[1], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);

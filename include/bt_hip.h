@@ -63,7 +63,7 @@ typedef struct bt_rng {
  * eps_b stays [S][Co]. Reparameterization only. The launch is offered to the split-precision (bf16x3) kernels alone, whose
  * injected instantiations read a unit's four draws with one 16-byte load where the on-chip ones run Philox: the same draws give
  * the same output bits as the on-chip launch. Needs mu_packed / sigma_packed; BT_ERR_UNSUPPORTED (nothing launched) with sign
- * tensors, under bt_set_contraction(1 | 2) / BT_CONTRACTION=f32 | bf16x2, or when no split flavour takes the launch -- call again
+ * tensors, under bt_set_contraction(1 | 2 | 3) / BT_CONTRACTION=f32 | bf16x2 | bf16, or when no split flavour takes the launch -- call again
  * with the natural layout then. The fused max-pool is available on this path. */
 #define BT_DRAWS_EPS_PACKED 1u
 /* With BT_DRAWS_EPS_PACKED, on the Flipout entry points: bt_draws.sign_in / sign_out point at the [S] BYTE images written by
@@ -74,7 +74,7 @@ typedef struct bt_rng {
  * images, 16-byte aligned, and mu_packed / sigma_packed. CONTRACT FOR THE SIGNS ON THIS PATH: +1 or -1. A byte image has no third
  * value: an exact 0 (torch's uniform_(-1, 1).sign() yields one with probability 2^-24 per element) is read as +1, and bt_pack_signs
  * counts it; the natural-layout path keeps multiplying by whatever value it is given. BT_ERR_BAD_ARG without BT_DRAWS_EPS_PACKED or
- * on a Reparameterization entry point; BT_ERR_UNSUPPORTED (nothing launched) under a forced f32 / bf16x2 contraction or when no
+ * on a Reparameterization entry point; BT_ERR_UNSUPPORTED (nothing launched) under a forced f32 / bf16x2 / bf16 contraction or when no
  * split-precision Flipout flavour takes the geometry -- call again with the natural layouts then. BT_DRAWS_EPS_PACKED alone on a
  * Flipout entry point stays BT_ERR_UNSUPPORTED. The fused max-pool is available on this path (the Flipout stem kernel). */
 #define BT_DRAWS_SIGNS_PACKED 2u
@@ -307,13 +307,25 @@ int bt_kl_normal_bwd_segs(int32_t n_segments, const float *const *mu, const floa
                           const float *const *prior_sigma, const int64_t *numel, const float *grad_kl, uint32_t flags,
                           float *const *dmu, float *const *drho, bt_stream_t stream);
 
-/* Contraction arithmetic of the fused forwards (process-wide; default from env BT_CONTRACTION = f32 | bf16x3 | bf16x2):
+/* Contraction arithmetic of the fused forwards (process-wide; read at every launch, so a captured graph keeps the kernels it was
+ * captured with; default from env BT_CONTRACTION = f32 | bf16x3 | bf16x2 | bf16):
  *   0  automatic: wherever a launch is eligible, every fp32 operand is cut into three bf16 pieces (an EXACT split of the
  *      24-bit significand) and the product runs as the 6 piece products of weight >= 2^-16 on the bf16 matrix pipe with
  *      fp32 accumulation -- fp32-level accuracy at 6/16 of the fp32-MFMA time; other launches use fp32 MFMA;
  *   1  fp32 MFMA everywhere (the bit-exact fp32 FMA chain of round 1);
- *   2  two pieces, 3 product terms (relative error ~1e-5 per product): opt-in. */
+ *   2  two pieces, 3 product terms (relative error ~1e-5 per product): opt-in;
+ *   3  bf16, opt-in, meant for inference: every operand value -- x, and the sampled weight mu + sigma * eps formed in fp32 exactly as
+ *      in mode 0 -- is rounded ONCE to bf16 (nearest even) and the product is ONE term per K16 step, fp32 accumulate: relative error
+ *      <= 2^-8 per product. It applies to the Reparameterization launches with on-chip draws that mode 0 gives to the general split,
+ *      stem or direct kernel, with the same launch plan (the kernel name carries `bf16x1,1 terms` where mode 0's carries
+ *      `bf16x3,6 terms`); K order, draw streams, bias draw, output stage and KL (bit-identical to mode 0's) are unchanged. Every
+ *      other launch -- Flipout, whatever mode 0 runs on fp32 MFMA, natural-layout injected draws -- runs exactly as in mode 0;
+ *      packed injected draws are BT_ERR_UNSUPPORTED as in modes 1 and 2. The backward is not affected: a forward made in this mode
+ *      is differentiated by the fp32 backward of the unrounded function.
+ * BT_ERR_BAD_ARG for any other mode. */
 int bt_set_contraction(int mode);
+/* The mode in force (0..3): what bt_set_contraction last set, else BT_CONTRACTION, else 0. */
+int bt_get_contraction(void);
 
 /* MC epilogue (examples/main_bayesian_cifar_dnn2bnn.py:551-557 and :402-412): from logits [S][B][C]
  * accumulate into packed[B*C + B + B*C] = [sum_s softmax | sum_s entropy | sum_s logits] (overwrites). */

@@ -24,7 +24,7 @@ ap.add_argument("--flip", action="store_true")
 ap.add_argument("--kl", action="store_true")
 ap.add_argument("--shared", action="store_true")
 ap.add_argument("--sigma", action="store_true")
-ap.add_argument("--mode", type=int, default=0, help="bt_set_contraction: 0 auto (bf16x3 split), 1 fp32 MFMA, 2 bf16x2")
+ap.add_argument("--mode", type=int, default=0, help="bt_set_contraction: 0 auto (bf16x3 split), 1 fp32 MFMA, 2 bf16x2, 3 bf16 (one rounded piece, 1 term)")
 a = ap.parse_args()
 Ci, Co, k, st, pd, H = SHAPES[a.shape]
 dev = torch.device("cuda")
