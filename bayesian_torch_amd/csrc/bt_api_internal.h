@@ -14,6 +14,7 @@ namespace bt {
 
 int set_error(int code, const char* msg);  // records msg for bt_last_error_string(); returns code
 void note_kernel(const char* name);         // records the kernel instance a fused launch chose (bt_last_kernel_name)
+bool plan_only();                           // test seam (bt_debug_plan_only): launch_kernel records the name and launches nothing
 
 inline int check_launch(const char* who) {
   const hipError_t e = hipGetLastError();
@@ -48,6 +49,10 @@ inline int raise_lds_limit(const void* kern, int bytes, const char* who) {
 template <typename... P, typename... A>
 int launch_kernel(void (*kern)(P...), const char* name, const char* who, dim3 grid, dim3 block, int lds, int lds_limit, hipStream_t stream,
                   const A&... args) {
+  if (plan_only()) {
+    if (name) note_kernel(name);
+    return BT_OK;
+  }
   if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kern), lds_limit, who)) return rc;
   if (name) note_kernel(name);
   hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);

@@ -9,9 +9,6 @@ int launch_reparam(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stre
 int launch_reparam_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
-int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);   // bt_fused_split.hip: 0 taken, 1 not applicable, < 0 error
-int launch_split_flip(FwdArgs a, FwdArgs& ran, hipStream_t stream);   // bt_fused_split_flip.hip: likewise
-int contraction_mode();
 
 static unsigned long long* g_dbg = nullptr;
 static thread_local long long g_launch_info[16] = {};
@@ -183,7 +180,6 @@ extern "C" int bt_flipout_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const f
   return bt::run(true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, stream, "bt_flipout_conv2d_fwd");
 }
 
-namespace bt { long long skinny_scratch_bytes(const bt_conv2d_geom& g, int S); }
 extern "C" size_t bt_fused_scratch_bytes(const bt_conv2d_geom* g, int32_t S) {
   if (!g || S <= 0) return 0;
   const long long n = bt::skinny_scratch_bytes(*g, S);

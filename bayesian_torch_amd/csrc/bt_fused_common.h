@@ -34,7 +34,7 @@ struct FwdArgs {
   int ep_relu;
   int ep_pool, ep_Hp, ep_Wp;  // fused 3x3 / stride 2 / pad 1 max-pool of the output stage (fast flavour, whole-image tiles)
   int out_vec4;  // spatial output stored as float4 along the pixel index (TRANS orientation; Ho*Wo % 4 == 0, aligned tensors)
-  int bn32;                 // general split kernel: 32-channel tiles (launch_split_one)
+  int bn32;                 // general split kernel: 32-channel tiles (split_plan)
   unsigned long long* dbg;  // diagnostic stamps (bt_debug_set_stamp_buffer); null in normal operation
   // split flavour: ceil(2^32 / d) of the launch-uniform divisors (0: divide), so the tile decode is a few multiplies
   uint32_t inv_m_tiles, inv_S, inv_n_tiles, inv_n_bt, inv_n_ct, inv_rw, inv_wt, inv_kw;
@@ -50,6 +50,13 @@ struct FwdArgs {
   int spw, n_sg;        // quad flavour, sample walk: samples per workgroup, sample groups = ceil(S / spw) (launch_quad)
   uint32_t inv_n_sg;
 };
+
+// The split-precision chains (bt_fused_split.hip, bt_fused_split_flip.hip), for every translation unit that calls them. Each works on
+// its own copy of the arguments: BT_OK and the plan that ran in `ran` when a flavour took the launch, 1 when none applies, < 0 on error.
+int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);
+int launch_split_flip(FwdArgs a, FwdArgs& ran, hipStream_t stream);
+int contraction_mode();   // 0 automatic, 1 fp32 MFMA only, 2 bf16x2 (opt-in), 3 bf16 (opt-in)
+long long skinny_scratch_bytes(const bt_conv2d_geom& g, int S);   // the split-K flavour's scratch behind the workspace (0: not its launch)
 
 // ---------------------------------------------------------------------------- draw-stream keys
 // The weight draws' key of this launch: (seed, call + the device-side call word, layer, tensor 0).

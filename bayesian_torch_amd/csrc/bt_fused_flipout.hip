@@ -1,6 +1,5 @@
 #include "bt_fused_dispatch.h"
 namespace bt {
-int launch_split_flip(FwdArgs a, FwdArgs& ran, hipStream_t stream);  // bt_fused_split_flip.hip: 0 taken, 1 not applicable, < 0 error
 int launch_flipout(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream) {
   const int rc = launch_split_flip(a, ran, stream);
   if (rc <= 0) return rc;

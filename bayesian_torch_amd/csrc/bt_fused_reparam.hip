@@ -1,6 +1,5 @@
 #include "bt_fused_dispatch.h"
 namespace bt {
-int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);  // bt_fused_split.hip: 0 taken, 1 not applicable, < 0 error
 int launch_reparam(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream) {
   // (a Linear layer is a 1x1 convolution over 1x1 images: the same memory layout)
   const int rc = launch_split(a, ran, stream);

@@ -1,85 +1,19 @@
 // Host side of the split-precision flavour (bt_fused_split.h): eligibility, tile geometry, launch.
-#include <atomic>
 #include <stdlib.h>
 #include <string.h>
 
-#include "bt_fused_split_quad.h"
-#include "bt_fused_split_direct.h"
-#include "bt_fused_split_skinny.h"
 #include "bt_fused_split_host.h"
+#include "bt_fused_split_launch.h"
 
 namespace bt {
 
-// The injected-draw instantiations of the four kernels (bt_fused_split_inj.hip). A launch that reaches this chain with a.eps_w set
-// carries PACKED draws (bt_pack_eps; bt::run sends the natural layout to the fp32 general kernel): the flavour functions below
-// choose flavour and geometry exactly as for on-chip draws and hand the launch to these.
-int launch_split_inj_cfg(const FwdArgs& a, int bm, int xm, hipStream_t stream);
-int launch_quad_inj(const FwdArgs& a, hipStream_t stream);
-int launch_direct_inj(const FwdArgs& a, bool resident, hipStream_t stream);
-int launch_skinny_inj(const FwdArgs& a, int ks, hipStream_t stream);
-
-// The bf16 mode's instantiations (bt_fused_split_bf16.hip): Reparameterization with on-chip draws. The flavour functions choose
-// flavour and geometry exactly as in the automatic mode -- a launch's plan does not depend on the mode -- and hand the launch to these.
-int launch_split_bf16_cfg(const FwdArgs& a, int bm, int xm, hipStream_t stream);
-int launch_quad_bf16(const FwdArgs& a, hipStream_t stream);
-int launch_direct_bf16(const FwdArgs& a, bool resident, hipStream_t stream);
-
 // 0: automatic (6-term exact split where the launch is eligible), 1: fp32 MFMA only, 2: 3-term split (opt-in, ~1e-5 relative),
 // 3: bf16 (opt-in: operands rounded once to bf16, 1 term, where mode 0 runs the general split, stem or direct kernel; else as mode 0)
-static std::atomic<int> g_contraction{-1};
-int contraction_mode() {
-  int m = g_contraction.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("BT_CONTRACTION");
-    m = !e ? 0 : (!strcmp(e, "f32") ? 1 : !strcmp(e, "bf16x2") ? 2 : !strcmp(e, "bf16") ? 3 : 0);
-    g_contraction.store(m, std::memory_order_relaxed);
-  }
-  return m;
-}
-
-template <int BM, int NP, int NPW, int XM, int BN = 64>
-static int launch_split_cfg(const FwdArgs& a, hipStream_t stream) {
-  constexpr int lds = split_lds_bytes<BN, BM, NP>();
-  static_assert(lds <= 160 * 1024, "LDS budget of one CU");
-  char nm[160];
-  snprintf(nm, sizeof(nm), "fused_split_kernel<%d,%d,bf16x%d,%d terms,npw=%d,xm=%d>", BN, BM, NP, NP == 3 ? 6 : 3, NPW, XM);
-  return launch_kernel(fused_split_kernel<BN, BM, NP, NPW, XM>, nm, "fused forward (split)", dim3((unsigned)a.total_blocks), dim3(256 + 64 * NPW),
-                       lds, lds, stream, a);
-}
-
-template <int BM, int NPW>
-static int launch_split_xm(const FwdArgs& a, int mode, int xm, hipStream_t stream) {
-  if (mode == 2) return launch_split_cfg<BM, 2, NPW, 0>(a, stream);   // (the opt-in 3-term form keeps the generic fetch)
-  if constexpr (BM == 128) {
-    if (a.bn32) {   // 32-channel tiles of a launch that would leave CUs idle (launch_split_one); same K order, same bits
-      if (xm == 1) return launch_split_cfg<BM, 3, NPW, 1, 32>(a, stream);
-      if (xm == 2) return launch_split_cfg<BM, 3, NPW, 2, 32>(a, stream);
-      return launch_split_cfg<BM, 3, NPW, 0, 32>(a, stream);
-    }
-    if (xm == 1) return launch_split_cfg<BM, 3, NPW, 1>(a, stream);
-    if (xm == 2) return launch_split_cfg<BM, 3, NPW, 2>(a, stream);
-  } else {
-    if (xm == 3) return launch_split_cfg<BM, 3, NPW, 3>(a, stream);
-    if (xm == 4) return launch_split_cfg<BM, 3, NPW, 4>(a, stream);
-    if constexpr (BM == 256) {
-      if (xm == 2) return launch_split_cfg<BM, 3, 8, 2>(a, stream);
-    }
-  }
-  return launch_split_cfg<BM, 3, NPW, 0>(a, stream);
-}
-
-// Layers with <= 4 input channels per group (the ResNet stems): bt_fused_split_quad.h. Whole-image 512-wide tiles, output through
-// the LDS-staged read-out (optionally with the fused 3x3 / stride-2 max-pool, power-of-two pooled widths).
-template <bool POOL, bool WALK = false>
-static int launch_quad_cfg(const FwdArgs& a, hipStream_t stream) {
-  constexpr int lds = split_lds_bytes<64, 512, 3>();
-  auto launch = [&](auto kern, const char* nm) {
-    return launch_kernel(kern, nm, "fused forward (split, quad)", dim3((unsigned)a.total_blocks), dim3(512), lds, lds, stream, a);
-  };
-  // (the opt-in two-piece form is not instantiated for the stems: they run the exact split in every split mode)
-  if constexpr (WALK) return launch(fused_split_quad_kernel<3, true, false, true>, "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=1,walk>");
-  return launch(fused_split_quad_kernel<3, POOL>, POOL ? "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=1>" : "fused_split_quad_kernel<64,512,bf16x3,6 terms,pool=0>");
-}
+static EnvKnob g_contraction{"BT_CONTRACTION", [](const char* e) { return !e ? 0 : (!strcmp(e, "f32") ? 1 : !strcmp(e, "bf16x2") ? 2 : !strcmp(e, "bf16") ? 3 : 0); }};
+int contraction_mode() { return g_contraction.get(); }
+EnvKnob g_bn32{"BT_BN32", [](const char* e) { return e ? (atoi(e) ? 1 : 0) : -1; }};   // -1 automatic; 0 / 1 forced (split_plan)
+static EnvKnob g_direct_off{nullptr, [](const char*) { return 0; }};   // (bt_debug_disable_direct alone)
+static EnvKnob g_skinny_off{"BT_NO_SKINNY", [](const char* e) { return (e && *e && *e != '0') ? 1 : 0; }};   // measurement knob (tools/trace_layers.py), like its test hook
 
 // Samples per workgroup of the quad flavour's sample walk (0: the one-sample path). Pooled 16x16 maps in tiles of two images over
 // an input that every sample shares: the patch is staged once for a run of samples. The largest of 8 / 4 / 2 that still gives a
@@ -119,17 +53,14 @@ static int launch_quad(FwdArgs a, FwdArgs& ran, int mode, hipStream_t stream) {
   ran = a;
   if (a.eps_w) return launch_quad_inj(a, stream);
   if (mode == 3) return launch_quad_bf16(a, stream);
-  if (spw) return launch_quad_cfg<true, true>(a, stream);
-  return a.ep_pool ? launch_quad_cfg<true>(a, stream) : launch_quad_cfg<false>(a, stream);
+  return spw ? launch_split_quad<3, false, false, true>(a, stream) : launch_split_quad<3, false, false>(a, stream);
 }
 
 // 1x1 / stride-1 convolutions with K <= 256 and many pixels (the bottleneck ResNets' expanding / reducing layers): the persistent
 // kernel of bt_fused_split_direct.h. Eligibility is geometric (never a matter of S or of the launch split), and its arithmetic is the
 // general kernel's, so a layer's results do not depend on which of the two serves it.
-static std::atomic<int> g_bn32{-2};   // -2: read BT_BN32 once; -1 automatic; 0 / 1 forced (bt_debug_force_bn32)
-static std::atomic<int> g_direct_off{0};
 static int launch_direct(FwdArgs a, FwdArgs& ran, int mode, hipStream_t stream) {
-  if (g_direct_off.load(std::memory_order_relaxed)) return 1;
+  if (g_direct_off.get()) return 1;
   if (a.ep_pool) return 1;
   // a 1x1 kernel without padding (any stride), or any window over a 1x1 image whose ONE live tap sits on the pixel (ResNet18 / CIFAR
   // layer4: 3x3, padding 1, 1x1 maps -- the centre tap; Linear layers are 1x1 kernels over 1x1 images)
@@ -176,15 +107,8 @@ static int launch_direct(FwdArgs a, FwdArgs& ran, int mode, hipStream_t stream) 
   a.inv_rw = inv_u32(a.HoWo, (long long)a.M + 64 * 8 * 2);   // pixel index -> (image, output position)
   a.inv_wt = inv_u32(a.Wo, a.HoWo);                          // output position -> (row, column): strided layers
   ran = a;
-  if (mode == 3 && !a.eps_w) return launch_direct_bf16(a, resident, stream);
-  // (the LDS limit is raised to the largest launch of each variant: K = 256 resident, any K streamed)
-  auto launch = [&](auto kern, const char* nm, int max_lds) {
-    return launch_kernel(kern, nm, "fused forward (split, direct)", dim3((unsigned)a.total_blocks), dim3(kDirectThreads), direct_lds_bytes(a.Cig),
-                         max_lds, stream, a);
-  };
   if (a.eps_w) return launch_direct_inj(a, resident, stream);
-  if (resident) return launch(fused_split_direct_kernel<true>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,resident W>", direct_lds_bytes(kDirectMaxK));
-  return launch(fused_split_direct_kernel<false>, "fused_split_direct_kernel<64,8x64,bf16x3,6 terms,streamed W>", direct_lds_bytes(kDirectMaxK + 1));
+  return mode == 3 ? launch_direct_bf16(a, resident, stream) : launch_split_direct<3, false>(a, resident, stream);
 }
 
 // Layers whose output map is one pixel and whose batch is small (Linear, CIFAR-sized layer4, the classifier head): the split-K kernel of
@@ -222,15 +146,8 @@ long long skinny_scratch_bytes(const bt_conv2d_geom& g, int S) {
   SkinnyPlan p;
   return skinny_plan(g.B, g.Ci, g.H, g.W, g.Co, g.kh, g.kw, g.ph, g.pw, g.dh, g.dw, g.groups, Ho, Wo, S, &p) ? p.scratch : 0;
 }
-static std::atomic<int> g_skinny_off{-1};
 static int launch_skinny(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
-  int off = g_skinny_off.load(std::memory_order_relaxed);
-  if (off < 0) {   // env BT_NO_SKINNY=1: measurement knob (tools/trace_layers.py), like the test hook below
-    const char* e = getenv("BT_NO_SKINNY");
-    off = (e && *e && *e != '0') ? 1 : 0;
-    g_skinny_off.store(off, std::memory_order_relaxed);
-  }
-  if (off || a.ep_pool || !a.sk_scratch || !a.sk_tickets) return 1;
+  if (g_skinny_off.get() || a.ep_pool || !a.sk_scratch || !a.sk_tickets) return 1;
   SkinnyPlan p;
   if (!skinny_plan(a.B, a.Ci, a.H, a.W, a.Co, a.KH, a.KW, a.PH, a.PW, a.DH, a.DW, a.G, a.Ho, a.Wo, a.S, &p)) return 1;
   if (p.scratch > a.sk_scratch_bytes) return 1;   // the caller brought no (or too little) scratch: the other flavours serve the launch
@@ -243,11 +160,7 @@ static int launch_skinny(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   if (!set_grid(a, p.tiles * p.nsl)) return 1;
   a.x_vec = (a.HW == 1 && ((((uintptr_t)a.x) & 15u) == 0) && (a.x_sample_stride & 3) == 0 && (a.Ci & 3) == 0) ? 1 : 0;
   ran = a;
-  if (a.eps_w) return launch_skinny_inj(a, p.ks, stream);
-  return launch_kernel(fused_split_skinny_kernel<false>,
-                       p.ks == 128 ? "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 128>" : "fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K 64>",
-                       "fused forward (split, skinny)", dim3((unsigned)a.total_blocks), dim3(kSkinnyThreads), skinny_lds_bytes(p.ks), skinny_lds_bytes(128),
-                       stream, a);
+  return a.eps_w ? launch_skinny_inj(a, p.ks, stream) : launch_split_skinny<false>(a, p.ks, stream);
 }
 
 // The stems', split-K, direct and general split kernels for one tile kind (the caller runs the fp32 kernels when none applies).
@@ -259,7 +172,7 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   const bool inj = a.eps_w != nullptr;
   if (inj && mode >= 2) return 1;   // (the opt-in forms have no injected instantiation)
   if (a.Cig <= 4) return launch_quad(a, ran, mode, stream);   // the stems
-  // whole channel octets, at most 9 taps, no fused pooling
+  // whole channel octets, no fused pooling
   if ((a.Cig & 7) || a.ep_pool) return 1;
   if (mode != 2) {   // (the flavours with a single live tap per slice / layer take any window size)
     // (the bf16 mode has no split-K instantiation: the direct / general kernels serve those launches)
@@ -268,61 +181,12 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
     const int rcd = launch_direct(a, ran, mode, stream);
     if (rcd <= 0) return rcd;
   }
-  if (a.T > 9) return 1;
-  const int Mdom = a.pixel_major ? a.B : a.M;
-  if (Mdom < 112) return 1;
-  a.n_tiles = (a.Cog + 63) / 64;
-  FwdArgs b512 = a, b256 = a, b128 = a;
-  const int live512 = Mdom >= 512 ? split_geometry<512>(b512) : 0;
-  const int live256 = Mdom >= 256 ? split_geometry<256>(b256) : 0;
-  const int live128 = split_geometry<128>(b128);
-  const long long per = (long long)a.G * a.n_tiles * a.S;
-  // the producers' synthesis floor: the 128-wide tile has 8 producer waves, the others 4
-  const double c512 = split_tile_cost(b512, live512, 512, 256, 96), c256 = split_tile_cost(b256, live256, 256, 256, 96),
-               c128 = split_tile_cost(b128, live128, 128, 128, 96);
-  int bm = 0;
-  static const int force_bm = [] { const char* e = getenv("BT_FORCE_BM"); return e ? atoi(e) : 0; }();   // measurement knob: prefer this tile width where it is eligible
-  if (force_bm == 512 && c512 < 1e30) bm = 512;
-  else if (force_bm == 256 && c256 < 1e30) bm = 256;
-  else if (force_bm == 128 && c128 < 1e30) bm = 128;
-  else if (c512 < 1e30 && c512 <= c256 && c512 <= c128) bm = 512;
-  else if (c256 < 1e30 && c256 <= c128) bm = 256;
-  else if (c128 < 1e30) bm = 128;
-  if (!bm) return 1;
-  a = bm == 512 ? b512 : bm == 256 ? b256 : b128;
-  // A 128-wide launch that offers at most one workgroup per two CUs (a training step's single sample; an MLP's wide first layer at 8
-  // samples) runs in 32-channel tiles instead: twice the workgroups, each drawing half the weights -- the chain of a workgroup of such a
-  // layer IS its weight synthesis. The K order does not depend on the channel tile, so the results are the same bits (and the choice may
-  // depend on S). BT_BN32 = 0 | 1 forces it off / on where eligible (tests, measurement).
-  int bn32_env = g_bn32.load(std::memory_order_relaxed);
-  if (bn32_env == -2) {
-    const char* e = getenv("BT_BN32");
-    bn32_env = e ? (atoi(e) ? 1 : 0) : -1;
-    g_bn32.store(bn32_env, std::memory_order_relaxed);
-  }
-  a.bn32 = 0;
-  if (bm == 128 && mode != 2 && a.Cog > 32) {
-    const long long wgs64 = per * a.m_tiles;
-    a.bn32 = bn32_env >= 0 ? (bn32_env ? 1 : 0) : (2 * wgs64 <= 256 ? 1 : 0);
-  }
-  if (a.bn32) a.n_tiles = (a.Cog + 31) / 32;
-  if (!set_grid(a, (long long)a.G * a.n_tiles * a.S * a.m_tiles)) return 1;
-  // x fetch mode (bt_fused_split.h): tiny input planes are read as 16-byte vectors
-  const bool xal = (((uintptr_t)a.x) & 15u) == 0 && (a.x_sample_stride & 3) == 0;
-  int xm = 0;
-  if (xal && a.HW == 1) xm = 1;
-  else if (xal && bm != 128 && !a.pixel_major && a.HW > 1 && (a.W & 3) == 0 && a.t_Wt == a.Wo && split_row_mode(a)) xm = split_row_mode(a);
-  else if (xal && bm != 128 && !a.pixel_major && a.HW > 1 && split_plane_flat(a)) xm = 3, a.x_flat = 1;
-  else if (xal && bm == 128 && !a.pixel_major && a.H == 2 && a.W == 2 && split_plane_flat(a)) xm = 2;   // whole 2x2 planes (a strided 3x3 down to 1x1 maps)
-  else if (xal && bm != 512 && a.row_taps && a.H == 2 && a.W == 2 && a.KW == 3 && a.PW == 1 && a.SW == 1 && a.DW == 1) xm = 2;   // a row tile's patch is the whole 2x2 plane
-  else if (xal && a.pixel_major && a.H == 2 && a.W == 2 && a.KH == 3 && a.KW == 3 && a.PH == 1 && a.PW == 1 && a.SH == 1 && a.SW == 1 && a.DH == 1 && a.DW == 1) xm = 2;
-  split_fill_inverses(a);
+  int bm, xm;
+  if (split_plan<false>(a, mode, &bm, &xm)) return 1;
   ran = a;
   if (inj) return launch_split_inj_cfg(a, bm, xm, stream);
   if (mode == 3) return launch_split_bf16_cfg(a, bm, xm, stream);
-  if (bm == 512) return launch_split_xm<512, 4>(a, mode, xm, stream);
-  if (bm == 256) return launch_split_xm<256, 8>(a, mode, xm, stream);
-  return launch_split_xm<128, 8>(a, mode, xm, stream);
+  return mode == 2 ? launch_split_general<2, false, false>(a, bm, xm, stream) : launch_split_general<3, false, false>(a, bm, xm, stream);   // (bf16x2: the generic fetch alone)
 }
 
 // Pixel-major tiles (2..4-pixel outputs) prune the padding taps per pixel: the first choice. When their patch does not fit (a
@@ -349,9 +213,9 @@ int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
 }  // namespace bt
 
 // Test hook (not part of include/bt_hip.h): 1 keeps 1x1 convolutions off the direct kernel, so a test can compare the two flavours.
-extern "C" void bt_debug_disable_direct(int off) { bt::g_direct_off.store(off ? 1 : 0, std::memory_order_relaxed); }
-extern "C" void bt_debug_force_bn32(int v) { bt::g_bn32.store(v < 0 ? -1 : (v ? 1 : 0), std::memory_order_relaxed); }
-extern "C" void bt_debug_disable_skinny(int off) { bt::g_skinny_off.store(off ? 1 : 0, std::memory_order_relaxed); }
+extern "C" void bt_debug_disable_direct(int off) { bt::g_direct_off.set(off ? 1 : 0); }
+extern "C" void bt_debug_force_bn32(int v) { bt::g_bn32.set(v < 0 ? -1 : (v ? 1 : 0)); }
+extern "C" void bt_debug_disable_skinny(int off) { bt::g_skinny_off.set(off ? 1 : 0); }
 
 // Contraction arithmetic of the fused forwards (process-wide knob, read at every launch; also env BT_CONTRACTION = f32 | bf16x3 |
 // bf16x2 | bf16): 0 automatic -- exact bf16x3 split (6 product terms, fp32 accumulate) on the bf16 matrix pipe wherever the launch is
@@ -360,7 +224,7 @@ extern "C" void bt_debug_disable_skinny(int off) { bt::g_skinny_off.store(off ? 
 // split, stem or direct kernel -- same plan; every other launch as in mode 0).
 extern "C" int bt_set_contraction(int mode) {
   if (mode < 0 || mode > 3) return bt::set_error(BT_ERR_BAD_ARG, "bt_set_contraction: mode must be 0 (auto), 1 (f32), 2 (bf16x2) or 3 (bf16)");
-  bt::g_contraction.store(mode, std::memory_order_relaxed);
+  bt::g_contraction.set(mode);
   return BT_OK;
 }
 extern "C" int bt_get_contraction(void) { return bt::contraction_mode(); }

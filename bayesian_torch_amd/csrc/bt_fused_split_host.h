@@ -1,12 +1,36 @@
-// Host-side helpers shared by the split flavour's translation units (bt_fused_split.hip, bt_fused_split_flip.hip).
+// Host-side helpers shared by the split flavour's translation units: the process-wide knobs, the tile geometry and the planner of
+// the general kernel's tile (bt_fused_split.hip, bt_fused_split_flip.hip). The launchers are in bt_fused_split_launch.h.
 #pragma once
+#include <limits.h>
 #include <stdlib.h>
+
+#include <atomic>
 
 #include "bt_fused_split.h"
 
 namespace bt {
 
-int contraction_mode();  // bt_fused_split.hip: 0 automatic, 1 fp32 MFMA only, 2 bf16x2 (opt-in), 3 bf16 (opt-in)
+// A process-wide int knob: first read from an environment variable (`parse` gets getenv's answer, null when unset; env == null:
+// no variable), overridable at any time by a hook (set).
+class EnvKnob {
+ public:
+  constexpr EnvKnob(const char* env, int (*parse)(const char*)) : env_(env), parse_(parse) {}
+  int get() {
+    int v = v_.load(std::memory_order_relaxed);
+    if (v == INT_MIN) {
+      v = parse_(env_ ? getenv(env_) : nullptr);
+      v_.store(v, std::memory_order_relaxed);
+    }
+    return v;
+  }
+  void set(int v) { v_.store(v, std::memory_order_relaxed); }
+
+ private:
+  const char* env_;
+  int (*parse_)(const char*);
+  std::atomic<int> v_{INT_MIN};
+};
+extern EnvKnob g_bn32;   // bt_fused_split.hip: -1 automatic; 0 / 1 forced (BT_BN32, bt_debug_force_bn32)
 
 // ceil(2^32 / d): __umulhi(n, .) == n / d for every dividend n with n * d < 2^32. 0 when that cannot be promised (or d == 1):
 // the kernel then divides.
@@ -189,6 +213,88 @@ static bool quad_geometry(FwdArgs& a, int BM, long long xcap) {
   a.n_tiles = (a.Cog + 63) / 64;
   a.t_NI = NI, a.t_R = R, a.t_Wt = a.Wo, a.n_bt = (a.B + NI - 1) / NI, a.n_rt = (a.Ho + R - 1) / R, a.n_ct = 1, a.m_tiles = a.n_bt * a.n_rt;
   return true;
+}
+
+// ---------------------------------------------------------------------------- the general kernel's tile
+// What the two chains plan differently. Candidate widths, widest first: 512 / 256 / 128 for Reparameterization; 256 / 128 for Flipout
+// (its two accumulator sets fill the consumers' registers at 32 x 128 per wave), and no 256 for pixel-major tiles. The producers'
+// synthesis floor of a width (the 128-wide Reparameterization tile has 8 producer waves, the others 4) and the fixed cost of a
+// workgroup, both in column-equivalents (split_tile_cost).
+constexpr int kSplitWidths[3] = {512, 256, 128};
+template <bool FLIP>
+constexpr int split_synth(int bm) { return FLIP || bm == 128 ? 128 : 256; }
+template <bool FLIP>
+constexpr int split_fixed() { return FLIP ? 48 : 96; }
+
+// x fetch mode of a planned tile (bt_fused_split.h): tiny input planes are read as 16-byte vectors. Flipout's rule is the
+// Reparameterization one restricted to what it instantiates: whole stride-1 rows (3) for the 256-wide tile, 1x1 planes (1) for the
+// 128-wide one.
+template <bool FLIP>
+static int split_x_mode(FwdArgs& a, int bm) {
+  if ((((uintptr_t)a.x) & 15u) || (a.x_sample_stride & 3)) return 0;
+  int xm = 0;
+  if (a.HW == 1) xm = 1;
+  else if (bm != 128 && !a.pixel_major && a.HW > 1 && (a.W & 3) == 0 && a.t_Wt == a.Wo && split_row_mode(a)) xm = split_row_mode(a);
+  else if constexpr (!FLIP) {
+    if (bm != 128 && !a.pixel_major && a.HW > 1 && split_plane_flat(a)) xm = 3, a.x_flat = 1;
+    else if (bm == 128 && !a.pixel_major && a.H == 2 && a.W == 2 && split_plane_flat(a)) xm = 2;   // whole 2x2 planes (a strided 3x3 down to 1x1 maps)
+    else if (bm != 512 && a.row_taps && a.H == 2 && a.W == 2 && a.KW == 3 && a.PW == 1 && a.SW == 1 && a.DW == 1) xm = 2;   // a row tile's patch is the whole 2x2 plane
+    else if (a.pixel_major && a.H == 2 && a.W == 2 && a.KH == 3 && a.KW == 3 && a.PH == 1 && a.PW == 1 && a.SH == 1 && a.SW == 1 && a.DH == 1 && a.DW == 1) xm = 2;
+  }
+  if constexpr (FLIP) {
+    if (bm == 256 ? !(xm == 3 && a.SH == 1 && a.SW == 1) : xm != 1) xm = 0;
+  }
+  return xm;
+}
+
+// The general split kernel's tile for one tile kind: the cheapest candidate width (split_geometry, split_tile_cost), the grid, the x
+// fetch mode and the decode's reciprocals. Fills `a` and returns BT_OK with (bm, xm), or 1 when no tile applies.
+template <bool FLIP>
+static int split_plan(FwdArgs& a, int mode, int* bm_out, int* xm_out) {
+  if (a.T > 9) return 1;   // at most 9 taps
+  const int Mdom = a.pixel_major ? a.B : a.M;
+  if (Mdom < 112) return 1;
+  a.n_tiles = (a.Cog + 63) / 64;
+  FwdArgs cand[3] = {a, a, a};
+  int live[3] = {0, 0, 0};
+  if constexpr (!FLIP) {
+    if (Mdom >= 512) live[0] = split_geometry<512>(cand[0]);
+  }
+  if (Mdom >= 256 && !(FLIP && a.pixel_major)) live[1] = split_geometry<256, FLIP>(cand[1]);
+  live[2] = split_geometry<128, FLIP>(cand[2]);
+  double cost[3];
+  for (int i = 0; i < 3; ++i) cost[i] = split_tile_cost(cand[i], live[i], kSplitWidths[i], split_synth<FLIP>(kSplitWidths[i]), split_fixed<FLIP>());
+  int pick = -1;
+  if constexpr (!FLIP) {
+    static const int force_bm = [] { const char* e = getenv("BT_FORCE_BM"); return e ? atoi(e) : 0; }();   // measurement knob: prefer this tile width where it is eligible
+    for (int i = 0; i < 3; ++i)
+      if (force_bm == kSplitWidths[i] && cost[i] < 1e30) pick = i;
+  }
+  for (int i = 0; i < 3 && pick < 0; ++i) {   // the widest tile that no narrower one beats
+    bool best = cost[i] < 1e30;
+    for (int j = i + 1; j < 3; ++j) best = best && cost[i] <= cost[j];
+    if (best) pick = i;
+  }
+  if (pick < 0) return 1;
+  const int bm = kSplitWidths[pick];
+  const long long per = (long long)a.G * a.n_tiles * a.S;
+  a = cand[pick];
+  if constexpr (!FLIP) {
+    // A 128-wide launch that offers at most one workgroup per two CUs (a training step's single sample; an MLP's wide first layer at 8
+    // samples) runs in 32-channel tiles instead: twice the workgroups, each drawing half the weights -- the chain of a workgroup of such a
+    // layer IS its weight synthesis. The K order does not depend on the channel tile, so the results are the same bits (and the choice may
+    // depend on S). BT_BN32 = 0 | 1 forces it off / on where eligible (tests, measurement).
+    a.bn32 = 0;
+    if (bm == 128 && mode != 2 && a.Cog > 32) {
+      const int forced = g_bn32.get();
+      a.bn32 = forced >= 0 ? forced : (2 * per * a.m_tiles <= 256 ? 1 : 0);
+    }
+    if (a.bn32) a.n_tiles = (a.Cog + 31) / 32;
+  }
+  if (!set_grid(a, (long long)a.G * a.n_tiles * a.S * a.m_tiles)) return 1;
+  *bm_out = bm, *xm_out = split_x_mode<FLIP>(a, bm);
+  split_fill_inverses(a);
+  return BT_OK;
 }
 
 }  // namespace bt

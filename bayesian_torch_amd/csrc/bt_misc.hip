@@ -1,6 +1,8 @@
 // Version / error plumbing, the RNG materialisation hooks and the MC epilogue.
 #include <string.h>
 
+#include <atomic>
+
 #include "bt_api_internal.h"
 
 namespace bt {
@@ -12,6 +14,9 @@ void note_kernel(const char* name) {
   strncpy(g_kname, name, sizeof(g_kname) - 1);
   g_kname[sizeof(g_kname) - 1] = 0;
 }
+
+static std::atomic<bool> g_plan_only{false};
+bool plan_only() { return g_plan_only.load(std::memory_order_relaxed); }
 
 int set_error(int code, const char* msg) {
   strncpy(g_err, msg, sizeof(g_err) - 1);
@@ -282,3 +287,8 @@ extern "C" int bt_debug_poison_lds(void* scratch_word, bt_stream_t stream) {
   return launch_kernel(poison_lds_kernel, nullptr, "bt_debug_poison_lds", dim3(1024), dim3(1024), 160 * 1024, 160 * 1024, (hipStream_t)stream,
                        (unsigned*)scratch_word);
 }
+
+// Test seam (not part of include/bt_hip.h): while on, launch_kernel records the kernel name and returns BT_OK without touching the
+// runtime, so the host dispatch -- eligibility, tile plan, instantiation choice -- runs on a machine without a GPU
+// (tools/record_split_plans.py, tests/test_split_plan_parity.py). Off by default.
+extern "C" void bt_debug_plan_only(int on) { bt::g_plan_only.store(on != 0, std::memory_order_relaxed); }

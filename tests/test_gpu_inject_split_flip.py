@@ -122,10 +122,10 @@ ROWS = {
     "flip Linear 512->256 (xm=1)": ("linear", 512, 256, 1, 1, 0, 1, 1, 1, 1, 128, 2, True, False, N128_1),
 }
 MAY_BE_GENERAL = ("one tap", "3x3 s2")       # the rows the existing suite allows to be ineligible for the split Flipout
-# Six of the seven instantiations can be launched. launch_split_flip_one selects <64,128,xm=2> only for PIXEL-MAJOR 128-wide tiles of
-# 2x2 maps, and such a tile holds >= 112 images x the 4 patch pixels of a plane = 448 pixels, more than the 301 the two weight images
-# leave in LDS: split_geometry declines, the launch falls to whole-image tiles (xm=0). The instantiation exists (it is in the
-# dispatch table) and nothing reaches it; DESIGN.md section 4.0c says so.
+# All six instantiations can be launched. A seventh, <64,128,xm=2> (whole 2x2 planes, as Reparameterization has it), is NOT
+# instantiated: it would serve only PIXEL-MAJOR 128-wide tiles of 2x2 maps, and such a tile holds >= 112 images x the 4 patch pixels
+# of a plane = 448 pixels, more than the 301 the two weight images leave in LDS: split_geometry declines, the launch falls to
+# whole-image tiles (xm=0). DESIGN.md section 4.0c says so; the name stays here so that nothing starts to report it.
 REACHABLE = {N256_3, N256_0, N128_0, N128_1, Q0, Q1}
 
 
