@@ -52,12 +52,22 @@ def _kl_grads_aten(mu, rho, pm, ps, g, kind):
     return (mu - pm) / (ps * ps) * (g / n), (sq / (ps * ps) - 1.0 / sq) * torch.sigmoid(rho) * (g / n)
 
 
+_CONTROL_KEYS = ("kl", "kl_stub", "defer", "layer")      # of FusedForward's opts; every other key is a keyword of fused_forward
+_BACKWARD_KEYS = ("flip", "conv", "S", "shared_x", "eps_w", "sign_in", "sign_out", "seed", "call", "layer_id", "sample0", "call_base")
+
+
+def _backward_kw(o):
+    """The keywords of ``functional.fused_backward`` among the forward's (FusedForward's opts): geometry, draws, RNG coordinates."""
+    return {k: o[k] for k in _BACKWARD_KEYS if k in o}
+
+
 class FusedForward(torch.autograd.Function):
     """out[S*B, ...] = fused stochastic forward; differentiable in x, mu_w, rho_w, mu_b, rho_b."""
 
     @staticmethod
     def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, opts):
-        """opts["kl"] = (prior_mu_w, prior_sigma_w, prior_mu_b, prior_sigma_b, kind): the layer's KL term rides along -- computed by
+        """opts: ``functional.fused_forward``'s keywords (layers/_fused.py: _launch_kw) plus the control keys below.
+        opts["kl"] = (prior_mu_w, prior_sigma_w, prior_mu_b, prior_sigma_b, kind): the layer's KL term rides along -- computed by
         the forward kernel's fused sweep, returned as a second differentiable output, and differentiated inside wgrad's finishing
         pass (bt_conv2d_bwd_kl): a training step then has no KL launches and no KL-gradient tensors for autograd to add.
         opts["kl_stub"]: the second output is a placeholder -- at ONE sample a layer's launch has a handful of workgroups and the fused
@@ -66,14 +76,12 @@ class FusedForward(torch.autograd.Function):
         opts["defer"] (a list; mc.TrainGraph): the weight gradients are computed on a side stream beside the dgrad chain and handed
         over through the list -- (layer, dmu, drho) -- instead of through autograd; ``mc.finish_deferred`` joins and assigns them."""
         o = dict(opts)
+        o.setdefault("workspace_owner", ("layer", o["layer_id"]))
         klo = o.get("kl")
         stub = klo is not None and bool(o.get("kl_stub"))
-        out, kl = F.fused_forward(x, mu_w, rho_w, mu_b, rho_b, flip=o["flip"], conv=o["conv"], S=o["S"], shared_x=o["shared"],
-                                  seed=o["seed"], call=o["call"], layer_id=o["layer_id"], sample0=o["sample0"],
-                                  eps_w=o.get("eps_w"), eps_b=o.get("eps_b"), sign_in=o.get("sign_in"), sign_out=o.get("sign_out"),
-                                  packed=o.get("packed"), workspace_owner=o.get("workspace_owner", ("layer", o["layer_id"])), call_base=o.get("call_base"),
-                                  priors=None if (klo is None or stub) else tuple(klo[:4]), want_kl=klo is not None and not stub,
-                                  prior_type="normal" if klo is None else klo[4],
+        fwd_kw = {k: v for k, v in o.items() if k not in _CONTROL_KEYS}      # opts speaks fused_forward's keywords
+        out, kl = F.fused_forward(x, mu_w, rho_w, mu_b, rho_b, **fwd_kw, priors=None if (klo is None or stub) else tuple(klo[:4]),
+                                  want_kl=klo is not None and not stub, prior_type="normal" if klo is None else klo[4],
                                   inject_path="general")      # (rng.set_inject_path covers inference; a training forward keeps its kernel)
         if stub:      # the VALUE comes from one launch over the whole model (KLValue, get_kl_loss); this output only routes its gradient here
             kl = out.new_empty(())
@@ -87,7 +95,7 @@ class FusedForward(torch.autograd.Function):
     def backward(ctx, g, g_kl=None):
         x, mu_w, rho_w, mu_b, rho_b = ctx.saved_tensors
         o = ctx.o
-        S, shared, conv, flip = o["S"], o["shared"], o["conv"], o["flip"]
+        S, shared, conv, flip = o["S"], o["shared_x"], o["conv"], o["flip"]
         dev = x.device
         g = torch.zeros(ctx.out_shape, dtype=torch.float32, device=dev) if g is None else g.contiguous()
         B = x.shape[0] // (1 if shared else S)
@@ -98,8 +106,7 @@ class FusedForward(torch.autograd.Function):
             need_x = ctx.needs_input_grad[0]
             need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
             packed = o.get("packed") or F.pack_params(mu_w.detach(), rho_w.detach())
-            kw = dict(flip=flip, conv=conv, S=S, shared_x=shared, eps_w=o.get("eps_w"), sign_in=o.get("sign_in"), sign_out=o.get("sign_out"),
-                      seed=o["seed"], call=o["call"], layer_id=o["layer_id"], sample0=o["sample0"], call_base=o.get("call_base"))
+            kw = _backward_kw(o)
             kl_arg = None if klo is None else (g_kl, klo[0], klo[1], klo[4])
             defer = o.get("defer")
             if defer is not None and need_w:

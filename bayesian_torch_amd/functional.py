@@ -1,6 +1,7 @@
-"""Functional form of the four fused forwards: tensors in, one C-ABI call, tensors out.
-The layer modules (layers/_fused.py) are thin wrappers over ``fused_forward``."""
+"""Functional form of the four fused forwards and of their backward: tensors in, C-ABI calls, tensors out.  The layer modules
+(layers/_fused.py, _family.py) add the MC frame, the call coordinates, the pack check and the KL wiring on top of ``fused_forward``."""
 import ctypes as C
+import math
 
 import torch
 
@@ -31,6 +32,87 @@ def maxpool_3x3s2(x):
     with _lib.on(x.device):
         _lib.check(_lib.lib().bt_maxpool_3x3s2(x.data_ptr(), out.data_ptr(), N * Cc, H, W, _lib.stream_ptr(x.device)))
     return out
+
+
+def _geometry(x, mu_w, conv, S, shared_x):
+    """-> (B, the launch's bt_conv2d_geom -- Linear as the 1 x 1 convolution --, one sample's x elements, the contraction's output tail)."""
+    per = 1 if shared_x else S
+    if x.shape[0] % per:
+        raise RuntimeError("stacked input rows are not a multiple of S")
+    B, Co = x.shape[0] // per, mu_w.shape[0]
+    if conv is None:
+        In = mu_w.shape[1]
+        if x.dim() != 2 or x.shape[1] != In:
+            raise RuntimeError(f"expected [N, {In}] input, got {tuple(x.shape)}")
+        return B, _lib.bt_conv2d_geom(B, In, 1, 1, Co, 1, 1, 1, 1, 0, 0, 1, 1, 1), x.numel() // per, (Co,)
+    kh, kw = mu_w.shape[2], mu_w.shape[3]
+    (sh, sw), (ph, pw), (dh, dw), groups = conv["stride"], conv["padding"], conv["dilation"], conv["groups"]
+    Ci, H, W = x.shape[1], x.shape[2], x.shape[3]
+    if Ci != mu_w.shape[1] * groups:
+        raise RuntimeError(f"input has {Ci} channels, weight expects {mu_w.shape[1] * groups}")
+    Ho, Wo = conv_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw)
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError("convolution output would be empty")
+    return B, _lib.bt_conv2d_geom(B, Ci, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, groups), x.numel() // per, (Co, Ho, Wo)
+
+
+def _split_inject_wanted(tens, flip, S, x_elems, n_so, inject_path, state, geo_key):
+    """Injected draws on the split-precision kernels: packed parameters and a whole draw (eps_b exactly when biased; Flipout: both sign
+    tensors, Reparameterization: none), of a geometry the caller's state does not remember as declined."""
+    ok = ((rng.get_inject_path() if inject_path is None else inject_path) == "split" and tens["eps_w"] is not None
+          and tens["mu_packed"] is not None and tens["eps_w"].numel() == S * tens["mu_w"].numel()
+          and (tens["mu_b"] is None) == (tens["eps_b"] is None))
+    if ok and flip:
+        ok = (tens["sign_in"] is not None and tens["sign_out"] is not None and tens["sign_in"].numel() == S * x_elems
+              and tens["sign_out"].numel() == S * n_so)
+    elif ok:
+        ok = tens["sign_in"] is None and tens["sign_out"] is None
+    return ok and not (state is not None and geo_key in state.setdefault("declined", set()))
+
+
+def _pack_supplied_draw(tens, flip, S, x_elems, n_so, R, state):
+    """Re-lay a whole supplied draw for the split-precision kernels (bt_pack_eps; Flipout: + two bt_pack_signs) -> the packed bt_draws.
+    The buffers are the caller's state's ("buf", "sign_in_buf", "sign_out_buf", "sign_count"), made again only when too small."""
+    L, mu_w = _lib.lib(), tens["mu_w"]
+    dev, st = mu_w.device, {} if state is None else state
+
+    def buffer(key, n, dtype):
+        buf = st.get(key)
+        if buf is None or buf.numel() < n or buf.device != dev:
+            buf = st[key] = torch.empty(n, dtype=dtype, device=dev)
+        return buf
+
+    Co, Cig, taps = mu_w.shape[0], mu_w.shape[1], mu_w[0, 0].numel()
+    eps_pk = buffer("buf", S * Co * taps * ((Cig + 3) // 4 * 4), torch.float32)
+    with _lib.on(dev):
+        _lib.check(L.bt_pack_eps(tens["eps_w"].data_ptr(), S, Co, Cig, taps, eps_pk.data_ptr(), _lib.stream_ptr(dev)))
+    sg_pk = [None, None]
+    if flip:      # the two sign tensors as byte images; the pass leaves its count of elements that are not +-1 in the state's counter
+        cnt = st.get("sign_count")
+        if cnt is None or cnt.device != dev:
+            cnt = st["sign_count"] = torch.zeros(2, dtype=torch.int32, device=dev)
+        for i, (key, n) in enumerate((("sign_in", x_elems), ("sign_out", n_so))):
+            sg_pk[i] = buffer(key + "_buf", S * _lib.signs_packed_stride(n), torch.uint8)
+            with _lib.on(dev):
+                _lib.check(L.bt_pack_signs(tens[key].data_ptr(), S, n, sg_pk[i].data_ptr(), cnt.data_ptr() + 4 * i, _lib.stream_ptr(dev)))
+    Rp = _lib.bt_rng(R.seed, R.call_base_dev, R.call, R.layer_id, R.sample0, _lib.DRAWS_EPS_PACKED | (_lib.DRAWS_SIGNS_PACKED if flip else 0))
+    return _lib.bt_draws(eps_pk.data_ptr(), _lib.ptr(tens["eps_b"]), _lib.ptr(sg_pk[0]), _lib.ptr(sg_pk[1]), Rp)
+
+
+def _epilogue(tens, out, S, relu, pool):
+    """The fused output stage as a bt_epilogue reference, or None when the launch has none."""
+    scale, shift, res = tens["post_scale"], tens["post_shift"], tens["residual"]
+    if scale is None and res is None and not relu and not pool:
+        return None
+    rstride, Co = 0, out.shape[1]
+    if res is not None:
+        if res.numel() == out.numel():
+            rstride = out.numel() // S
+        elif res.numel() * S != out.numel():
+            raise RuntimeError(f"residual has {res.numel()} elements, out has {out.numel()} (S={S})")
+    if scale is not None and (scale.numel() != Co or shift is None or shift.numel() != Co):
+        raise RuntimeError("post_scale / post_shift must both have Co elements")
+    return C.byref(_lib.bt_epilogue(_lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res), rstride, 1 if relu else 0, 1 if pool else 0))
 
 
 def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=None, S=1, shared_x=True,
@@ -64,108 +146,43 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
         if t is not None and t.device != dev:
             raise RuntimeError(f"{k} on {t.device} but input on {dev}")
         tens[k] = t
-    if x.shape[0] % (1 if shared_x else S):
-        raise RuntimeError("stacked input rows are not a multiple of S")
-    B = x.shape[0] // (1 if shared_x else S)
-    Co = mu_w.shape[0]
-    if conv is None:
-        In = mu_w.shape[1]
-        if x.dim() != 2 or x.shape[1] != In:
-            raise RuntimeError(f"expected [N, {In}] input, got {tuple(x.shape)}")
-        tail = (Co,)
-    else:
-        kh, kw = mu_w.shape[2], mu_w.shape[3]
-        (sh, sw), (ph, pw), (dh, dw), groups = conv["stride"], conv["padding"], conv["dilation"], conv["groups"]
-        Ci, H, W = x.shape[1], x.shape[2], x.shape[3]
-        if Ci != mu_w.shape[1] * groups:
-            raise RuntimeError(f"input has {Ci} channels, weight expects {mu_w.shape[1] * groups}")
-        Ho, Wo = conv_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw)
-        if Ho <= 0 or Wo <= 0:
-            raise RuntimeError("convolution output would be empty")
-        tail = (Co, Ho, Wo)
-        geom = _lib.bt_conv2d_geom(B, Ci, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, groups)
-    x_elems = x.numel() // (1 if shared_x else S)
+    B, geom, x_elems, tail = _geometry(x, mu_w, conv, S, shared_x)
+    n_so = B * math.prod(tail)      # one sample's contraction output, before any fused pooling
     if pool:
         if conv is None or residual is not None:
             raise RuntimeError("pool=True needs a Conv2d launch without residual")
-        tail = (Co, (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1)
+        tail = (tail[0], (tail[1] - 1) // 2 + 1, (tail[2] - 1) // 2 + 1)
     out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev)
     kl = ws = None
     pr = [None] * 4
     L = _lib.lib()
+    geo_key = (B, S, bool(shared_x), tuple(x.shape[1:]), None if conv is None else (*conv["stride"], *conv["padding"], *conv["dilation"], conv["groups"]),
+               bool(pool), residual is not None)
+    split_inj = _split_inject_wanted(tens, flip, S, x_elems, n_so, inject_path, eps_pack_state, geo_key)
     # layers whose output map is one pixel may run split over K-slices that meet in scratch behind the workspace (include/bt_hip.h)
-    gq = geom if conv is not None else _lib.bt_conv2d_geom(B, In, 1, 1, Co, 1, 1, 1, 1, 0, 0, 1, 1, 1)
-    # injected draws on the split-precision kernels: packed parameters, a whole draw (Flipout: with both sign tensors)
-    n_so = out.numel() // S if not pool else B * Co * Ho * Wo      # one sample's contraction output, before any fused pooling
-    split_inj = ((rng.get_inject_path() if inject_path is None else inject_path) == "split" and tens["eps_w"] is not None
-                 and packed is not None and tens["eps_w"].numel() == S * tens["mu_w"].numel()
-                 and (tens["mu_b"] is None) == (tens["eps_b"] is None))
-    if split_inj and flip:
-        split_inj = (tens["sign_in"] is not None and tens["sign_out"] is not None and tens["sign_in"].numel() == S * x_elems
-                     and tens["sign_out"].numel() == S * n_so)
-    elif split_inj:
-        split_inj = tens["sign_in"] is None and tens["sign_out"] is None
-    geo_key = (B, S, bool(shared_x), tuple(x.shape[1:]), None if conv is None else (sh, sw, ph, pw, dh, dw, groups), bool(pool), residual is not None)
-    if split_inj and eps_pack_state is not None and geo_key in eps_pack_state.setdefault("declined", set()):
-        split_inj = False
-    scratch = int(L.bt_fused_scratch_bytes(C.byref(gq), S)) if ((eps_w is None or split_inj) and not flip and packed is not None) else 0
-    if scratch:
-        ws = _lib.workspace(workspace_owner, dev, scratch)
+    scratch = int(L.bt_fused_scratch_bytes(C.byref(geom), S)) if ((eps_w is None or split_inj) and not flip and packed is not None) else 0
     if want_kl:
         if priors is None:
             raise ValueError("want_kl needs priors")
         pr = [_lib.dev_f32(t, "prior") for t in priors]
         kl = torch.empty((), dtype=torch.float32, device=dev)
+    if scratch or want_kl:
         ws = _lib.workspace(workspace_owner, dev, scratch)
     P = _lib.bt_params(tens["mu_w"].data_ptr(), tens["rho_w"].data_ptr(), _lib.ptr(tens["mu_b"]), _lib.ptr(tens["rho_b"]),
                        _lib.ptr(pr[0]), _lib.ptr(pr[1]), _lib.ptr(pr[2]), _lib.ptr(pr[3]), _lib.ptr(tens["mu_packed"]), _lib.ptr(tens["sigma_packed"]),
                        _lib.PRIOR_LAPLACE if prior_type == "laplace" else _lib.PRIOR_NORMAL, 0)
-    R = _lib.bt_rng(int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(call_base), int(call) & 0xFFFFFFFF, int(layer_id), int(sample0), 0)
-    D = _lib.bt_draws(_lib.ptr(tens["eps_w"]), _lib.ptr(tens["eps_b"]), _lib.ptr(tens["sign_in"]), _lib.ptr(tens["sign_out"]), R)
-    D_nat = D
+    R = _rng(seed, call, layer_id, sample0, call_base)
+    D = D_nat = _lib.bt_draws(_lib.ptr(tens["eps_w"]), _lib.ptr(tens["eps_b"]), _lib.ptr(tens["sign_in"]), _lib.ptr(tens["sign_out"]), R)
     if split_inj:
-        Cig, taps = mu_w.shape[1], mu_w[0, 0].numel()
-        n_pk = S * Co * taps * ((Cig + 3) // 4 * 4)
-        eps_pk = None if eps_pack_state is None else eps_pack_state.get("buf")
-        if eps_pk is None or eps_pk.numel() < n_pk or eps_pk.device != dev:
-            eps_pk = torch.empty(n_pk, dtype=torch.float32, device=dev)
-            if eps_pack_state is not None:
-                eps_pack_state["buf"] = eps_pk
-        with _lib.on(dev):
-            _lib.check(L.bt_pack_eps(tens["eps_w"].data_ptr(), S, Co, Cig, taps, eps_pk.data_ptr(), _lib.stream_ptr(dev)))
-        sg_pk = [None, None]
-        if flip:      # the two sign tensors as byte images; the pass leaves its count of elements that are not +-1 in the state's counter
-            st = {} if eps_pack_state is None else eps_pack_state
-            cnt = st.get("sign_count")
-            if cnt is None or cnt.device != dev:
-                cnt = st["sign_count"] = torch.zeros(2, dtype=torch.int32, device=dev)
-            for i, (key, n) in enumerate((("sign_in", x_elems), ("sign_out", n_so))):
-                nb = S * _lib.signs_packed_stride(n)
-                buf = st.get(key + "_buf")
-                if buf is None or buf.numel() < nb or buf.device != dev:
-                    buf = st[key + "_buf"] = torch.empty(nb, dtype=torch.uint8, device=dev)
-                with _lib.on(dev):
-                    _lib.check(L.bt_pack_signs(tens[key].data_ptr(), S, n, buf.data_ptr(), cnt.data_ptr() + 4 * i, _lib.stream_ptr(dev)))
-                sg_pk[i] = buf
-        Rp = _lib.bt_rng(R.seed, R.call_base_dev, R.call, R.layer_id, R.sample0, _lib.DRAWS_EPS_PACKED | (_lib.DRAWS_SIGNS_PACKED if flip else 0))
-        D = _lib.bt_draws(eps_pk.data_ptr(), _lib.ptr(tens["eps_b"]), _lib.ptr(sg_pk[0]), _lib.ptr(sg_pk[1]), Rp)
-    E = None
-    if tens["post_scale"] is not None or tens["residual"] is not None or relu or pool:
-        res, rstride = tens["residual"], 0
-        if res is not None:
-            if res.numel() == out.numel():
-                rstride = out.numel() // S
-            elif res.numel() * S != out.numel():
-                raise RuntimeError(f"residual has {res.numel()} elements, out has {out.numel()} (S={S})")
-        if tens["post_scale"] is not None and (tens["post_scale"].numel() != Co or tens["post_shift"] is None or tens["post_shift"].numel() != Co):
-            raise RuntimeError("post_scale / post_shift must both have Co elements")
-        E = C.byref(_lib.bt_epilogue(_lib.ptr(tens["post_scale"]), _lib.ptr(tens["post_shift"]), _lib.ptr(res), rstride, 1 if relu else 0, 1 if pool else 0))
+        D = _pack_supplied_draw(tens, flip, S, x_elems, n_so, R, eps_pack_state)
+    E = _epilogue(tens, out, S, relu, pool)
+
     def launch(draws):
         tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), C.byref(draws), E, out.data_ptr(), _lib.ptr(kl), _lib.ptr(ws),
                      ws.numel() if ws is not None else 0, _lib.stream_ptr(dev))
         if conv is None:
             fn = L.bt_flipout_linear_fwd if flip else L.bt_reparam_linear_fwd
-            return fn(B, In, Co, S, *tail_args)
+            return fn(B, geom.Ci, geom.Co, S, *tail_args)
         fn = L.bt_flipout_conv2d_fwd if flip else L.bt_reparam_conv2d_fwd
         return fn(C.byref(geom), S, *tail_args)
 
@@ -248,6 +265,17 @@ def _kl_entry(kl):
     return _lib.bt_pack_kl(pm.data_ptr(), ps.data_ptr(), *[_lib.ptr(t) for t in b], out.data_ptr(), n_bias), (pm, ps, b, out)
 
 
+def _pack_sync_launch(arr, karr, owner, dev):
+    """One bt_pack_sync call over the marshalled segments ``arr``; with ``karr`` (their bt_pack_kl entries) bt_pack_sync_kl."""
+    L = _lib.lib()
+    with _lib.on(dev):
+        ws = _lib.workspace((owner, "pack"), dev).data_ptr()
+        if karr is None:
+            _lib.check(L.bt_pack_sync(len(arr), arr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+        else:
+            _lib.check(L.bt_pack_sync_kl(len(arr), arr, karr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+
+
 def pack_sync(segments, owner="pack", kls=None):
     """segments: list of dict(mu, rho, src_mu|None, src_rho|None, mu_packed, sigma_packed, state, Co, Ci, taps, force) on ONE device.
     Re-packs, ON THE DEVICE and in the current stream, exactly the layers whose (mu, rho) no longer match the fingerprint their pack
@@ -257,21 +285,13 @@ def pack_sync(segments, owner="pack", kls=None):
     layer's forward can go without its own KL sweep."""
     if not segments:
         return
-    L = _lib.lib()
     dev = segments[0]["mu"].device
     if kls is not None and all(k is None for k in kls):
         kls = None
     if len(segments) == 1 and "_c" in segments[0]:      # a layer checking itself again: its marshalled entry is still valid (same tensors, same buffers)
         arr = segments[0]["_c"][0]
         arr[0].force = 1 if segments[0].get("force") else 0
-        with _lib.on(dev):
-            ws = _lib.workspace((owner, "pack"), dev).data_ptr()
-            if kls is None:
-                _lib.check(L.bt_pack_sync(1, arr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
-            else:
-                karr = (_lib.bt_pack_kl * 1)(_kl_entry(kls[0])[0])
-                _lib.check(L.bt_pack_sync_kl(1, arr, karr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
-        return
+        return _pack_sync_launch(arr, None if kls is None else (_lib.bt_pack_kl * 1)(_kl_entry(kls[0])[0]), owner, dev)
     for c0 in range(0, len(segments), _lib.PACK_MAX_SEGMENTS):
         chunk = segments[c0:c0 + _lib.PACK_MAX_SEGMENTS]
         kchunk = None if kls is None else kls[c0:c0 + _lib.PACK_MAX_SEGMENTS]
@@ -297,12 +317,7 @@ def pack_sync(segments, owner="pack", kls=None):
                 keep.append(kept)
         if len(segments) == 1:
             segments[0]["_c"] = (arr, keep[:1])
-        with _lib.on(dev):
-            ws = _lib.workspace((owner, "pack"), dev).data_ptr()
-            if karr is None:
-                _lib.check(L.bt_pack_sync(len(chunk), arr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
-            else:
-                _lib.check(L.bt_pack_sync_kl(len(chunk), arr, karr, ws, _lib.WORKSPACE_BYTES, _lib.stream_ptr(dev)))
+        _pack_sync_launch(arr, karr, owner, dev)
 
 
 def mc_epilogue(logits):
@@ -325,14 +340,7 @@ def fused_backward(x, grad_out, mu_w, rho_w, packed, *, flip=False, conv=None, S
     x, g = _lib.dev_f32(x, "input"), _lib.dev_f32(grad_out, "grad_out")
     dev = x.device
     mu_w, rho_w = _lib.dev_f32(mu_w, "mu_w"), _lib.dev_f32(rho_w.detach(), "rho_w")
-    B = x.shape[0] // (1 if shared_x else S)
-    Co = mu_w.shape[0]
-    if conv is None:
-        geom = _lib.bt_conv2d_geom(B, mu_w.shape[1], 1, 1, Co, 1, 1, 1, 1, 0, 0, 1, 1, 1)
-    else:
-        (sh, sw), (ph, pw), (dh, dw), groups = conv["stride"], conv["padding"], conv["dilation"], conv["groups"]
-        geom = _lib.bt_conv2d_geom(B, x.shape[1], x.shape[2], x.shape[3], Co, mu_w.shape[2], mu_w.shape[3], sh, sw, ph, pw, dh, dw, groups)
-    x_elems = x.numel() // (1 if shared_x else S)
+    B, geom, x_elems, _ = _geometry(x, mu_w, conv, S, shared_x)
     dx = torch.empty((S,) + (B,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev) if need_x else None
     dmu = torch.empty_like(mu_w) if need_w else None
     drho = torch.empty_like(mu_w) if need_w else None

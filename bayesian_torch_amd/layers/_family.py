@@ -22,7 +22,7 @@ taken by the standalone KL kernel on the parameters in their own layout.
 import torch
 import torch.nn.functional as TF
 
-from .. import _lib, mc, rng
+from .. import _lib, rng
 from .. import functional as F
 from ._fused import FusedBayesLayer
 from .base_variational_layer import get_kernel_size
@@ -139,60 +139,32 @@ class FamilyConvLayer(FusedBayesLayer):
             t = t.reshape(L + (g, Co // g, Cig) + ks).transpose(lead + 1, lead + 2).reshape(L + (g * Cig, Co // g) + ks)
         return t.contiguous()
 
+    _sign_keys = ("sign_in_eq", "sign_out_eq")
+
+    def _supplied_draw(self, d, S):
+        return dict(d, eps_w=self._w_nat(d["eps_w"], lead=1))
+
     def materialize_last_draw(self):
         """The last forward's draw in the REFERENCE's layouts where one exists: eps_w [S, *kernel], eps_b [S, Co]. The on-chip
         Flipout signs are defined over the Conv2d launch's operands (``sign_in_eq`` / ``sign_out_eq``: the re-arranged x and the
         launch's output): a transposed convolution's zero-upsampled x carries one sign per real element like the reference, Conv3d's
         depth-unfolded x one sign per (element, depth window) -- see DESIGN.md 4.6."""
-        if self._last is None:
-            raise RuntimeError("no forward has run yet")
-        st = self._last
-        if st["draw"] is not None:
-            d = dict(st["draw"])
-            d["eps_w"] = self._w_nat(d["eps_w"], lead=1)
-            return d
-        seed, call_base, call, lid, sample0 = st["rng"]
-        if call_base is not None:
-            raise RuntimeError("draws made under a graph call_base cannot be replayed after the word advanced")
-        dev, S = self._w("mu").device, st["S"]
-        res = dict(eps_w=self._w_nat(F.rng_fill_normal(seed, call, lid, sample0, 0, S, st["w_eq_shape"], dev), lead=1))
-        if self.mu_bias is not None:
-            res["eps_b"] = F.rng_fill_normal(seed, call, lid, sample0, 1, S, (self.out_channels,), dev)
-        if self._flip:
-            res["sign_in_eq"] = F.rng_fill_sign(seed, call, lid, sample0, 2, S, st["x_shape"], dev)
-            res["sign_out_eq"] = F.rng_fill_sign(seed, call, lid, sample0, 3, S, st["out_shape"], dev)
-        return res
+        return super().materialize_last_draw()
 
     # ------------------------------------------------------------------ forward
     def forward(self, input, return_kl=True):
         if self.post_scale is not None or self.post_shift is not None or self.post_relu or self.post_pool:
             raise RuntimeError(f"{type(self).__name__} has no fused output stage: post_scale / post_shift / post_relu / post_pool must stay unset")
-        if self.dnn_to_bnn_flag:
-            return_kl = False
-        ctx = mc.current()
-        collect = ctx is not None and ctx.collect_kl
-        want_kl = return_kl or collect
+        ctx, collect, want_kl, return_kl = self._mc_frame(return_kl)
         x = _lib.dev_f32(input, "input")
         if x.dim() != self._nd + 2 or x.shape[1] != self.in_channels:
             raise RuntimeError(f"{type(self).__name__}: expected [N, {self.in_channels}, {self._nd} spatial dims], got {tuple(x.shape)}")
-        if ctx is None:
-            S, shared = 1, True
-        else:
-            S = ctx.S
-            if x.shape[0] == ctx.batch:
-                shared = True
-            elif x.shape[0] == S * ctx.batch:
-                shared = False
-            else:
-                raise RuntimeError(f"inside mc_samples(S={S}, batch={ctx.batch}) a Bayesian layer got batch {x.shape[0]}")
-        sample0 = 0 if ctx is None else ctx.sample0
-        call_base = None if ctx is None else ctx.call_base
-        call, seed = rng.next_call(), rng.seed()
+        S, shared, coords = self._call_coords(ctx, x.shape[0])
         xe, conv, back = self._x_eq(x)
         mu_e, rho_e = self._w_eq(self._w("mu")), self._w_eq(self._w("rho"))
         draw = {}
-        if self.inject_draw is not None:           # draws in the reference's layouts (test hook), re-arranged like the operands
-            inj = self.inject_draw.pop(0) if isinstance(self.inject_draw, list) else self.inject_draw
+        inj = self._take_injected()
+        if inj is not None:           # draws in the reference's layouts (test hook), re-arranged like the operands
             draw["eps_w"] = self._w_eq(inj["eps_w"], lead=1)
             if inj.get("eps_b") is not None:
                 draw["eps_b"] = inj["eps_b"]
@@ -205,17 +177,13 @@ class FamilyConvLayer(FusedBayesLayer):
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad:
             from ..autograd import FusedForward
-            if call_base is not None:
+            if coords.call_base is not None:
                 raise RuntimeError("graph-replayed draws (call_base) are not supported on the training path")
-            opts = dict(flip=self._flip, conv=conv, S=S, shared=shared, seed=seed, call=call, layer_id=self._layer_id, sample0=sample0,
-                        eps_w=draw.get("eps_w"), eps_b=draw.get("eps_b"), sign_in=draw.get("sign_in"), sign_out=draw.get("sign_out"), packed=self._packed())
-            out = FusedForward.apply(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, opts)
+            out = FusedForward.apply(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, self._launch_kw(conv, S, shared, coords, draw, self._packed()))
         else:
-            out, _ = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, flip=self._flip, conv=conv, S=S, shared_x=shared,
-                                     eps_w=draw.get("eps_w"), eps_b=draw.get("eps_b"), sign_in=draw.get("sign_in"), sign_out=draw.get("sign_out"),
-                                     seed=seed, call=call, layer_id=self._layer_id, sample0=sample0, call_base=call_base, packed=self._packed())
+            out, _ = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, draw, self._packed()))
         Be = xe.shape[0] // (1 if shared else S)
-        self._last = dict(draw=draw or None, rng=(seed, call_base, call, self._layer_id, sample0), S=S, kernel=_lib.lib().bt_last_kernel_name().decode(),
+        self._last = dict(draw=draw or None, rng=coords, S=S, kernel=_lib.lib().bt_last_kernel_name().decode(),
                           w_eq_shape=tuple(mu_e.shape), x_shape=(Be,) + tuple(xe.shape[1:]), out_shape=(Be,) + tuple(out.shape[1:]))
         out = back(out).contiguous()
         kl = self.kl_loss() if want_kl else None

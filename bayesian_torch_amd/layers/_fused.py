@@ -6,9 +6,10 @@ Reference behaviour reproduced (paths under /root/reference/bayesian_torch/layer
   forward(input, return_kl=True)  linear_variational.py:160-204, conv_variational.py:362-407,
                                   flipout_layers/linear_flipout.py:145-197, conv_flipout.py:370-439
   kl_loss()                       linear_variational.py:146-158
-Training: the same fused forward; gradients come from the autograd bridge (autograd.py: draws regenerated from the RNG
-coordinates, ATen conv/matmul backward) -- a fused HIP backward is the next step.
+Training: the same fused forward; gradients come from the autograd bridge (autograd.py: the HIP backward kernels of
+csrc/bt_bwd.hip regenerate the draws from the RNG coordinates; an ATen checker path stays for the tests).
 """
+import collections
 import ctypes as C
 import warnings
 
@@ -20,6 +21,7 @@ from .. import functional as F
 from .base_variational_layer import BaseVariationalLayer_, check_prior_type, get_kernel_size
 
 _warned = [False]
+Coords = collections.namedtuple("Coords", "seed call_base call layer_id sample0")      # a call's RNG coordinates: ``_last["rng"]``
 
 
 import os as _os
@@ -232,15 +234,42 @@ class FusedBayesLayer(BaseVariationalLayer_):
         return dict(stride=get_kernel_size(self.stride, 2), padding=get_kernel_size(pad, 2),
                     dilation=get_kernel_size(self.dilation, 2), groups=self.groups)
 
-    def _forward(self, x, return_kl=True, residual=None):
+    # (the four helpers below serve this class's _forward and layers/_family.py's forward alike)
+    def _mc_frame(self, return_kl):
+        """-> (the mc_samples context or None, whether it collects KL terms, whether this call needs its KL, return_kl as honoured)."""
         if self.dnn_to_bnn_flag:
             return_kl = False
         ctx = mc.current()
         collect = ctx is not None and ctx.collect_kl
-        want_kl = return_kl or collect
+        return ctx, collect, return_kl or collect, return_kl
+
+    def _call_coords(self, ctx, rows):
+        """The sample axis of an input of ``rows`` rows, and -- only now, so that a refused input consumes none -- this call's RNG
+        coordinates -> (S, whether x is shared by the samples, Coords)."""
+        S, shared = 1, True
+        if ctx is not None:
+            S = ctx.S
+            if rows != ctx.batch and rows != S * ctx.batch:
+                raise RuntimeError(f"inside mc_samples(S={S}, batch={ctx.batch}) a Bayesian layer got batch {rows}")
+            shared = rows == ctx.batch
+        call, seed = rng.next_call(), rng.seed()
+        return S, shared, Coords(seed, None if ctx is None else ctx.call_base, call, self._layer_id, 0 if ctx is None else ctx.sample0)
+
+    def _take_injected(self):
+        """The supplied draw of this call (test hook ``inject_draw``; a list feeds successive calls), or None."""
+        return self.inject_draw.pop(0) if isinstance(self.inject_draw, list) else self.inject_draw
+
+    def _launch_kw(self, conv, S, shared, coords, draw, packed):
+        """The keywords of ``functional.fused_forward`` that inference and training launches (``FusedForward``'s opts) have in common."""
+        return dict(flip=self._flip, conv=conv, S=S, shared_x=shared, seed=coords.seed, call=coords.call, layer_id=coords.layer_id,
+                    sample0=coords.sample0, call_base=coords.call_base, packed=packed, **draw)
+
+    def _forward(self, x, return_kl=True, residual=None):
+        ctx, collect, want_kl, return_kl = self._mc_frame(return_kl)
         kind = self._prior_kind() if want_kl else "normal"
         x = _lib.dev_f32(x, "input")
         lead = None
+        one_d = getattr(self, "_one_d", False)
         if self._kind == "linear":
             if x.shape[-1] != self.in_features:
                 raise RuntimeError(f"{type(self).__name__}: expected last dim {self.in_features}, got {tuple(x.shape)}")
@@ -251,7 +280,6 @@ class FusedBayesLayer(BaseVariationalLayer_):
                 x = x.reshape(-1, self.in_features)
             conv = None
         else:
-            one_d = getattr(self, "_one_d", False)
             if one_d:
                 if x.dim() != 3 or x.shape[1] != self.in_channels:
                     raise RuntimeError(f"{type(self).__name__}: expected [N, {self.in_channels}, L], got {tuple(x.shape)}")
@@ -261,27 +289,13 @@ class FusedBayesLayer(BaseVariationalLayer_):
             conv = self._conv_desc()
         if x.shape[0] == 0:
             raise RuntimeError("empty batch")
-        if ctx is None:
-            S, shared = 1, True
-        else:
-            S = ctx.S
-            if x.shape[0] == ctx.batch:
-                shared = True
-            elif x.shape[0] == S * ctx.batch:
-                shared = False
-            else:
-                raise RuntimeError(f"inside mc_samples(S={S}, batch={ctx.batch}) a Bayesian layer got batch {x.shape[0]}")
+        S, shared, coords = self._call_coords(ctx, x.shape[0])
         B = x.shape[0] // (1 if shared else S)
-        one_d = getattr(self, "_one_d", False)
         mu_t, rho_t = self._w("mu"), self._w("rho")
         if one_d:                      # [Co, Ci/g, k] -> [Co, Ci/g, 1, k] (views: same storage, autograd flows through)
             mu_t, rho_t = mu_t.unsqueeze(2), rho_t.unsqueeze(2)
-
-        sample0 = 0 if ctx is None else ctx.sample0
-        call_base = None if ctx is None else ctx.call_base
-        call, seed = rng.next_call(), rng.seed()
-        if self.inject_draw is not None:
-            inj = self.inject_draw.pop(0) if isinstance(self.inject_draw, list) else self.inject_draw   # a list feeds successive calls
+        inj = self._take_injected()
+        if inj is not None:
             draw = {k: v for k, v in inj.items() if v is not None}
             if draw["eps_w"].shape[0] != S:
                 raise RuntimeError(f"inject_draw holds {draw['eps_w'].shape[0]} samples, this call computes {S}")
@@ -295,10 +309,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
             if self.post_scale is not None or residual is not None or self.post_relu or self.post_pool:
                 raise RuntimeError("the folded output stage (fuse.py) is inference-only: unfold or run under torch.no_grad()")
             from ..autograd import FusedForward, KLNormal
-            opts = dict(flip=self._flip, conv=conv, S=S, shared=shared, seed=seed, call=call, layer_id=self._layer_id, sample0=sample0,
-                        eps_w=draw.get("eps_w"), eps_b=draw.get("eps_b"), sign_in=draw.get("sign_in"), sign_out=draw.get("sign_out"),
-                        packed=self._packed(), call_base=call_base,      # call_base: a captured training step (mc.TrainGraph)
-                        workspace_owner=("layer", self._ws_id))
+            opts = self._launch_kw(conv, S, shared, coords, draw, self._packed())      # (call_base: a captured training step, mc.TrainGraph)
+            opts["workspace_owner"] = ("layer", self._ws_id)
             fused_kl = ctx is not None and getattr(ctx, "train_fused", False)
             if fused_kl:
                 # a training step (mc.TrainGraph): the KL term comes out of the forward kernel's fused sweep and is differentiated in
@@ -321,12 +333,9 @@ class FusedBayesLayer(BaseVariationalLayer_):
             mu_pk, sg_pk, kl_synced = self._packed_kl(sync_kl)
             fwd_kl = want_kl and kl_synced is None
             priors = (self.prior_weight_mu, self.prior_weight_sigma, self.prior_bias_mu, self.prior_bias_sigma) if fwd_kl else None
-            out, kl = F.fused_forward(x, mu_t, rho_t, self.mu_bias, self.rho_bias, flip=self._flip, conv=conv,
-                                      S=S, shared_x=shared, priors=priors, eps_w=draw.get("eps_w"), eps_b=draw.get("eps_b"),
-                                      sign_in=draw.get("sign_in"), sign_out=draw.get("sign_out"), seed=seed, call=call,
-                                      layer_id=self._layer_id, sample0=sample0, call_base=call_base, want_kl=fwd_kl,
-                                      workspace_owner=("layer", self._ws_id), post_scale=self.post_scale, post_shift=self.post_shift,
-                                      residual=residual, relu=self.post_relu, pool=self.post_pool, packed=(mu_pk, sg_pk), prior_type=kind,
+            out, kl = F.fused_forward(x, mu_t, rho_t, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, draw, (mu_pk, sg_pk)),
+                                      priors=priors, want_kl=fwd_kl, workspace_owner=("layer", self._ws_id), post_scale=self.post_scale,
+                                      post_shift=self.post_shift, residual=residual, relu=self.post_relu, pool=self.post_pool, prior_type=kind,
                                       eps_pack_state=self._eps_pack)
             if kl_synced is not None:
                 kl = kl_synced
@@ -334,8 +343,7 @@ class FusedBayesLayer(BaseVariationalLayer_):
         if self.post_pool and conv is not None:
             conv_shape = (out.shape[1],) + F.conv_out_hw(x.shape[2], x.shape[3], mu_t.shape[2], mu_t.shape[3], *conv["stride"],
                                                          *conv["padding"], *conv["dilation"])
-        self._last = dict(draw=draw or None, rng=(seed, call_base, call, self._layer_id, sample0), S=S,
-                          kernel=_lib.lib().bt_last_kernel_name().decode(), launch=_lib.last_launch_info(),
+        self._last = dict(draw=draw or None, rng=coords, S=S, kernel=_lib.lib().bt_last_kernel_name().decode(), launch=_lib.last_launch_info(),
                           shared_x=shared, residual=residual is not None, fused_kl=bool(not needs_grad and fwd_kl),
                           x_shape=(B,) + tuple(x.shape[1:]), out_shape=(B,) + conv_shape)
         if lead is not None:
@@ -381,6 +389,19 @@ class FusedBayesLayer(BaseVariationalLayer_):
             d["sign_out"] = torch.empty(os_, device=dev).uniform_(-1, 1).sign_()
         return d
 
+    _sign_keys = ("sign_in", "sign_out")      # what materialize_last_draw calls the regenerated Flipout signs
+
+    def _w_nat(self, t, lead=0):
+        """A weight-shaped tensor of the launch in this class's own kernel layout (the family layers re-arrange theirs)."""
+        return t
+
+    def _supplied_draw(self, d, S):
+        res = dict(eps_w=d["eps_w"].reshape((S,) + tuple(self._w("mu").shape)))
+        if d.get("eps_b") is not None:
+            res["eps_b"] = d["eps_b"].reshape(S, -1)
+        res.update({k: d[k] for k in ("sign_in", "sign_out") if d.get(k) is not None})
+        return res
+
     def materialize_last_draw(self):
         """The draw the last forward used, as tensors: eps_w [S, *w], eps_b [S, Co], and for Flipout
         sign_in [S, B, ...], sign_out [S, B, ...].  In 'torch' mode these are the tensors that were
@@ -388,25 +409,17 @@ class FusedBayesLayer(BaseVariationalLayer_):
         if self._last is None:
             raise RuntimeError("no forward has run yet")
         st = self._last
-        S = st["S"]
-        wshape = tuple(self._w("mu").shape)
         if st["draw"] is not None:
-            d = st["draw"]
-            res = dict(eps_w=d["eps_w"].reshape((S,) + wshape))
-            if d.get("eps_b") is not None:
-                res["eps_b"] = d["eps_b"].reshape(S, -1)
-            for k in ("sign_in", "sign_out"):
-                if d.get(k) is not None:
-                    res[k] = d[k]
-            return res
+            return self._supplied_draw(st["draw"], st["S"])
         seed, call_base, call, lid, sample0 = st["rng"]
         if call_base is not None:
             raise RuntimeError("draws made under a graph call_base cannot be replayed after the word advanced")
-        dev = self._w("mu").device
-        res = dict(eps_w=F.rng_fill_normal(seed, call, lid, sample0, 0, S, wshape, dev))
+        dev, S = self._w("mu").device, st["S"]
+        wshape = st.get("w_eq_shape") or tuple(self._w("mu").shape)      # (the family layers: the equivalent Conv2d kernel's)
+        res = dict(eps_w=self._w_nat(F.rng_fill_normal(seed, call, lid, sample0, 0, S, wshape, dev), lead=1))
         if self.mu_bias is not None:
             res["eps_b"] = F.rng_fill_normal(seed, call, lid, sample0, 1, S, (wshape[0],), dev)
         if self._flip:
-            res["sign_in"] = F.rng_fill_sign(seed, call, lid, sample0, 2, S, st["x_shape"], dev)
-            res["sign_out"] = F.rng_fill_sign(seed, call, lid, sample0, 3, S, st["out_shape"], dev)
+            res[self._sign_keys[0]] = F.rng_fill_sign(seed, call, lid, sample0, 2, S, st["x_shape"], dev)
+            res[self._sign_keys[1]] = F.rng_fill_sign(seed, call, lid, sample0, 3, S, st["out_shape"], dev)
         return res

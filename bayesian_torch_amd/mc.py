@@ -131,7 +131,44 @@ def mc_forward(model, x, S, sample0=0, with_kl=True):
     return out, kl
 
 
-class McGraph:
+class _CapturedStep:
+    """What McGraph and TrainGraph share: a step ``run()`` warmed up, captured once in a HIP graph, and replayed at the host call counter's
+    current position. The subclass owns ``call_base`` (the device word every captured kernel adds to its baked-in call coordinate)."""
+
+    def _warm_up(self, run, runs):
+        """``runs`` (>= 2) eager runs on a side stream, outside capture (packs, optimizer state, workspaces, LDS attributes); the last one
+        counts the call coordinates a run consumes."""
+        from . import rng
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(runs - 1):
+                run()
+            c0 = rng.peek_call()
+            run()
+            self.calls_per_run = rng.peek_call() - c0
+        torch.cuda.current_stream().wait_stream(side)
+        self.call0 = rng.peek_call()           # the call coordinate baked into the first captured layer
+
+    def _capture(self, run):
+        from . import rng
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            result = run()
+        rng.set_call(self.call0)               # capture executes nothing: its coordinates are still unused
+        return result
+
+    def _replay(self):
+        """Replay with the draws an eager run at this moment would make, and advance the host counter past them."""
+        from . import rng
+        c = rng.peek_call()
+        d = (c - self.call0) & 0xFFFFFFFF          # the device adds the word mod 2^32; the tensor holds it as int32
+        self.call_base.fill_(d - (1 << 32) if d >= (1 << 31) else d)
+        self.graph.replay()
+        rng.set_call(c + self.calls_per_run)
+
+
+class McGraph(_CapturedStep):
     """``mc_forward`` (+ the MC epilogue) captured once in a HIP graph and replayed per batch: the ~25 kernel launches of a
     model become one graph launch.  The draws stay fresh: every fused kernel adds a device-side word (``call_base``,
     bt_rng.call_base_dev) to its baked-in ``call`` coordinate, and ``replay()`` sets that word so that the replay draws at the
@@ -145,7 +182,7 @@ class McGraph:
     ("capturing the whole model per sample in a HIP graph".)"""
 
     def __init__(self, model, x, S, sample0=0, with_kl=True, epilogue=True, force_pack=False):
-        from . import functional as F, rng
+        from . import functional as F
         self.S, self.B = int(S), x.shape[0]
         self.x = x.clone()
         self.call_base = torch.zeros(1, dtype=torch.int32, device=x.device)
@@ -162,31 +199,15 @@ class McGraph:
             packed = F.mc_epilogue(logits.reshape(self.S, B, -1)) if epilogue else None
             return logits, kl, packed
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # warm-up outside capture: parameter packs, workspaces, LDS attributes
-            run()
-            c0 = rng.peek_call()
-            run()
-            self.calls_per_run = rng.peek_call() - c0
-        torch.cuda.current_stream().wait_stream(side)
-        self.call0 = rng.peek_call()           # the call coordinate baked into the first captured layer
+        self._warm_up(run, 2)
         self._packs = [m._pack for m in model.modules() if hasattr(m, "_pack_segment")]   # the buffers whose addresses the graph bakes in
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.logits, self.kl, self.packed = run()
-        rng.set_call(self.call0)               # capture executes nothing: its coordinates are still unused
+        self.logits, self.kl, self.packed = self._capture(run)
 
     def replay(self, x=None):
         """-> (logits [S, B, ...], kl, packed epilogue sums) -- tensors owned by the graph, overwritten by the next replay."""
-        from . import rng
         if x is not None:
             self.x.copy_(x)
-        c = rng.peek_call()
-        d = (c - self.call0) & 0xFFFFFFFF          # the device adds the word mod 2^32; the tensor holds it as int32
-        self.call_base.fill_(d - (1 << 32) if d >= (1 << 31) else d)
-        self.graph.replay()
-        rng.set_call(c + self.calls_per_run)
+        self._replay()
         return self.logits, self.kl, self.packed
 
 
@@ -210,7 +231,7 @@ def finish_deferred(ctx):
     ctx.deferred.clear()
 
 
-class TrainGraph:
+class TrainGraph(_CapturedStep):
     """One TRAINING step -- zero_grad, forward (fused kernels, one MC sample), ``loss_fn(model, out, y)``, backward (HIP dgrad /
     wgrad with the draws regenerated on chip), optimizer step -- captured once in a HIP graph and replayed per batch: the ~400
     kernel launches of a ResNet18 step become one graph launch (eager mode is launch-bound).  Fresh draws per step exactly as
@@ -224,7 +245,6 @@ class TrainGraph:
         """fused=True: every layer's KL term comes out of its forward kernel and is differentiated inside its weight-gradient pass
         (no KL launches, no KL-gradient tensors), and the weight-gradient passes run on a side stream -- a parallel branch of the
         captured graph -- beside the data-gradient chain. fused=False: plain autograd wiring (the checker the tests compare with)."""
-        from . import rng
         import os
         if side_wgrad is None:
             side_wgrad = os.environ.get("BT_TRAIN_SIDE_WGRAD", "0") not in ("", "0")
@@ -251,31 +271,14 @@ class TrainGraph:
             optimizer.step()
             return loss.detach()
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # warm-up outside capture: optimizer state, workspaces, LDS attributes
-            for _ in range(max(2, warmup) - 1):
-                run()
-            c0 = rng.peek_call()
-            run()
-            self.calls_per_run = rng.peek_call() - c0
-        torch.cuda.current_stream().wait_stream(side)
-        self.call0 = rng.peek_call()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.loss = run()
-        rng.set_call(self.call0)               # capture executes nothing: its coordinates are still unused
+        self._warm_up(run, max(2, warmup))
+        self.loss = self._capture(run)
 
     def step(self, x=None, y=None):
         """One optimizer step on (x, y) (default: the captured batch) -> loss (a tensor owned by the graph)."""
-        from . import rng
         if x is not None:
             self.x.copy_(x)
         if y is not None:
             self.y.copy_(y)
-        c = rng.peek_call()
-        d = (c - self.call0) & 0xFFFFFFFF
-        self.call_base.fill_(d - (1 << 32) if d >= (1 << 31) else d)
-        self.graph.replay()
-        rng.set_call(c + self.calls_per_run)
+        self._replay()
         return self.loss
