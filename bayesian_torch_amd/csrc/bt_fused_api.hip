@@ -9,13 +9,17 @@ int launch_reparam(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stre
 int launch_reparam_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 int launch_flipout_inj(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
+int launch_reparam_updil(const FwdArgs& a, FwdArgs& ran, hipStream_t stream);   // input-dilated images (bt_*_conv2d_updil_fwd)
+int launch_flipout_updil(const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
 
 static unsigned long long* g_dbg = nullptr;
 static thread_local long long g_launch_info[16] = {};
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// u: the input dilation and explicit padding of bt_*_conv2d_updil_fwd (g holds the REAL input dims), or null.
 static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const float* x, int64_t x_sample_stride, const bt_params* p,
-               const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream, const char* who) {
+               const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream, const char* who,
+               const bt_updil* u = nullptr) {
   char msg[256];
   auto bad = [&](const char* what) {
     snprintf(msg, sizeof(msg), "%s: %s", who, what);
@@ -29,6 +33,11 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
   if (g.sh <= 0 || g.sw <= 0 || g.dh <= 0 || g.dw <= 0 || g.ph < 0 || g.pw < 0 || g.groups <= 0) return bad("bad stride / padding / dilation / groups");
   if (g.Ci % g.groups || g.Co % g.groups) return bad("invalid in_channels size");  // conv_variational.py:270-273
   if (x_sample_stride < 0) return bad("negative x_sample_stride");
+  if (u) {
+    if (u->uh < 1 || u->uw < 1) return bad("input dilation must be >= 1");
+    if (u->lo_h < 0 || u->hi_h < 0 || u->lo_w < 0 || u->hi_w < 0) return bad("negative explicit padding (a crop: materialise the input instead)");
+    if (g.ph != 0 || g.pw != 0) return bad("ph / pw must be 0: the padding of the dilated image is explicit (lo / hi)");
+  }
   if (kl_out) {
     if (!p->prior_mu_w || !p->prior_sigma_w) return bad("kl_out given but weight priors are NULL");
     if (p->mu_b && (!p->prior_mu_b || !p->prior_sigma_b)) return bad("kl_out given but bias priors are NULL");
@@ -60,9 +69,19 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
     if (contraction_mode() != 0) return unsupported("the contraction is forced to f32 / bf16x2 / bf16 (bt_set_contraction, BT_CONTRACTION): only the exact split reads packed draws");
   }
 
-  const int Ho = (g.H + 2 * g.ph - g.dh * (g.kh - 1) - 1) / g.sh + 1;
-  const int Wo = (g.W + 2 * g.pw - g.dw * (g.kw - 1) - 1) / g.sw + 1;
+  // an input-dilated launch convolves the VIRTUAL image: the real one with u - 1 zeros between its pixels, padded by lo / hi
+  const long long Hv = u ? (long long)(g.H - 1) * u->uh + 1 + u->lo_h + u->hi_h : g.H, Wv = u ? (long long)(g.W - 1) * u->uw + 1 + u->lo_w + u->hi_w : g.W;
+  if (Hv >= (1ll << 30) || Wv >= (1ll << 30) || Hv * Wv >= (1ll << 30))
+    return set_error(BT_ERR_UNSUPPORTED, "fused forward: a dilated image of 2^30 pixels or more exceeds the kernel's 32-bit offsets");
+  const bool updil = u && (u->uh > 1 || u->uw > 1 || u->lo_h || u->hi_h || u->lo_w || u->hi_w);   // (else: the plain convolution, launch for launch)
+  const int Ho = (int)((Hv + 2 * g.ph - (long long)g.dh * (g.kh - 1) - 1) / g.sh + 1);
+  const int Wo = (int)((Wv + 2 * g.pw - (long long)g.dw * (g.kw - 1) - 1) / g.sw + 1);
   if (Ho <= 0 || Wo <= 0) return bad("empty output");
+  if (updil) {   // nothing is launched for what the dilated fetch does not cover
+    if (d->eps_w || d->eps_b || d->sign_in || d->sign_out || eps_packed)
+      return set_error(BT_ERR_UNSUPPORTED, "input-dilated launch: on-chip draws only (supplied draws take the materialised input)");
+    if (ep && ep->pool != BT_POOL_NONE) return set_error(BT_ERR_UNSUPPORTED, "input-dilated launch: no fused max-pool");
+  }
 
   FwdArgs a;
   FwdArgs zero = {}; a = zero;
@@ -80,20 +99,23 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
     a.sk_scratch_bytes = (long long)(ws_bytes - BT_WORKSPACE_BYTES);
     a.sk_tickets = reinterpret_cast<unsigned*>(ws_slots(ws) + 4000);
   }
-  a.B = g.B, a.Ci = g.Ci, a.H = g.H, a.W = g.W, a.Co = g.Co, a.KH = g.kh, a.KW = g.kw;
+  a.B = g.B, a.Ci = g.Ci, a.H = (int)Hv, a.W = (int)Wv, a.Co = g.Co, a.KH = g.kh, a.KW = g.kw;
+  if (updil) a.updil = 1, a.UH = u->uh, a.UW = u->uw, a.LH = u->lo_h, a.LW = u->lo_w, a.Hr = g.H, a.Wr = g.W, a.HWr = g.H * g.W;
   a.SH = g.sh, a.SW = g.sw, a.PH = g.ph, a.PW = g.pw, a.DH = g.dh, a.DW = g.dw, a.G = g.groups;
   a.Ho = Ho, a.Wo = Wo, a.HoWo = Ho * Wo;
   const long long M = (long long)g.B * Ho * Wo;
   a.Cig = g.Ci / g.groups, a.Cog = g.Co / g.groups;
   const long long K = (long long)a.Cig * g.kh * g.kw;
-  a.x_elems = (long long)g.B * g.Ci * g.H * g.W;
+  a.x_elems = (long long)g.B * g.Ci * g.H * g.W;   // (the REAL elements of an input-dilated launch: what x holds and what the input signs index)
+  if ((long long)g.B * g.Ci * Hv * Wv >= (1ll << 30))
+    return set_error(BT_ERR_UNSUPPORTED, "fused forward: a tensor of 2^30 elements or more exceeds the kernel's 32-bit offsets");
   a.out_elems = M * g.Co;
   a.w_elems = (long long)g.Co * K;
   // 32-bit index budget of the kernel (tile indices, hashed sign indices, Philox block index)
   if (M >= (1ll << 30) || K >= (1ll << 30) || a.x_elems >= (1ll << 30) || a.out_elems >= (1ll << 30) || a.w_elems >= (1ll << 30))
     return set_error(BT_ERR_UNSUPPORTED, "fused forward: a tensor of 2^30 elements or more exceeds the kernel's 32-bit offsets");
   a.M = (int)M, a.K = (int)K, a.S = S;
-  a.T = g.kh * g.kw, a.HW = g.H * g.W;
+  a.T = g.kh * g.kw, a.HW = (int)(Hv * Wv);
   if (a.T > kMaxTaps) return set_error(BT_ERR_UNSUPPORTED, "fused forward: kernels larger than 128 taps are not supported");
   // pixel-major tiles prune padding taps per output pixel; worth it when images are tiny (2x2 outputs: 4 of 9 taps)
   a.pixel_major = (!linear && a.HoWo >= 2 && a.HoWo <= 4 && (g.ph > 0 || g.pw > 0)) ? 1 : 0;
@@ -133,7 +155,8 @@ static int run(bool flip, bool linear, const bt_conv2d_geom& g, int S, const flo
       snprintf(msg, sizeof(msg), "%s: BT_DRAWS_EPS_PACKED: no split-precision flavour takes this launch (inject the natural layout)", who);
       return set_error(BT_ERR_UNSUPPORTED, msg);
     }
-  } else if (inj) rc = flip ? launch_flipout_inj(linear, a, r, (hipStream_t)stream) : launch_reparam_inj(linear, a, r, (hipStream_t)stream);
+  } else if (updil) rc = flip ? launch_flipout_updil(a, r, (hipStream_t)stream) : launch_reparam_updil(a, r, (hipStream_t)stream);
+  else if (inj) rc = flip ? launch_flipout_inj(linear, a, r, (hipStream_t)stream) : launch_reparam_inj(linear, a, r, (hipStream_t)stream);
   else rc = flip ? launch_flipout(linear, a, r, (hipStream_t)stream) : launch_reparam(linear, a, r, (hipStream_t)stream);
   if (rc == BT_OK) {   // tile geometry of the launch just made (bt_last_launch_info)
     const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, r.do_kl, 0};
@@ -178,6 +201,17 @@ extern "C" int bt_flipout_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const f
                                      const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g) return bt::set_error(BT_ERR_BAD_ARG, "bt_flipout_conv2d_fwd: null geometry");
   return bt::run(true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, stream, "bt_flipout_conv2d_fwd");
+}
+
+extern "C" int bt_reparam_conv2d_updil_fwd(const bt_conv2d_geom* g, const bt_updil* u, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
+                                           const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
+  if (!g || !u) return bt::set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_updil_fwd: null geometry");
+  return bt::run(false, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, stream, "bt_reparam_conv2d_updil_fwd", u);
+}
+extern "C" int bt_flipout_conv2d_updil_fwd(const bt_conv2d_geom* g, const bt_updil* u, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
+                                           const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
+  if (!g || !u) return bt::set_error(BT_ERR_BAD_ARG, "bt_flipout_conv2d_updil_fwd: null geometry");
+  return bt::run(true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, stream, "bt_flipout_conv2d_updil_fwd", u);
 }
 
 extern "C" size_t bt_fused_scratch_bytes(const bt_conv2d_geom* g, int32_t S) {

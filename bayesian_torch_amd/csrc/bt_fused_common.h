@@ -49,6 +49,13 @@ struct FwdArgs {
   int d_tap;     // direct flavour: the ONE tap of the kernel window that meets data (0 for 1x1 kernels; the centre of a padded window over a 1x1 image)
   int spw, n_sg;        // quad flavour, sample walk: samples per workgroup, sample groups = ceil(S / spw) (launch_quad)
   uint32_t inv_n_sg;
+  // input-dilated launches (bt_*_conv2d_updil_fwd: the transposed convolutions without the upsampled copy). H, W, HW above are the
+  // VIRTUAL image's -- planner, tile geometry, tap pruning and draw streams are those of the launch over the materialised tensor --
+  // and x is [B][Ci][Hr][Wr]: virtual pixel (y, x) is the real element ((y - LH) / UH, (x - LW) / UW) where both divide and the
+  // quotients are inside the real image, else a zero of the dilation or of the explicit padding. x_elems counts the REAL elements.
+  int updil;
+  int UH, UW, LH, LW, Hr, Wr, HWr;
+  uint32_t inv_uh, inv_uw;   // ceil(2^32 / UH), ceil(2^32 / UW) (0: divide), split_fill_inverses
 };
 
 // The split-precision chains (bt_fused_split.hip, bt_fused_split_flip.hip), for every translation unit that calls them. Each works on

@@ -106,7 +106,12 @@ __device__ __forceinline__ double block_sum_all(double v, double* scratch) {  //
 // is branch-free straight-line code in both flavours (a runtime branch between two loads is a scheduling barrier).
 // LINEAR: row-major [rows][K] operands with K % 4 == 0 and 16-B aligned bases (float4 loads); any other Linear runs as a
 // 1x1 convolution over a 1x1 image, which is the same memory layout.
-template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ>
+// UPD: x is the real image of an input-dilated launch (FwdArgs::updil: the transposed convolutions without the upsampled copy). Every
+// gather below works on the VIRTUAL image -- taps, patch, tile columns -- and maps the virtual pixel to the real element's offset at
+// the point where it forms the address; a pixel between the lattice points or in the explicit padding is masked like the zero padding.
+// An instantiation of its own, so that the other forms carry none of it. Flipout's input sign is hashed over the offset that is
+// read: one sign per real element.
+template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false>
 __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   unsigned long long* const dbg_ = kStamps ? a.dbg : nullptr;  // stage stamps: diagnostic build only (make STAMPS=1)
   constexpr int CWM = 4 / CWN;
@@ -117,6 +122,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   constexpr int W_WORDS = kBK * WS, X_WORDS = kBK * XS, BUF_WORDS = NW * (W_WORDS + X_WORDS);
   static_assert(TN >= 1 && TM >= 1 && BN % 32 == 0 && BM % 32 == 0 && WTM * CWM == BM && WTN * CWN == BN && BM <= kProducers, "tile shape");
   static_assert(!LINEAR || TRANS, "Linear always stores with lanes along the output features");
+  static_assert(!UPD || (!LINEAR && !INJ), "the input-dilated form: convolutions, on-chip draws");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];  // ONE LDS object
   int4* const taptab = reinterpret_cast<int4*>(smem + 2 * BUF_WORDS);
@@ -240,7 +246,16 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
     hi0 = ho * a.SH - a.PH;
     wi0 = wo * a.SW - a.PW;
     xoff0 = (b * a.Ci + g * Cig) * a.HW + hi0 * a.W + wi0;
+    if constexpr (UPD) xoff0 = (b * a.Ci + g * Cig) * a.HWr;  // the image's first real element (the pixel part comes from upd_map)
   }
+  // UPD: virtual pixel (y, x) -> offset of the real element inside its plane; -1: no element (off the lattice, explicit padding, outside)
+  [[maybe_unused]] auto upd_map = [&](int y, int x) -> int {
+    const int yv = y - a.LH, xw = x - a.LW;
+    if (yv < 0 || xw < 0) return -1;
+    const int yr = yv / a.UH, xr = xw / a.UW;
+    return (yr * a.UH == yv && xr * a.UW == xw && yr < a.Hr && xr < a.Wr) ? yr * a.Wr + xr : -1;
+  };
+  const int HWx = UPD ? a.HWr : a.HW;  // elements between the channels of a pixel in x
   const int Cig4 = (Cig + 3) & ~3;  // the draw index pads the channel axis to a multiple of 4: a weight unit is one Philox block
 
   // ---- producer state hoisted out of the stage loop -----------------------------------------------------------------------
@@ -281,6 +296,12 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int4 e = taptab[a0 + (t < na_s ? t : 0)];
+      if constexpr (UPD) {
+        const int m = (mvalid && t < na_s) ? upd_map(hi0 + e.y, wi0 + e.z) : -1;
+        g_off[t] = xoff0 + (m < 0 ? 0 : m);
+        if (m >= 0) g_ok |= 1u << t;
+        continue;
+      }
       g_off[t] = xoff0 + e.x;
       if (mvalid && t < na_s && (unsigned)(hi0 + e.y) < (unsigned)a.H && (unsigned)(wi0 + e.z) < (unsigned)a.W) g_ok |= 1u << t;
     }
@@ -304,8 +325,14 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
       const int yy = PWt == 1 ? rem : (int)__umulhi((uint32_t)rem, inv_pw);
       const int xx = rem - yy * PWt;
       const int b = b0 + img, y = y_lo + yy * gs_h, x = x_lo + xx * gs_w;
-      const bool ok = pos < PCH && b < a.B && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
-      p_off[i] = ok ? (b * a.Ci + g * Cig) * a.HW + y * a.W + x : 0;
+      bool ok = pos < PCH && b < a.B && (unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W;
+      if constexpr (UPD) {
+        const int m = ok ? upd_map(y, x) : -1;
+        ok = m >= 0;
+        p_off[i] = ok ? (b * a.Ci + g * Cig) * a.HWr + m : 0;
+      } else {
+        p_off[i] = ok ? (b * a.Ci + g * Cig) * a.HW + y * a.W + x : 0;
+      }
       if (ok) p_ok |= 1u << i;
     }
   }
@@ -439,7 +466,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
           for (int c = 0; c < CCs; ++c) {
             const bool ok = ((p_ok >> i) & 1u) && (c0 + c < Cig);
             if (ok) xok |= 1ull << (i * CCs + c);
-            const uint32_t off = ok ? (uint32_t)(p_off[i] + (c0 + c) * a.HW) : 0u;
+            const uint32_t off = ok ? (uint32_t)(p_off[i] + (c0 + c) * HWx) : 0u;
             xv[i * CCs + c] = xs[off];
             if constexpr (FLIP) {
               xo[i * CCs + c] = off;
@@ -450,14 +477,14 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
       }
     } else if constexpr (FASTX) {
       const int ci0 = c0 + xg;
-      const int cbase = ci0 * a.HW;
+      const int cbase = ci0 * HWx;
 #pragma unroll
       for (int t = 0; t < TPS; ++t) {
 #pragma unroll
         for (int c = 0; c < CPT; ++c) {
           const bool ok = ((g_ok >> t) & 1u) && (ci0 + c * NG < Cig);
           if (ok) xok |= 1ull << (t * CPT + c);
-          const uint32_t off = ok ? (uint32_t)(g_off[t] + cbase + c * NG * a.HW) : 0u;
+          const uint32_t off = ok ? (uint32_t)(g_off[t] + cbase + c * NG * HWx) : 0u;
           xv[t * CPT + c] = xs[off];
           if constexpr (FLIP) {
             xo[t * CPT + c] = off;
@@ -472,9 +499,14 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
         const int kc = xg + q * NG;
         const int4 e = taptab[a0 + (kc < KC ? (kc >> LCC) : 0)];
         const int ci = c0 + (kc & (CCs - 1));
-        const bool ok = mvalid && kc < KC && ci < Cig && (unsigned)(hi0 + e.y) < (unsigned)a.H && (unsigned)(wi0 + e.z) < (unsigned)a.W;
+        bool ok = mvalid && kc < KC && ci < Cig && (unsigned)(hi0 + e.y) < (unsigned)a.H && (unsigned)(wi0 + e.z) < (unsigned)a.W;
+        int pxo = e.x;  // the pixel's offset from xoff0
+        if constexpr (UPD) {
+          pxo = ok ? upd_map(hi0 + e.y, wi0 + e.z) : -1;
+          ok = pxo >= 0;
+        }
         if (ok) xok |= 1ull << q;
-        const uint32_t off = ok ? (uint32_t)(xoff0 + ci * a.HW + e.x) : 0u;
+        const uint32_t off = ok ? (uint32_t)(xoff0 + ci * HWx + pxo) : 0u;
         xv[q] = xs[off];
         if constexpr (FLIP) {
           xo[q] = off;

@@ -1,0 +1,11 @@
+// Reparameterization forward over an input-dilated image (FwdArgs::updil): the split-precision chain first (the general split kernel's
+// xm 5 fetch), then the fp32 general kernel's UPD instantiations for what the split tiles do not hold. In a translation unit of its
+// own so the build stays parallel.
+#include "bt_fused_dispatch.h"
+namespace bt {
+int launch_reparam_updil(const FwdArgs& a, FwdArgs& ran, hipStream_t stream) {
+  const int rc = launch_split(a, ran, stream);
+  if (rc <= 0) return rc;
+  return launch_flavour_updil<false>(a, ran, stream);
+}
+}  // namespace bt

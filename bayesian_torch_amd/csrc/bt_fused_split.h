@@ -110,6 +110,10 @@ __device__ __forceinline__ int div_small(int n, int d) { return d == 1 ? n : d =
 //   4: the same for a patch that keeps every SECOND column (1x1 / stride 2: the downsamples): item = (4 consecutive input
 //      pixels, octet) = 2 patch pixels x 8 channels. (A dword gather at stride 2 costs the texture path ~70 cycles per wave
 //      instruction against 16 for a contiguous 16-byte one: 9.4 K -> 2 K cycles per stage on ResNet18's downsamples.)
+//   5: an input-dilated image (FwdArgs::updil: the transposed convolutions). The items, the patch and everything behind it are XM 0's
+//      over the VIRTUAL image; the decode maps a virtual pixel to the real element it stands for, or -- between the lattice points and
+//      in the explicit padding -- to the out-of-range offset that reads as zero, and the stage loop steps by the REAL plane size.
+//      Flipout hashes its input signs over the real element index: one sign per element of [B][Ci][Hr][Wr], as the reference draws them.
 //
 // FLIP: the Flipout forward  out = x*mu + s_out o ((x o s_in) * (sigma o eps))  (flipout_layers.py:conv / linear forward): two
 // contractions that share the x pieces. The producers stage mu and sigma*eps as two weight images and, next to the pieces of
@@ -537,7 +541,14 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           const int xx = rem - yy * NXR;
           const int b = b0 + img, y = y_lo + (yy + kmin_h) * gs_h, x = x_lo + (xx + kmin_w) * gs_w;   // a real pixel by construction
           lds = (ol * PCH + r) * PB;
-          if (b < a.B) off = 4 * ((b * a.Ci + g * Cig) * a.HW + y * a.W + x);
+          if constexpr (XM == 5) {  // virtual -> real: on the lattice and inside the real image, else a zero (kOOB)
+            const int yv = y - a.LH, xw = x - a.LW;
+            const int yr = yv > 0 ? udiv_inv(yv, a.UH, a.inv_uh) : 0, xr = xw > 0 ? udiv_inv(xw, a.UW, a.inv_uw) : 0;
+            const bool on = yv >= 0 && xw >= 0 && yr * a.UH == yv && xr * a.UW == xw && yr < a.Hr && xr < a.Wr;
+            if (b < a.B && on) off = 4 * ((b * a.Ci + g * Cig) * a.HWr + yr * a.Wr + xr);
+          } else if (b < a.B) {
+            off = 4 * ((b * a.Ci + g * Cig) * a.HW + y * a.W + x);
+          }
         }
         it_off[i] = off;
         it_lds[i] = f < n_items ? lds : -1;
@@ -545,7 +556,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       }
     }
     if (stamp0) dbg_[214] = __builtin_amdgcn_s_memtime();
-    const int HWb = 4 * a.HW;
+    const int HWx = XM == 5 ? a.HWr : a.HW;   // elements between the channels of a pixel in x
+    const int HWb = 4 * HWx;
     const int wave_i0 = wave_u0;  // first item index of this wave (iteration 0)
     const int n_items_w = n_items;
 
@@ -650,7 +662,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         if ((i == 0 || wave_i0 + kProducers * i < n_items_w) && it_lds[i] >= 0) {
           char* const dst = Xt + it_lds[i];
           // Flipout: element offset (in the sample's x) of the item's first element -- the index of its sign
-          const uint32_t e0 = FLIP ? ((uint32_t)it_off[i] >> 2) + (uint32_t)(8 * (st * NO + it_ol[i])) * (uint32_t)a.HW : 0u;
+          const uint32_t e0 = FLIP ? ((uint32_t)it_off[i] >> 2) + (uint32_t)(8 * (st * NO + it_ol[i])) * (uint32_t)HWx : 0u;
           if constexpr (XM == 2) {  // 2 channels x the plane's 4 pixels: one dword of each pixel's 16-byte slots
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
@@ -701,7 +713,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           } else {
             const float v[8] = {xv[i][0], xv[i][1], xv[i][2], xv[i][3], xv[i][4], xv[i][5], xv[i][6], xv[i][7]};
             if constexpr (SGN) store_px_sg(dst, v, sgv[i]);
-            else store_px(dst, v, e0, XM == 1 ? 1u : (uint32_t)a.HW);
+            else store_px(dst, v, e0, XM == 1 ? 1u : (uint32_t)HWx);
           }
         }
       }

@@ -42,7 +42,7 @@ static inline uint32_t inv_u32(long long d, long long nmax) {
 static inline void split_fill_inverses(FwdArgs& a) {
   static const bool off = getenv("BT_NO_HOST_INV") != nullptr;   // test hook: every kernel-side division takes its fallback path
   if (off) {
-    a.inv_m_tiles = a.inv_S = a.inv_n_tiles = a.inv_n_bt = a.inv_n_ct = a.inv_rw = a.inv_wt = a.inv_kw = a.inv_n_sg = 0u;
+    a.inv_m_tiles = a.inv_S = a.inv_n_tiles = a.inv_n_bt = a.inv_n_ct = a.inv_rw = a.inv_wt = a.inv_kw = a.inv_n_sg = a.inv_uh = a.inv_uw = 0u;
     return;
   }
   const long long tb = a.total_blocks;
@@ -55,6 +55,7 @@ static inline void split_fill_inverses(FwdArgs& a) {
   a.inv_wt = inv_u32(a.t_Wt, 1024);
   a.inv_kw = inv_u32(a.KW, 64);
   a.inv_n_sg = inv_u32(a.n_sg, tb);
+  a.inv_uh = a.updil ? inv_u32(a.UH, a.H) : 0u, a.inv_uw = a.updil ? inv_u32(a.UW, a.W) : 0u;   // (virtual pixel -> real element, XM 5)
 }
 
 // Extent of the window of taps that can meet data along one axis (the kernel's own rule: bt_fused_split.h), for the whole

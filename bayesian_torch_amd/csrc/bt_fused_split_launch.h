@@ -24,6 +24,9 @@ int launch_quad_bf16(const FwdArgs& a, hipStream_t stream);
 int launch_direct_bf16(const FwdArgs& a, bool resident, hipStream_t stream);
 int launch_split_flip_inj_cfg(const FwdArgs& a, int bm, int xm, hipStream_t stream);   // bt_fused_split_flip_inj.hip: + BT_DRAWS_SIGNS_PACKED
 int launch_quad_flip_inj(const FwdArgs& a, hipStream_t stream);
+// bt_fused_split_updil.hip: the input-dilated fetch (xm 5, FwdArgs::updil) of the general kernel, on-chip draws -- np 3 / 1
+// Reparameterization (every tile), Flipout (np 3). BT_ERR_UNSUPPORTED, nothing launched, for anything else.
+int launch_split_updil_cfg(const FwdArgs& a, int bm, int np, bool flip, hipStream_t stream);
 
 // ---------------------------------------------------------------------------- names
 // bt_last_kernel_name's strings (tests, bench.py's tables and the tools parse them) and the `who` of the error messages.
@@ -70,19 +73,25 @@ inline SplitNames skinny_kernel_names(bool inj, int ks) {
 //   NP 3 / 1, Reparam.       xm {0,1,2} x BN {64,32}       xm {0,2,3,4}            xm {0,3,4}
 //   NP 2 (bf16x2, opt-in)    xm 0 (the generic fetch)      xm 0                    xm 0
 //   Flipout                  xm {0,1}                      xm {0,3}                --
+// xm 5 (input-dilated images) exists for every tile of the np 3 / 1 Reparameterization and of the Flipout variant with on-chip draws. No
+// other fetch can stand in for it -- the generic one would read the real image as if it were the virtual one -- so launch_split_xm never
+// reaches it: launch_split_updil_cfg names its instantiations one by one.
 // (Flipout's 128-wide xm 2 -- whole 2x2 planes of a pixel-major 3x3 -- is not instantiated: DESIGN 4.0c.)
 constexpr int split_npw(int bm, bool flip) { return flip ? (bm == 128 ? 8 : 4) : (bm == 512 ? 4 : 8); }
 constexpr bool split_exists(int bn, int bm, int np, bool flip, int xm) {
   if (flip ? (bn != 64 || bm == 512) : (bn == 32 && (bm != 128 || np == 2))) return false;
   if (xm == 0) return true;
   if (np == 2) return false;
+  if (xm == 5) return true;
   if (flip) return bm == 128 ? xm == 1 : xm == 3;
   return bm == 128 ? xm <= 2 : bm == 256 ? xm >= 2 : xm >= 3;
 }
 
 template <int NP, bool FLIP, bool INJ, int BN, int BM, int XM>
 int launch_split_inst(const FwdArgs& a, hipStream_t stream) {
-  if constexpr (!split_exists(BN, BM, NP, FLIP, XM)) {
+  if constexpr (XM == 5 && (INJ || !split_exists(BN, BM, NP, FLIP, XM))) {
+    return set_error(BT_ERR_UNSUPPORTED, "fused forward (split): no input-dilated instantiation of this tile and variant");
+  } else if constexpr (!split_exists(BN, BM, NP, FLIP, XM)) {
     static_assert(XM != 0, "the generic fetch exists for every tile a variant has");
     return launch_split_inst<NP, FLIP, INJ, BN, BM, 0>(a, stream);   // a fetch mode without an instantiation: the generic fetch
   } else {

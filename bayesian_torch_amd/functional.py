@@ -35,7 +35,8 @@ def maxpool_3x3s2(x):
 
 
 def _geometry(x, mu_w, conv, S, shared_x):
-    """-> (B, the launch's bt_conv2d_geom -- Linear as the 1 x 1 convolution --, one sample's x elements, the contraction's output tail)."""
+    """-> (B, the launch's bt_conv2d_geom -- Linear as the 1 x 1 convolution --, one sample's x elements, the contraction's output tail).
+    An input-dilated conv (``conv["updil"]``): the geom holds x's own dims and no padding, the tail is the virtual image's output."""
     per = 1 if shared_x else S
     if x.shape[0] % per:
         raise RuntimeError("stacked input rows are not a multiple of S")
@@ -50,7 +51,13 @@ def _geometry(x, mu_w, conv, S, shared_x):
     Ci, H, W = x.shape[1], x.shape[2], x.shape[3]
     if Ci != mu_w.shape[1] * groups:
         raise RuntimeError(f"input has {Ci} channels, weight expects {mu_w.shape[1] * groups}")
-    Ho, Wo = conv_out_hw(H, W, kh, kw, sh, sw, ph, pw, dh, dw)
+    Hv, Wv = H, W
+    if conv.get("updil") is not None:       # the virtual image of bt_*_conv2d_updil_fwd
+        (uh, uw), (lo_h, hi_h, lo_w, hi_w) = conv["updil"], conv["pads"]
+        if (ph, pw) != (0, 0) or min(uh, uw) < 1 or min(lo_h, hi_h, lo_w, hi_w) < 0:
+            raise RuntimeError("an input-dilated conv takes dilation >= 1, explicit pads >= 0 and padding (0, 0)")
+        Hv, Wv = (H - 1) * uh + 1 + lo_h + hi_h, (W - 1) * uw + 1 + lo_w + hi_w
+    Ho, Wo = conv_out_hw(Hv, Wv, kh, kw, sh, sw, ph, pw, dh, dw)
     if Ho <= 0 or Wo <= 0:
         raise RuntimeError("convolution output would be empty")
     return B, _lib.bt_conv2d_geom(B, Ci, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, groups), x.numel() // per, (Co, Ho, Wo)
@@ -122,6 +129,9 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
                    inject_path=None, eps_pack_state=None):
     """x: [B, In] (conv=None) or [B, Ci, H, W]; when ``shared_x`` is False x holds S stacked batches
     ([S*B, ...]).  conv: dict(stride=(sh,sw), padding=(ph,pw), dilation=(dh,dw), groups=g) for Conv2d.
+    With ``updil=(uh, uw)`` and ``pads=(lo_h, hi_h, lo_w, hi_w)`` in it (padding (0, 0)), x is convolved as the input-dilated, explicitly
+    padded image it stands for (bt_*_conv2d_updil_fwd: a transposed convolution without the upsampled copy); on-chip draws only, and a
+    launch the library declines (BT_ERR_UNSUPPORTED, nothing launched) returns None instead of a result.
     priors: (prior_mu_w, prior_sigma_w, prior_mu_b, prior_sigma_b) -- required when want_kl.
     eps_*/sign_*: injected draws with a leading S axis, or None for the on-chip generators.
     post_scale/post_shift [Co], residual ([S*B, ...] like out, or [B, ...] shared), relu: fused output stage
@@ -158,9 +168,13 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     L = _lib.lib()
     geo_key = (B, S, bool(shared_x), tuple(x.shape[1:]), None if conv is None else (*conv["stride"], *conv["padding"], *conv["dilation"], conv["groups"]),
                bool(pool), residual is not None)
-    split_inj = _split_inject_wanted(tens, flip, S, x_elems, n_so, inject_path, eps_pack_state, geo_key)
+    updil = None
+    if conv is not None and conv.get("updil") is not None:
+        updil = _lib.bt_updil(*conv["updil"], *conv["pads"])
+        geo_key += (tuple(conv["updil"]), tuple(conv["pads"]))
+    split_inj = updil is None and _split_inject_wanted(tens, flip, S, x_elems, n_so, inject_path, eps_pack_state, geo_key)
     # layers whose output map is one pixel may run split over K-slices that meet in scratch behind the workspace (include/bt_hip.h)
-    scratch = int(L.bt_fused_scratch_bytes(C.byref(geom), S)) if ((eps_w is None or split_inj) and not flip and packed is not None) else 0
+    scratch = int(L.bt_fused_scratch_bytes(C.byref(geom), S)) if ((eps_w is None or split_inj) and not flip and packed is not None and updil is None) else 0
     if want_kl:
         if priors is None:
             raise ValueError("want_kl needs priors")
@@ -183,6 +197,9 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
         if conv is None:
             fn = L.bt_flipout_linear_fwd if flip else L.bt_reparam_linear_fwd
             return fn(B, geom.Ci, geom.Co, S, *tail_args)
+        if updil is not None:
+            fn = L.bt_flipout_conv2d_updil_fwd if flip else L.bt_reparam_conv2d_updil_fwd
+            return fn(C.byref(geom), C.byref(updil), S, *tail_args)
         fn = L.bt_flipout_conv2d_fwd if flip else L.bt_reparam_conv2d_fwd
         return fn(C.byref(geom), S, *tail_args)
 
@@ -192,7 +209,7 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
             if eps_pack_state is not None:
                 eps_pack_state["declined"].add(geo_key)
             rc = launch(D_nat)
-        if pool and rc == _lib.ERR_UNSUPPORTED:
+        if (pool or updil is not None) and rc == _lib.ERR_UNSUPPORTED:
             return None
         _lib.check(rc)
     return out, kl

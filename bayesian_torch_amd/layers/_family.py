@@ -16,9 +16,20 @@ re-arrangements that are exact (no arithmetic):
     [Co][Ci/g][kd][kh][kw] kernel IS a [Co][(Ci/g)*kd][kh][kw] kernel in memory;
   * Conv1d-like = a 1 x k kernel over 1 x L images.
 The re-arrangements of x are torch gathers (differentiable: training goes through the same autograd bridge as Conv2d) and cost
-one extra pass over the activations; doing them inside the kernel's x staging (a dgrad-style gather) is the follow-up. KL is
-taken by the standalone KL kernel on the parameters in their own layout.
+one extra pass over the activations. KL is taken by the standalone KL kernel on the parameters in their own layout.
+
+ConvTranspose1d / ConvTranspose2d can skip that pass: ``set_transpose_path("native")`` (or ``BT_CONVT_PATH=native``) hands the
+UN-upsampled x to the input-dilated entry points (bt_*_conv2d_updil_fwd), whose kernels resolve the virtual zero-upsampled, padded image
+where they form their x addresses -- no tensor of the upsampled size is written or read. It applies to inference calls (no grad) that
+draw on chip and crop nothing (d*(k-1) - p >= 0 in every axis); every other call, and any launch the library declines, takes the
+materialising path. Reparameterization results are the same bits where both paths run the general split-precision kernel. Flipout
+then draws one input sign per REAL element ([B][Ci][spatial], the reference's layout and distribution), so its samples differ from
+the materialising path's, whose stream runs over the upsampled tensor. Under the "native" setting ``_last["x_path"]`` says which path
+the call took ("native" | "upsample") and ``_last["x_shape"]`` is the shape of the x that was launched. The default is "upsample":
+every launch, and the launch record, as before. ConvTranspose3d, Conv3d's depth unfolding and the training path always materialise.
 """
+import os
+
 import torch
 import torch.nn.functional as TF
 
@@ -30,6 +41,30 @@ from .base_variational_layer import get_kernel_size
 
 def _tup(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
+
+
+TRANSPOSE_PATHS = ("upsample", "native")
+
+
+def _check_path(name, what):
+    if name not in TRANSPOSE_PATHS:
+        raise ValueError(f"{what}: expected one of {TRANSPOSE_PATHS}, got {name!r}")
+    return name
+
+
+_transpose_path = [_check_path(os.environ.get("BT_CONVT_PATH", "upsample"), "BT_CONVT_PATH")]
+
+
+def set_transpose_path(name):
+    """How ConvTranspose1d / ConvTranspose2d layers feed their launch: "upsample" (default) materialises the zero-upsampled, padded
+    input; "native" lets the kernels read the real input through the input-dilated fetch where the call is eligible (module docstring).
+    Process-wide; also the environment variable BT_CONVT_PATH, read at import. Returns the previous setting."""
+    prev, _transpose_path[0] = _transpose_path[0], _check_path(name, "set_transpose_path")
+    return prev
+
+
+def get_transpose_path():
+    return _transpose_path[0]
 
 
 class FamilyConvLayer(FusedBayesLayer):
@@ -112,6 +147,27 @@ class FamilyConvLayer(FusedBayesLayer):
             back = lambda o: o.reshape(-1, Do, o.shape[1], o.shape[2], o.shape[3]).permute(0, 2, 1, 3, 4)
         return x.contiguous(), conv, back
 
+    def _native_pads(self):
+        """Per spatial axis (lo, hi): the explicit padding of the dilated input -- exactly what _x_eq hands to F.pad."""
+        s, p, d, op, ks = self._geom()
+        return [(d[i] * (ks[i] - 1) - p[i], d[i] * (ks[i] - 1) - p[i] + op[i]) for i in range(self._nd)]
+
+    def _native_eligible(self, needs_grad, supplied):
+        """Does this call take the input-dilated launch? ConvTranspose1d / 2d under set_transpose_path("native"), no grad, on-chip draws,
+        nothing cropped (a negative pad keeps the materialising path)."""
+        return (self._transposed and self._nd <= 2 and _transpose_path[0] == "native" and not needs_grad and not supplied
+                and all(lo >= 0 for lo, _ in self._native_pads()))
+
+    def _x_native(self, x):
+        """[N][C][spatial...] of a ConvTranspose1d / 2d -> (the real input as [N][C][H][W], the input-dilated conv dict, back)."""
+        s, p, d, op, ks = self._geom()
+        pads = self._native_pads()
+        if self._nd == 1:
+            conv = dict(stride=(1, 1), padding=(0, 0), dilation=(1, d[0]), groups=self.groups, updil=(1, s[0]), pads=(0, 0) + pads[0])
+            return x.unsqueeze(2).contiguous(), conv, lambda o: o.squeeze(2)
+        conv = dict(stride=(1, 1), padding=(0, 0), dilation=d, groups=self.groups, updil=s, pads=pads[0] + pads[1])
+        return x.contiguous(), conv, lambda o: o
+
     def _sign_out_eq(self, t):
         """[S][B][Co][spatial...] (the reference's layout) -> the Conv2d launch's [S][B'][Co][Ho][Wo]."""
         if self._nd == 1:
@@ -148,8 +204,14 @@ class FamilyConvLayer(FusedBayesLayer):
         """The last forward's draw in the REFERENCE's layouts where one exists: eps_w [S, *kernel], eps_b [S, Co]. The on-chip
         Flipout signs are defined over the Conv2d launch's operands (``sign_in_eq`` / ``sign_out_eq``: the re-arranged x and the
         launch's output): a transposed convolution's zero-upsampled x carries one sign per real element like the reference, Conv3d's
-        depth-unfolded x one sign per (element, depth window) -- see DESIGN.md 4.6."""
-        return super().materialize_last_draw()
+        depth-unfolded x one sign per (element, depth window) -- see DESIGN.md 4.6. A launch on the "native" path drew its input signs
+        over the real x: they are reported as ``sign_in`` [S, B, Ci, spatial...] and ``sign_out`` [S, B, Co, spatial...], the reference's
+        own layouts (``sign_out_eq`` stays: the same values in the launch's layout)."""
+        res = super().materialize_last_draw()
+        if self._flip and self._last.get("x_path") == "native" and "sign_in_eq" in res:
+            si, so = res.pop("sign_in_eq"), res["sign_out_eq"]
+            res["sign_in"], res["sign_out"] = (si.squeeze(3), so.squeeze(3)) if self._nd == 1 else (si, so)
+        return res
 
     # ------------------------------------------------------------------ forward
     def forward(self, input, return_kl=True):
@@ -160,31 +222,40 @@ class FamilyConvLayer(FusedBayesLayer):
         if x.dim() != self._nd + 2 or x.shape[1] != self.in_channels:
             raise RuntimeError(f"{type(self).__name__}: expected [N, {self.in_channels}, {self._nd} spatial dims], got {tuple(x.shape)}")
         S, shared, coords = self._call_coords(ctx, x.shape[0])
-        xe, conv, back = self._x_eq(x)
         mu_e, rho_e = self._w_eq(self._w("mu")), self._w_eq(self._w("rho"))
-        draw = {}
-        inj = self._take_injected()
-        if inj is not None:           # draws in the reference's layouts (test hook), re-arranged like the operands
-            draw["eps_w"] = self._w_eq(inj["eps_w"], lead=1)
-            if inj.get("eps_b") is not None:
-                draw["eps_b"] = inj["eps_b"]
-            if self._flip:
-                si = inj["sign_in"]
-                draw["sign_in"] = self._x_eq(si.reshape((-1,) + tuple(si.shape[2:])))[0].reshape((si.shape[0], -1) + tuple(xe.shape[1:]))
-                draw["sign_out"] = self._sign_out_eq(inj["sign_out"])
-        elif rng.get_mode() == "torch":
-            raise NotImplementedError("rng mode 'torch' covers Linear / Conv1d / Conv2d; the rest of the family draws on chip or takes inject_draw")
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if needs_grad:
-            from ..autograd import FusedForward
-            if coords.call_base is not None:
-                raise RuntimeError("graph-replayed draws (call_base) are not supported on the training path")
-            out = FusedForward.apply(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, self._launch_kw(conv, S, shared, coords, draw, self._packed()))
-        else:
-            out, _ = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, draw, self._packed()))
+        inj = self._take_injected()
+        out, x_path = None, "upsample"
+        if self._native_eligible(needs_grad, inj is not None or rng.get_mode() == "torch"):
+            xe, conv, back = self._x_native(x)      # the real x: the kernels resolve the upsampled, padded image in their x fetch
+            r = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, {}, self._packed()))
+            if r is not None:      # (None: the library declined, nothing was launched -> the materialising path, same coordinates)
+                out, x_path = r[0], "native"
+        draw = {}
+        if out is None:
+            xe, conv, back = self._x_eq(x)
+            if inj is not None:           # draws in the reference's layouts (test hook), re-arranged like the operands
+                draw["eps_w"] = self._w_eq(inj["eps_w"], lead=1)
+                if inj.get("eps_b") is not None:
+                    draw["eps_b"] = inj["eps_b"]
+                if self._flip:
+                    si = inj["sign_in"]
+                    draw["sign_in"] = self._x_eq(si.reshape((-1,) + tuple(si.shape[2:])))[0].reshape((si.shape[0], -1) + tuple(xe.shape[1:]))
+                    draw["sign_out"] = self._sign_out_eq(inj["sign_out"])
+            elif rng.get_mode() == "torch":
+                raise NotImplementedError("rng mode 'torch' covers Linear / Conv1d / Conv2d; the rest of the family draws on chip or takes inject_draw")
+            if needs_grad:
+                from ..autograd import FusedForward
+                if coords.call_base is not None:
+                    raise RuntimeError("graph-replayed draws (call_base) are not supported on the training path")
+                out = FusedForward.apply(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, self._launch_kw(conv, S, shared, coords, draw, self._packed()))
+            else:
+                out, _ = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, draw, self._packed()))
         Be = xe.shape[0] // (1 if shared else S)
         self._last = dict(draw=draw or None, rng=coords, S=S, kernel=_lib.lib().bt_last_kernel_name().decode(),
                           w_eq_shape=tuple(mu_e.shape), x_shape=(Be,) + tuple(xe.shape[1:]), out_shape=(Be,) + tuple(out.shape[1:]))
+        if _transpose_path[0] == "native":      # (under the default setting the record stays what it was, key for key)
+            self._last["x_path"] = x_path
         out = back(out).contiguous()
         kl = self.kl_loss() if want_kl else None
         if collect:

@@ -172,6 +172,34 @@ int bt_reparam_conv2d_fwd(const bt_conv2d_geom *g, int32_t S,
                           float *out /* [S][B][Co][Ho][Wo] */, float *kl_out,
                           void *workspace, size_t workspace_bytes, bt_stream_t stream);
 
+/* The same two convolutions over an INPUT-DILATED image: the forward of a transposed convolution without its zero-upsampled copy.
+ * x is the real input [B][Ci][g->H][g->W]; the kernels convolve the virtual image of
+ *     Hv = (H - 1) * uh + 1 + lo_h + hi_h,   Wv = (W - 1) * uw + 1 + lo_w + hi_w
+ * pixels -- uh - 1 / uw - 1 zeros between neighbouring input pixels, lo / hi zeros around them -- with the weights in Conv2d layout
+ * [Co][Ci/groups][kh][kw] (a ConvTranspose kernel with its channel axes swapped and its taps flipped), stride g->sh / g->sw and
+ * dilation g->dh / g->dw as usual: out is [S][B][Co][Ho][Wo] over (Hv, Wv). g->ph and g->pw must be 0 (the padding is explicit).
+ * The virtual pixels are resolved where the kernels form their x addresses: nothing of size Hv x Wv is written or read. Tile plan,
+ * tap pruning, K order and draw streams are those of bt_*_conv2d_fwd on the materialised image, so Reparameterization results are the
+ * same bits where both run the general split-precision kernel; Flipout draws ONE input sign per real element, indexed in
+ * [B][Ci][H][W] (bt_rng_sign_fill, tensor 2, n = B*Ci*H*W) -- the reference's distribution, not the materialised launch's stream.
+ * Kernels: the general split-precision kernel (x fetch mode 5; bt_set_contraction modes 0 and 3) or the fp32 general kernel. On-chip
+ * draws only and no fused max-pool: BT_ERR_UNSUPPORTED with nothing launched otherwise. uh, uw < 1, a negative lo / hi, or
+ * ph / pw != 0: BT_ERR_BAD_ARG. With uh == uw == 1 and no padding the call is bt_*_conv2d_fwd, launch for launch. */
+typedef struct bt_updil {
+  int32_t uh, uw;                 /* input dilation, >= 1 */
+  int32_t lo_h, hi_h, lo_w, hi_w; /* explicit zero padding of the dilated image, >= 0 */
+} bt_updil;
+int bt_reparam_conv2d_updil_fwd(const bt_conv2d_geom *g, const bt_updil *u, int32_t S,
+                                const float *x, int64_t x_sample_stride,
+                                const bt_params *p, const bt_draws *d, const bt_epilogue *ep /* or NULL */,
+                                float *out /* [S][B][Co][Ho][Wo] */, float *kl_out,
+                                void *workspace, size_t workspace_bytes, bt_stream_t stream);
+int bt_flipout_conv2d_updil_fwd(const bt_conv2d_geom *g, const bt_updil *u, int32_t S,
+                                const float *x, int64_t x_sample_stride,
+                                const bt_params *p, const bt_draws *d, const bt_epilogue *ep /* or NULL */,
+                                float *out, float *kl_out,
+                                void *workspace, size_t workspace_bytes, bt_stream_t stream);
+
 /* a9: LinearFlipout.forward  (layers/flipout_layers/linear_flipout.py:145-174)
  *   out = x W_mu^T + mu_b + ((x o s_in) (sigma o eps)^T + sigma_b o eps_b) o s_out  -- both contractions share one x tile. */
 int bt_flipout_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S,
