@@ -1,8 +1,11 @@
 // Host-side helpers shared by the C-ABI entry points.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
+#include <stdlib.h>
 
+#include <atomic>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -14,7 +17,36 @@ namespace bt {
 
 int set_error(int code, const char* msg);  // records msg for bt_last_error_string(); returns code
 void note_kernel(const char* name);         // records the kernel instance a fused launch chose (bt_last_kernel_name)
-bool plan_only();                           // test seam (bt_debug_plan_only): launch_kernel records the name and launches nothing
+bool plan_only();                           // test seam (bt_debug_plan_only): launch_kernel records the launch and launches nothing
+void note_launch(dim3 grid, dim3 block, int lds, int lds_limit, uint64_t args_digest);   // plan-only: bt_debug_last_launch_record
+
+// A process-wide int knob: first read from an environment variable (`parse` gets getenv's answer, null when unset; env == null:
+// no variable), overridable at any time by a hook (set).
+class EnvKnob {
+ public:
+  constexpr EnvKnob(const char* env, int (*parse)(const char*)) : env_(env), parse_(parse) {}
+  int get() {
+    int v = v_.load(std::memory_order_relaxed);
+    if (v == INT_MIN) {
+      v = parse_(env_ ? getenv(env_) : nullptr);
+      v_.store(v, std::memory_order_relaxed);
+    }
+    return v;
+  }
+  void set(int v) { v_.store(v, std::memory_order_relaxed); }
+
+ private:
+  const char* env_;
+  int (*parse_)(const char*);
+  std::atomic<int> v_{INT_MIN};
+};
+// 64-bit FNV-1a over a kernel argument's bytes (plan-only records). A type with padding overloads digest_arg (FwdArgs).
+inline uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+  for (size_t i = 0; i < n; ++i) h = (h ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
+  return h;
+}
+template <typename T>
+uint64_t digest_arg(uint64_t h, const T& v) { return fnv1a(h, &v, sizeof(T)); }
 
 inline int check_launch(const char* who) {
   const hipError_t e = hipGetLastError();
@@ -51,6 +83,9 @@ int launch_kernel(void (*kern)(P...), const char* name, const char* who, dim3 gr
                   const A&... args) {
   if (plan_only()) {
     if (name) note_kernel(name);
+    uint64_t h = 14695981039346656037ull;
+    ((h = digest_arg(h, args)), ...);
+    note_launch(grid, block, lds, lds_limit, h);
     return BT_OK;
   }
   if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kern), lds_limit, who)) return rc;

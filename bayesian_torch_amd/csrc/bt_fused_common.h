@@ -58,6 +58,14 @@ struct FwdArgs {
   uint32_t inv_uh, inv_uw;   // ceil(2^32 / UH), ceil(2^32 / UW) (0: divide), split_fill_inverses
 };
 
+// Plan-only digest of the argument block: every field in declaration order, without the two padding holes (behind sample0, at the end).
+inline uint64_t digest_arg(uint64_t h, const FwdArgs& a) {
+  constexpr size_t hole = offsetof(FwdArgs, sample0) + sizeof(uint32_t), end = offsetof(FwdArgs, inv_uw) + sizeof(uint32_t);
+  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && sizeof(FwdArgs) == end + 4, "FwdArgs padding moved: name the holes here");
+  h = fnv1a(h, &a, hole);
+  return fnv1a(h, &a.call_base, end - offsetof(FwdArgs, call_base));
+}
+
 // The split-precision chains (bt_fused_split.hip, bt_fused_split_flip.hip), for every translation unit that calls them. Each works on
 // its own copy of the arguments: BT_OK and the plan that ran in `ran` when a flavour took the launch, 1 when none applies, < 0 on error.
 int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);

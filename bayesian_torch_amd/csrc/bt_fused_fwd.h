@@ -56,6 +56,27 @@ inline bool packed_ok(const FwdArgs& a) {
   return a.mu_pk && !((((uintptr_t)a.mu_pk | (uintptr_t)a.sig_pk) & 15u)) && a.w_elems < (1ll << 29) && a.x_elems < (1ll << 29);
 }
 
+// Host: the tile shapes of the patch-staging flavours (fast, split), widest first. A tile is NI images x R output rows x Wt output
+// columns of at most BM columns: images x ONE output row (a.row_taps: the split flavour's row tile), one output position of BM images
+// (one_position), whole images, a band of rows of one image, or a segment of one row; images, then rows, are given up until fits(NI, R,
+// Wt). clamp_images: never more images than the batch has. False when nothing fits.
+template <typename Fits>
+inline bool tile_shape(const FwdArgs& a, int BM, bool one_position, bool clamp_images, Fits fits, int* NI_out, int* R_out, int* Wt_out) {
+  int NI = 1, R = 1, Wt = 1;
+  bool drop_images = false, drop_rows = false;
+  if (a.row_taps) NI = BM / a.Wo, Wt = a.Wo;
+  else if (one_position) NI = BM;
+  else if (a.HoWo <= BM) NI = BM / a.HoWo, R = a.Ho, Wt = a.Wo, drop_images = true;
+  else if (a.Wo <= BM) R = BM / a.Wo, Wt = a.Wo, drop_rows = true;
+  else Wt = BM;
+  if (clamp_images && NI > a.B) NI = a.B;
+  if (NI < 1) return false;
+  while (drop_images && NI > 1 && !fits(NI, R, Wt)) --NI;
+  while (drop_rows && R > 1 && !fits(NI, R, Wt)) --R;
+  *NI_out = NI, *R_out = R, *Wt_out = Wt;
+  return fits(NI, R, Wt);
+}
+
 // Blocks are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2). Give every XCD a CONTIGUOUS range of
 // the logical block order, which is n-tile-major: an XCD then works on few n-tiles for all samples and m-tiles, so
 // its (mu, rho) working set stays in its own L2. Bijective for any grid size (cdna_hip_programming.md, T1).
@@ -80,9 +101,10 @@ __host__ __device__ inline int row_chunks(int x_lo, int x_hi, int W, int* xa_out
 // as a patch and gets room for the 2-image 7x7/s2 stem patch of 32x32 inputs (4 x 2 x 37 x 37 words).
 // (Flipout keeps two x tiles per stage: its 256-wide tile -- fast flavour only, x as a patch -- gets a 160-column budget:
 // room for the 37x37 patch of one 7x7/s2 stem image.)
+constexpr int x_words(int bm, bool flip) { return kBK * ((flip && bm > 128 ? 160 : bm <= 256 ? bm : 320) + 1); }
 template <int BM, bool FLIP = false>
 constexpr int x_words() {
-  return kBK * ((FLIP && BM > 128 ? 160 : BM <= 256 ? BM : 320) + 1);
+  return x_words(BM, FLIP);
 }
 
 template <int BN, int BM, bool FLIP>

@@ -3,9 +3,5 @@
 // own so the build stays parallel.
 #include "bt_fused_dispatch.h"
 namespace bt {
-int launch_reparam_updil(const FwdArgs& a, FwdArgs& ran, hipStream_t stream) {
-  const int rc = launch_split(a, ran, stream);
-  if (rc <= 0) return rc;
-  return launch_flavour_updil<false>(a, ran, stream);
-}
+int launch_reparam_updil(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream) { return run_fp32<false, false, true>(linear, a, ran, stream); }
 }  // namespace bt

@@ -1,35 +1,12 @@
 // Host-side helpers shared by the split flavour's translation units: the process-wide knobs, the tile geometry and the planner of
 // the general kernel's tile (bt_fused_split.hip, bt_fused_split_flip.hip). The launchers are in bt_fused_split_launch.h.
 #pragma once
-#include <limits.h>
 #include <stdlib.h>
-
-#include <atomic>
 
 #include "bt_fused_split.h"
 
 namespace bt {
 
-// A process-wide int knob: first read from an environment variable (`parse` gets getenv's answer, null when unset; env == null:
-// no variable), overridable at any time by a hook (set).
-class EnvKnob {
- public:
-  constexpr EnvKnob(const char* env, int (*parse)(const char*)) : env_(env), parse_(parse) {}
-  int get() {
-    int v = v_.load(std::memory_order_relaxed);
-    if (v == INT_MIN) {
-      v = parse_(env_ ? getenv(env_) : nullptr);
-      v_.store(v, std::memory_order_relaxed);
-    }
-    return v;
-  }
-  void set(int v) { v_.store(v, std::memory_order_relaxed); }
-
- private:
-  const char* env_;
-  int (*parse_)(const char*);
-  std::atomic<int> v_{INT_MIN};
-};
 extern EnvKnob g_bn32;   // bt_fused_split.hip: -1 automatic; 0 / 1 forced (BT_BN32, bt_debug_force_bn32)
 
 // ceil(2^32 / d): __umulhi(n, .) == n / d for every dividend n with n * d < 2^32. 0 when that cannot be promised (or d == 1):
@@ -110,7 +87,6 @@ static int split_row_mode(const FwdArgs& a) {
   if (gs == 1) return kept == a.W ? 3 : 0;
   return kept == a.W / 2 ? 4 : 0;
 }
-static bool split_rows_cover(const FwdArgs& a) { return split_row_mode(a) == 3; }
 // Tiles of whole images whose patch is the whole input plane (every row, every column): a plane is then one contiguous run of
 // H*W floats in memory AND in the patch, so with H*W % 4 == 0 the 16-byte fetch of XM 3 works on the flattened plane whatever
 // W is (ResNet50's 14x14 maps).
@@ -121,7 +97,7 @@ static bool split_plane_flat(const FwdArgs& a) {
   return gh == 1 && gw == 1 && kh == a.H && kw == a.W;
 }
 
-// Tile geometry as bt_fused_dispatch.h's fast_geometry, with the split flavour's capacity: the patch of ONE octet plane has to
+// Tile geometry as bt_fused_dispatch.h's fast_geometry (tile_shape), with the split flavour's capacity: the patch of ONE octet plane has to
 // fit XPO pixels. Fills the tile fields and returns the tile's live columns (0: does not fit).
 template <int BM, bool FLIP = false>
 static int split_geometry(FwdArgs& a) {
@@ -142,27 +118,7 @@ static int split_geometry(FwdArgs& a) {
     return NI * PHt * PWt <= XPO;
   };
   int NI, R, Wt;
-  if (a.row_taps) {   // images x one output row (bt_fused_split.hip: 2-row maps)
-    NI = BM / a.Wo, R = 1, Wt = a.Wo;
-    if (NI > a.B) NI = a.B;
-    if (NI < 1 || !fits(NI, R, Wt)) return 0;
-  } else if (a.HoWo == 1 || a.pixel_major) {
-    NI = BM, R = 1, Wt = 1;
-    if (NI > a.B) NI = a.B;
-    if (!fits(NI, R, Wt)) return 0;
-  } else if (a.HoWo <= BM) {
-    NI = BM / a.HoWo, R = a.Ho, Wt = a.Wo;  // whole images
-    if (NI > a.B) NI = a.B;
-    while (NI > 1 && !fits(NI, R, Wt)) --NI;
-    if (!fits(NI, R, Wt)) return 0;
-  } else if (a.Wo <= BM) {
-    NI = 1, R = BM / a.Wo, Wt = a.Wo;  // a band of rows of one image
-    while (R > 1 && !fits(NI, R, Wt)) --R;
-    if (!fits(NI, R, Wt)) return 0;
-  } else {
-    NI = 1, R = 1, Wt = BM;  // a segment of one row
-    if (!fits(NI, R, Wt)) return 0;
-  }
+  if (!tile_shape(a, BM, a.HoWo == 1 || a.pixel_major, true, fits, &NI, &R, &Wt)) return 0;   // (row tiles, bt_fused_split.hip: images x one output row of 2-row maps)
   a.t_NI = NI, a.t_R = R, a.t_Wt = Wt;
   a.n_bt = (a.B + NI - 1) / NI;
   a.n_rt = (a.pixel_major || a.row_taps) ? a.Ho : (a.HoWo > 1 ? (a.Ho + R - 1) / R : 1);
@@ -191,21 +147,11 @@ static bool quad_geometry(FwdArgs& a, int BM, long long xcap) {
   tap_window(a.KW, a.DW, a.SW, a.PW, a.W, a.Wo, false, &nw, &dxs);
   const long long PWt = (long long)(a.Wo - 1) * (dxs ? a.SW : 1) + dxs + 1;
   auto rows_px = [&](int R) { return ((long long)(R - 1) * (dys ? a.SH : 1) + dys + 1) * PWt; };
-  int NI, R;
-  long long tiles_per_sample;
-  if (a.HoWo <= BM) {   // whole images
-    NI = BM / a.HoWo, R = a.Ho;
-    if (NI > a.B) NI = a.B;
-    while (NI > 1 && NI * rows_px(R) > xcap) --NI;
-    if (NI * rows_px(R) > xcap) return false;
-    tiles_per_sample = (a.B + NI - 1) / NI;
-  } else {              // a band of whole rows of one image (ImageNet stems: 112 x 112 outputs -> 4 rows per 512-wide tile)
-    if (a.ep_pool) return false;   // (the pooled read-out needs whole images: the caller pools in a separate pass)
-    NI = 1, R = BM / a.Wo;
-    while (R > 1 && rows_px(R) > xcap) --R;
-    if (rows_px(R) > xcap) return false;
-    tiles_per_sample = (long long)a.B * ((a.Ho + R - 1) / R);
-  }
+  // whole images, or a band of whole rows of one image (ImageNet stems: 112 x 112 outputs -> 4 rows per 512-wide tile)
+  if (a.HoWo > BM && a.ep_pool) return false;   // (the pooled read-out needs whole images: the caller pools in a separate pass)
+  int NI, R, Wt;
+  if (!tile_shape(a, BM, false, true, [&](int ni, int r, int) { return ni * rows_px(r) <= xcap; }, &NI, &R, &Wt)) return false;
+  const long long tiles_per_sample = (long long)((a.B + NI - 1) / NI) * ((a.Ho + R - 1) / R);
   if ((double)a.M / ((double)tiles_per_sample * BM) < 0.75) return false;   // the wide tile must be filled
   if (a.ep_pool) {
     const int Wp = a.ep_Wp;

@@ -67,24 +67,31 @@ class Recorder:
         self.h = C.CDLL(_lib.LIB_PATH)      # the bt_debug_* hooks are outside include/bt_hip.h
         self.info = (C.c_int64 * 16)()
         self.lines = {}                     # variant -> [line]
+        self.pool_ep = m_ep = self.m.bt_epilogue(None, None, None, 0, 1, POOL_MAX_3x3_S2_P1)
+        self.pool_ref = C.byref(m_ep)
 
-    def _call(self, variant, key, fn, head, geom, S, flip, packed, pool, xss):
+    def _draws(self, flip, packed, inject=False):
+        """The draws of a call: on chip, packed images (``packed``) or the natural layout (``inject``)."""
+        m = self.m
+        if not (packed or inject):
+            return m.bt_draws(None, None, None, None, m.bt_rng(1, None, 0, 1, 0, 0))
+        flags = (m.DRAWS_EPS_PACKED | (m.DRAWS_SIGNS_PACKED if flip else 0)) if packed else 0
+        return m.bt_draws(P, P, P if flip else None, P if flip else None, m.bt_rng(1, None, 0, 1, 0, flags))
+
+    def _record(self, rc):
+        """What follows ``variant|case|rc|`` in a line."""
+        if rc != 0:
+            return "-|-"
+        self.L.bt_last_launch_info(self.info, 16)
+        return "%s|%s" % (self.L.bt_last_kernel_name().decode(), ",".join(str(int(v)) for v in self.info))
+
+    def _call(self, variant, key, fn, head, geom, S, flip, packed, pool, xss, inject=False, packs=True, x=P):
         m, L = self.m, self.L
-        par = m.bt_params(P, P, P, P, P, P, P, P, P, P, 0, 0)
-        if packed:
-            draws = m.bt_draws(P, P, P if flip else None, P if flip else None,
-                               m.bt_rng(1, None, 0, 1, 0, m.DRAWS_EPS_PACKED | (m.DRAWS_SIGNS_PACKED if flip else 0)))
-        else:
-            draws = m.bt_draws(None, None, None, None, m.bt_rng(1, None, 0, 1, 0, 0))
-        ep = m.bt_epilogue(None, None, None, 0, 1, POOL_MAX_3x3_S2_P1) if pool else None
+        par = m.bt_params(P, P, P, P, P, P, P, P, P if packs else None, P if packs else None, 0, 0)
+        draws = self._draws(flip, packed, inject)
         ws_bytes = m.WORKSPACE_BYTES + int(L.bt_fused_scratch_bytes(C.byref(geom), S))
-        rc = fn(*head, S, P, xss, C.byref(par), C.byref(draws), C.byref(ep) if ep else None, P, P, P, ws_bytes, None)
-        if rc == 0:
-            L.bt_last_launch_info(self.info, 16)
-            rec = "%s|%s" % (L.bt_last_kernel_name().decode(), ",".join(str(int(v)) for v in self.info))
-        else:
-            rec = "-|-"
-        self.lines[variant].append("%s|%s|%d|%s" % (variant, key, rc, rec))
+        rc = fn(*head, S, x, xss, C.byref(par), C.byref(draws), self.pool_ref if pool else None, P, P, P, ws_bytes, None)
+        self.lines[variant].append("%s|%s|%d|%s" % (variant, key, rc, self._record(rc)))
 
     def conv(self, variant, flip, packed, case, tag=""):
         Ci, Co, k, st, pad, H, B, S, pool, per_sample = case
