@@ -489,6 +489,8 @@ static int conv2d_bwd_impl(const bt_conv2d_geom* g, int32_t S, int32_t flipout, 
     if (!p->mu_w || (!lap && (!p->prior_mu_w || !p->prior_sigma_w))) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd_kl: needs mu_w and the weight priors");
   }
   if (!p->mu_packed || !p->sigma_packed || !p->rho_w) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: needs rho_w and the packed parameters (bt_pack_params)");
+  // dgrad reads the packs as float4 quads (the one access of this file wider than 4 bytes); a pack is a buffer of its own, never a slice
+  if ((((uintptr_t)p->mu_packed | (uintptr_t)p->sigma_packed) & 15u) != 0) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: mu_packed / sigma_packed must be 16-byte aligned");
   if (S <= 0 || g->B <= 0 || g->Ci <= 0 || g->Co <= 0 || g->groups <= 0 || g->Ci % g->groups || g->Co % g->groups) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: bad geometry");
   if ((dmu_w == nullptr) != (drho_w == nullptr)) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: dmu_w and drho_w go together");
   const bool inj = d->eps_w != nullptr;

@@ -215,6 +215,8 @@ __device__ __forceinline__ void kl_close(const FwdArgs& a, double t, int lane) {
 __device__ __forceinline__ double kl_slot_sum(const FwdArgs& a, int nslots, int lane) {  // slots lane, lane + 64, ... in index order
   double t = 0.0;
   for (int q = lane; q < nslots; q += 64) t += __hip_atomic_load(&a.slots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // calls leave the workspace zeroed (include/bt_hip.h); a loop of its own, so that the loads above stay back to back
+  for (int q = lane; q < nslots; q += 64) __hip_atomic_store(&a.slots[q], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return t;
 }
 

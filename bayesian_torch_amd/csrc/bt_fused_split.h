@@ -308,6 +308,9 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   const bool kl_block = a.do_kl && (int)blockIdx.x < a.kl_slices;
   float* const out_s = a.out + (long long)s * a.out_elems;
   const float* const res_s = a.ep_res ? a.ep_res + (long long)s * a.ep_res_stride : nullptr;
+  // The scalar output stage's two vector forms (below) store 8 / 16 bytes at even / quad element offsets: legal only from bases that
+  // are aligned so (a sliced result or residual is 4-byte aligned). Wave-uniform: else the element-wise form, the same values.
+  const uint32_t out_mis = (uint32_t)((uintptr_t)out_s | (uintptr_t)res_s);
   const bool relu = a.ep_relu != 0;
   if (stamp0 && tid == 0) dbg_[212] = __builtin_amdgcn_s_memtime();
 
@@ -1021,7 +1024,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
       // In all three forms below the residual values of a column group are fetched in ONE batch before its first store: written
       // as load -> add -> store per element, the loads cannot be moved above the stores (the compiler has to assume out and
       // residual alias) and every element pays a full memory round trip -- 17 K of layer3's 170 K cycles per workgroup.
-      if (a.row_taps && t_Wt == 2 && (a.Wo & 1) == 0) {
+      if (a.row_taps && t_Wt == 2 && (a.Wo & 1) == 0 && (out_mis & 7u) == 0) {
         // Row tiles of two-pixel rows: columns 2i, 2i + 1 are the two pixels of one image's row -- 8 contiguous bytes per channel.
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
@@ -1055,7 +1058,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
             }
           }
         }
-      } else if (!pix && !a.row_taps && HoWo == 4 && t_R == a.Ho && t_Wt == a.Wo) {
+      } else if (!pix && !a.row_taps && HoWo == 4 && t_R == a.Ho && t_Wt == a.Wo && (out_mis & 15u) == 0) {
         // Tiles of whole four-pixel images: columns 4i .. 4i + 3 are one image's plane -- 16 contiguous bytes per channel.
 #pragma unroll
         for (int j = 0; j < TM; ++j) {

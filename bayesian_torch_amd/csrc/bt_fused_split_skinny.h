@@ -221,6 +221,9 @@ __global__ __launch_bounds__(kSkinnyThreads, 3) void fused_split_skinny_kernel(c
         for (int j = 0; j < 8; ++j) v[j] = k + 64 * j < nslots ? __hip_atomic_load(&a.slots[k + 64 * j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) t += v[j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)   // calls leave the workspace zeroed (include/bt_hip.h)
+          if (k + 64 * j < nslots) __hip_atomic_store(&a.slots[k + 64 * j], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       t = wave_sum(t);
       double bt_ = 0.0;

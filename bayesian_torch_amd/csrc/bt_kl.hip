@@ -87,7 +87,10 @@ __global__ __launch_bounds__(kKlThreads) void kl_normal_kernel(KlSegs sg, float*
   __shared__ double seg_sum[BT_KL_MAX_SEGMENTS];
   for (int s = 0; s < sg.nseg; ++s) {
     double t = 0.0;
-    for (int b = sg.first_block[s] + (int)threadIdx.x; b < sg.first_block[s + 1]; b += kKlThreads) t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int b = sg.first_block[s] + (int)threadIdx.x; b < sg.first_block[s + 1]; b += kKlThreads) {
+      t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&slots[b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
+    }
     t = wave_sum(t);
     __syncthreads();   // (red is free again)
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;

@@ -150,7 +150,10 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg,
   for (int s = threadIdx.x >> 6; s < sg.nseg; s += kFpThreads / 64) {
     if (sg.kl_out[s] == nullptr) continue;
     double t = 0.0;
-    for (int b = sg.first_block[s] + lane; b < sg.first_block[s + 1]; b += 64) t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int b = sg.first_block[s] + lane; b < sg.first_block[s + 1]; b += 64) {
+      t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&slots[b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
+    }
     t = wave_sum(t);
     double bt_ = 0.0;
     const float *mb = sg.mu_b[s], *rb = sg.rho_b[s], *pb = sg.pmu_b[s], *qb = sg.psig_b[s];
