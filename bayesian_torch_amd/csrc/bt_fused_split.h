@@ -95,6 +95,316 @@ __device__ __forceinline__ int udiv_inv(int n, int d, uint32_t inv) {
 __device__ __forceinline__ uint32_t inv32(int d) { return 0xFFFFFFFFu / (uint32_t)d + 1u; }
 __device__ __forceinline__ int div_small(int n, int d) { return d == 1 ? n : d == 2 ? n >> 1 : n / d; }  // n >= 0; strides are 1 or 2 in practice
 
+// ---------------------------------------------------------------------------- one-pixel tiles
+// The XM == 1 Reparameterization instantiations (64 / 32 x 128 tiles, 8 producer waves) on launches whose input AND output planes
+// are one pixel -- a padded window over a 1x1 map, Linear -- run split_one_pixel_tile below instead of the general body. Such a tile
+// has one live tap and no window: an operand fragment of a lane (the 8 channels of octet 2 * step + lane half of its image) is 32
+// contiguous bytes of x that nobody else in the wave tile reads, so the CONSUMER loads it into registers a few steps ahead, splits it
+// there and feeds the MFMA (as the direct kernel does, bt_fused_split_direct.h) -- no x image in LDS, no tap table, no patch or item
+// decode, no buffer clear, and the producers draw and stage weights only. Same K order (consecutive octets in pairs), same pieces, same
+// terms in the same order, same output-stage operations: bit for bit the general body's result (tests/test_gpu_one_pixel_tiles.py
+// holds it to the xm=0 instantiation). Any other geometry on a 1x1 input plane (an output larger than its input) takes the general body.
+#ifndef BT_ONE_PIXEL_STEPS
+#define BT_ONE_PIXEL_STEPS 4
+#endif
+// K16 steps per barrier stage (a multiple of 4). The x buffers' room would hold stages of 8 or 12 steps; measured inside the cfg3 graph
+// (profiles/r08_one_pixel_tiles_ab.txt) 8-step stages were no faster than 4-step ones -- fewer barriers, but a longer first stage before the
+// consumers start and a longer last one after the producers are done -- so the stage stays one group of four steps.
+constexpr int kOnePixelSteps = BT_ONE_PIXEL_STEPS;
+
+__device__ __forceinline__ uint32_t guarded_off(bool in, uint32_t off) {  // (bit arithmetic on purpose: guard_off in the kernel below)
+  const uint32_t m = 0u - (uint32_t)in;
+  return (off & m) | (0x80000000u & ~m);
+}
+
+// Launch-uniform: is this a launch of one-pixel tiles, and which tap of the window meets the pixel?
+__device__ __forceinline__ bool one_pixel_tile(const FwdArgs& a, int* tap) {
+  if (a.HoWo != 1 || a.HW != 1 || a.t_R != 1 || a.t_Wt != 1 || a.m_tiles != a.n_bt || a.updil) return false;
+  const int kh = a.DH == 1 ? a.PH : a.PH / a.DH, kw = a.DW == 1 ? a.PW : a.PW / a.DW;  // input row 0 = -PH + kh * DH
+  *tap = kh * a.KW + kw;
+  return kh * a.DH == a.PH && kh < a.KH && kw * a.DW == a.PW && kw < a.KW && (a.Cig >> 3) > 0;
+}
+
+template <int BN, int NP, int NPW, bool INJ>
+__device__ __forceinline__ void split_one_pixel_tile(const FwdArgs& a, const int tap) {
+  constexpr int BM = 128, KS = kOnePixelSteps, kProducers = 64 * NPW, TN = BN / 32;
+  constexpr int W_STEP = 2 * NP * BN * 16, W_HALF = NP * BN * 16, W_PIECE = BN * 16, W_RING = KS * W_STEP;
+  constexpr int XD = 4;  // x ring: steps in flight per lane; the consumers walk a stage in groups of XD steps
+  static_assert(KS % XD == 0, "whole groups per stage");
+  static_assert(2 * W_RING + 3 * BN * 4 <= split_stage_cap<BN, BM, NP>(), "two weight images + the channel constants fit the operand buffers");
+  extern __shared__ __attribute__((aligned(16))) char smem_c[];   // [2][W_RING] | bias | scale | shift
+  float* const bias0 = reinterpret_cast<float*>(smem_c + 2 * W_RING);
+  float* const osc = bias0 + BN;
+  float* const osh = bias0 + 2 * BN;
+
+  unsigned long long* const dbg_ = kStamps ? a.dbg : nullptr;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool stamp0 = dbg_ && blockIdx.x == 0 && (tid == 0 || tid == 256);
+  if (stamp0 && tid == 0) dbg_[210] = __builtin_amdgcn_s_memtime();
+  const bool producer = wave >= 4;
+  const int ptid = producer ? tid - 256 : tid;
+  const int li = lane & 31, lh = lane >> 5;
+
+  int L = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, a.total_blocks));
+  int Lq = udiv_inv(L, a.m_tiles, a.inv_m_tiles);
+  const int mt = __builtin_amdgcn_readfirstlane(L - Lq * a.m_tiles);
+  L = Lq, Lq = udiv_inv(L, a.S, a.inv_S);
+  const int s = __builtin_amdgcn_readfirstlane(L - Lq * a.S);
+  L = Lq, Lq = udiv_inv(L, a.n_tiles, a.inv_n_tiles);
+  const int nt = __builtin_amdgcn_readfirstlane(L - Lq * a.n_tiles);
+  const int g = __builtin_amdgcn_readfirstlane(Lq);
+  const int n0 = nt * BN, b0 = mt * a.t_NI;   // tile column c = image b0 + c
+  const uint32_t sample = a.sample0 + (uint32_t)s;
+  const int T = a.T, Cig = a.Cig, G8 = Cig >> 3;
+  const RngKey key_w = weight_key(a);
+
+  // Stage shape: KS steps = 2 KS octets, or all of a short K in whole groups of four steps (the octets past the last are staged as zeros)
+  const int NO = G8 < 2 * KS ? (G8 + 7) & ~7 : 2 * KS;
+  const int NSTEPS = (G8 + 1) >> 1, NS = (NSTEPS + KS - 1) / KS;
+
+  const float* const xs = a.x + (long long)s * a.x_sample_stride;
+  constexpr uint32_t kOOB = 0x80000000u;
+  const int pk_bytes = a.Co * T * Cig * 4;
+  const __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.mu_pk), 0, pk_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sig_pk), 0, pk_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)(a.x_elems * 4), 0x00020000);
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_ep =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
+  auto ldf4 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0)); };
+  const bool kl_block = a.do_kl && (int)blockIdx.x < a.kl_slices;
+  if (stamp0 && tid == 0) dbg_[211] = dbg_[212] = __builtin_amdgcn_s_memtime();
+
+  if (producer) {
+    // =================================================== PRODUCERS ===========================================================
+    // Weight units as in the general body's one-tap form: u = ptid + kProducers i -> (channel quad, octet of the stage) fastest, then
+    // the row, so consecutive lanes read consecutive 16-byte pieces of a row of the packed tensors.
+    constexpr int UMAX = (2 * BN * 2 * KS + kProducers - 1) / kProducers;
+    const int nunits = 2 * BN * NO;
+    const uint32_t inv_no = inv32(NO);
+    uint32_t e_off[UMAX];  // draw index (== element offset in the packed tensors) of the unit at octet 0 of stage 0
+    int l_off[UMAX];       // LDS byte offset inside a weight image; -1: no slot
+    int u_ol[UMAX];        // octet inside the stage
+    bool u_live[UMAX];     // wave-uniform: some lane of this wave holds a row that exists (else the unit only stages zeros)
+#pragma unroll
+    for (int i = 0; i < UMAX; ++i) {
+      const int u = ptid + kProducers * i;
+      const int uu = u < nunits ? u : 0;
+      const int cq = uu & 1, t2 = uu >> 1;
+      const int n = (int)__umulhi((uint32_t)t2, inv_no), ol = t2 - n * NO;
+      const int co_g = n0 + n;
+      const bool rv = co_g < a.Cog;
+      const uint32_t co = (uint32_t)(g * a.Cog + (rv ? co_g : 0));
+      e_off[i] = rv ? (co * (uint32_t)T + (uint32_t)tap) * (uint32_t)Cig + (uint32_t)(8 * ol + 4 * cq) : (kOOB >> 2);
+      l_off[i] = u < nunits ? (ol >> 1) * W_STEP + (ol & 1) * W_HALF + (n ^ (ol & 7)) * 16 + cq * 8 : -1;   // (row slots swizzled with the plane index, as in the general body)
+      u_ol[i] = ol;
+      u_live[i] = __builtin_amdgcn_readfirstlane(__ballot(rv && u < nunits) != 0ull ? 1 : 0) != 0;
+    }
+    if (stamp0) dbg_[213] = dbg_[214] = __builtin_amdgcn_s_memtime();
+    float4 mu[UMAX], rs[UMAX];
+    [[maybe_unused]] float4 epl[INJ ? UMAX : 1];
+    auto load_w = [&](int st) {
+      const int oct0 = st * NO;
+#pragma unroll
+      for (int i = 0; i < UMAX; ++i) {
+        if (u_live[i]) {  // wave-uniform
+          const bool in = l_off[i] >= 0 && oct0 + u_ol[i] < G8 && e_off[i] != (kOOB >> 2);
+          const uint32_t sb = guarded_off(in, 4u * (e_off[i] + (uint32_t)(8 * oct0)));
+          mu[i] = ldf4(r_mu, sb), rs[i] = ldf4(r_rs, sb);
+          if constexpr (INJ) epl[i] = ldf4(r_ep, sb);  // masked units read 0.0
+        }
+      }
+    };
+    load_w(0);
+    if (stamp0) dbg_[215] = __builtin_amdgcn_s_memtime();
+    const bool pstamp = dbg_ && blockIdx.x == 0 && tid == 256;
+    for (int st = 0; st < NS; ++st) {
+      if (pstamp && st < 60) dbg_[128 + 2 * st] = __builtin_amdgcn_s_memtime();
+      char* const Wt = smem_c + (st & 1) * W_RING;
+      const int oct0 = st * NO;
+      float ep[UMAX][4];
+#pragma unroll
+      for (int i = 0; i < UMAX; ++i)
+        if (u_live[i]) {  // wave-uniform
+          if constexpr (INJ) ep[i][0] = epl[i].x, ep[i][1] = epl[i].y, ep[i][2] = epl[i].z, ep[i][3] = epl[i].w;
+          else philox_normal4(key_w, sample, (e_off[i] + (uint32_t)(8 * oct0)) >> 2, ep[i]);
+        }
+#pragma unroll
+      for (int i = 0; i < UMAX; ++i) {
+        if (u_live[i]) {  // wave-uniform
+          const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
+          if constexpr (NP == 1) {
+            float w4[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j]));
+            if (l_off[i] >= 0) *reinterpret_cast<uint2*>(Wt + l_off[i]) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
+          } else {
+            uint32_t wh[4], wm_[4], wl[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)  // masked units loaded zeros: w = 0 + 0 * eps = 0
+              split_pieces(__fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j])), wh[j], wm_[j], wl[j]);
+            if (l_off[i] >= 0) {
+              char* const dst = Wt + l_off[i];
+              *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
+              if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+              if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
+            }
+          }
+        } else if (l_off[i] >= 0) {  // rows past the group's channels: nothing is cleared up front, so the slots get their zeros here
+          char* const dst = Wt + l_off[i];
+#pragma unroll
+          for (int p = 0; p < NP; ++p) *reinterpret_cast<uint2*>(dst + p * W_PIECE) = make_uint2(0u, 0u);
+        }
+      }
+      if (st + 1 < NS) load_w(st + 1);  // next stage's loads: in flight across the barrier and the draws
+      if (pstamp && st < 60) dbg_[128 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
+      __syncthreads();  // stage st staged; the consumers have left stage st - 1 (the image that stage st + 1 overwrites)
+    }
+    // bias draw + output-stage constants of this workgroup's channels, while the consumers run the last stage
+    if (ptid < BN) {
+      const ChannelConsts c = channel_consts<false, INJ>(a, key_w, s, g, n0 + ptid);
+      bias0[ptid] = c.bias0, osc[ptid] = c.scale, osh[ptid] = c.shift;
+    }
+    __syncthreads();
+  } else {
+    // =================================================== CONSUMERS ===========================================================
+    // Wave w owns tile columns 32 w .. 32 w + 31 (lane li = the image) x all BN channels.
+    const int wm = wave;
+    KlSlice<1024> kls;
+    if (kl_block) kls.open(a, ptid);
+    const int col = wm * 32 + li, b = b0 + col;
+    const bool xok = col < a.t_NI && b < a.B;
+    const uint32_t xb = (uint32_t)(4 * (b * a.Ci + g * Cig));   // this lane's image, first channel of the group
+    float xr[XD][8];
+    auto load_x = [&](float (&d)[8], int step) {   // octet 2 * step + lh; past the last octet (and dead columns): zeros
+      const int o = 2 * step + lh;
+      const bool in = xok && o < G8;
+      const float4 v0 = ldf4(r_x, guarded_off(in, xb + (uint32_t)(32 * o))), v1 = ldf4(r_x, guarded_off(in, xb + (uint32_t)(32 * o + 16)));
+      d[0] = v0.x, d[1] = v0.y, d[2] = v0.z, d[3] = v0.w, d[4] = v1.x, d[5] = v1.y, d[6] = v1.z, d[7] = v1.w;
+    };
+#pragma unroll
+    for (int q = 0; q < XD; ++q) {
+      load_x(xr[q], q);
+      __builtin_amdgcn_sched_barrier(0);   // in step order: issued last-step-first, step 0 of EVERY group would wait for all loads in flight (one wait count serves both ways into the loop)
+    }
+    int wlq[4];  // this lane's row slot inside the (step, half) plane, swizzled like the producers' writes: the swizzle has period 4 in the step
+#pragma unroll
+    for (int q = 0; q < 4; ++q) wlq[q] = lh * W_HALF + (li ^ ((2 * q + lh) & 7)) * 16;
+
+    f32x16 acc[TN];
+#pragma unroll
+    for (int i = 0; i < TN; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+    const bool cstamp = dbg_ && blockIdx.x == 0 && tid == 0;
+    if (cstamp) dbg_[216] = dbg_[0] = __builtin_amdgcn_s_memtime();
+    for (int st = 0; st < NS; ++st) {
+      __syncthreads();  // stage st staged
+      if (cstamp && st < 60) dbg_[2 + 2 * st] = __builtin_amdgcn_s_memtime();
+      const char* const Wt = smem_c + (st & 1) * W_RING;
+      const int step0 = st * KS;
+      const int nstep = NSTEPS - step0 < KS ? NSTEPS - step0 : KS;
+      // Groups of four steps, straight-line code inside a group (a branch per step made the compiler drain every x load in flight at
+      // each block boundary). The steps that pad the last group meet zero weights (the producers stage whole groups) and zero x.
+      for (int q4 = 0; q4 < nstep; q4 += 4) {
+        const char* const wq = Wt + q4 * W_STEP;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          // the step's weight fragments: their LDS round trip runs behind the split of the x fragment below
+          bf16x8 wf[TN][NP];
+#pragma unroll
+          for (int i = 0; i < TN; ++i)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) wf[i][p] = *reinterpret_cast<const bf16x8*>(wq + wlq[u] + u * W_STEP + p * W_PIECE + i * 32 * 16);
+          const float(&v)[8] = xr[u];
+          bf16x8 xf[NP];
+          if constexpr (NP == 1) {
+            xf[0] = __builtin_bit_cast(bf16x8, make_uint4(rne_pair(v[0], v[1]), rne_pair(v[2], v[3]), rne_pair(v[4], v[5]), rne_pair(v[6], v[7])));
+          } else {
+            uint32_t ph[8], pm[8], pl[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) split_pieces(v[c], ph[c], pm[c], pl[c]);
+            xf[0] = __builtin_bit_cast(bf16x8, make_uint4(pack_hi16(ph[1], ph[0]), pack_hi16(ph[3], ph[2]), pack_hi16(ph[5], ph[4]), pack_hi16(ph[7], ph[6])));
+            xf[1] = __builtin_bit_cast(bf16x8, make_uint4(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]), pack_hi16(pm[5], pm[4]), pack_hi16(pm[7], pm[6])));
+            if constexpr (NP == 3)
+              xf[2] = __builtin_bit_cast(bf16x8, make_uint4(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]), pack_hi16(pl[5], pl[4]), pack_hi16(pl[7], pl[6])));
+          }
+          load_x(xr[u], step0 + q4 + u + 4);   // the slot's next step
+#pragma unroll
+          for (int i = 0; i < TN; ++i) {
+            // D[pixel][channel]: x is the A operand, W the B operand; terms in decreasing weight
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[i][0], acc[i], 0, 0, 0);
+            if constexpr (NP >= 2) {
+              acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[i][1], acc[i], 0, 0, 0);
+              acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[1], wf[i][0], acc[i], 0, 0, 0);
+            }
+            if constexpr (NP == 3) {
+              acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[0], wf[i][2], acc[i], 0, 0, 0);
+              acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[1], wf[i][1], acc[i], 0, 0, 0);
+              acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[2], wf[i][0], acc[i], 0, 0, 0);
+            }
+          }
+          // (without it the compiler splits all four steps ahead of the group's MFMAs and sinks the x loads behind them: every group
+          //  then waits for loads it has only just issued)
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (cstamp && st < 60) dbg_[2 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
+      if (kl_block) kls.group(a);
+    }
+    if (cstamp) dbg_[1] = __builtin_amdgcn_s_memtime();
+
+    // ---- output stage: register r of acc[i] = image (r & 3) + 8 (r >> 2) + 4 lh of this wave's 32, channel 32 i + li. The residual
+    // values are fetched in one batch BEFORE the barrier that publishes the channel constants: their round trip is not exposed. ----
+    float* const out_s = a.out + (long long)s * a.out_elems;
+    const float* const res_s = a.ep_res ? a.ep_res + (long long)s * a.ep_res_stride : nullptr;
+    const bool relu = a.ep_relu != 0;
+    const int c_lim = (a.t_NI < a.B - b0 ? a.t_NI : a.B - b0) - wm * 32 - 4 * lh;   // register r is an image that exists when its row (r & 3) + 8 (r >> 2) < c_lim
+    const uint32_t oi0 = (uint32_t)((b0 + wm * 32 + 4 * lh) * a.Co + g * a.Cog + n0 + li);
+    bool cok[TN];
+#pragma unroll
+    for (int i = 0; i < TN; ++i) cok[i] = n0 + i * 32 + li < a.Cog;
+    float rr[16][TN];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2);
+#pragma unroll
+      for (int i = 0; i < TN; ++i) {
+        rr[r][i] = 0.f;
+        if (res_s && row < c_lim && cok[i]) rr[r][i] = res_s[oi0 + (uint32_t)(row * a.Co + i * 32)];
+      }
+    }
+    if (kl_block) {  // every consumer wave stores its partial write-through and drains the store; thread 0 takes the workgroup's ticket
+      const double wsum = kls.rest(a);
+      if (lane == 0) __hip_atomic_store(&a.slots[(int)blockIdx.x * 4 + wave], wsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();  // the producers have staged bias / output-stage constants; every consumer wave has published its KL partial
+    if (kl_block && wave == 0) {
+      int last = 0;
+      if (lane == 0) last = (__hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)a.kl_slices - 1u) ? 1 : 0;
+      if (__builtin_amdgcn_readfirstlane(last)) kl_close(a, kl_slot_sum(a, 4 * a.kl_slices, lane), lane);
+    }
+    if (cstamp) dbg_[120] = dbg_[121] = dbg_[122] = __builtin_amdgcn_s_memtime();
+    float bsv[TN], scv[TN], shv[TN];
+#pragma unroll
+    for (int i = 0; i < TN; ++i) bsv[i] = bias0[i * 32 + li], scv[i] = osc[i * 32 + li], shv[i] = osh[i * 32 + li];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+#pragma unroll
+      for (int i = 0; i < TN; ++i) {
+        if ((r & 3) + 8 * (r >> 2) < c_lim && cok[i]) {
+          float v = __fadd_rn(__fmul_rn(__fadd_rn(acc[i][r], bsv[i]), scv[i]), shv[i]);
+          if (res_s) v = __fadd_rn(v, rr[r][i]);
+          v = (relu && v < 0.f) ? 0.f : v;
+          out_s[oi0 + (uint32_t)(((r & 3) + 8 * (r >> 2)) * a.Co + i * 32)] = v;
+        }
+      }
+    }
+    if (cstamp) dbg_[123] = dbg_[126] = __builtin_amdgcn_s_memtime();
+  }
+}
+
 // NP: pieces per value (3: exact split, 6 product terms; 2: 3 terms; 1: the bf16 mode -- every operand value rounded ONCE to nearest
 // even (rne_pair, not the truncation of split_pieces: one truncated piece is biased toward zero), one product term; same K order, tile
 // plan, draws and output stage, bt_fused_split_bf16.hip). 4 consumer waves (64 x BM/4 each) + NPW producer waves
@@ -137,6 +447,14 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   static_assert((BN == 64 && (BM == 512 || BM == 256 || BM == 128)) || (BN == 32 && BM == 128 && !FLIP), "tile shapes of this flavour");
   static_assert(!FLIP || ((BM == 256 || BM == 128) && NP == 3), "Flipout: the 64 x 256 / 64 x 128 tiles, exact split");
   static_assert(NP >= 1 && NP <= 3 && (NP != 1 || !INJ), "pieces per value; the bf16 mode draws on chip");
+  if constexpr (XM == 1 && !FLIP) {  // one-pixel tiles: a body of their own (above)
+    static_assert(BM == 128 && NPW == 8, "the tile of the 1x1 planes");
+    int tap1;
+    if (one_pixel_tile(a, &tap1)) {  // launch-uniform
+      split_one_pixel_tile<BN, NP, NPW, INJ>(a, tap1);
+      return;
+    }
+  }
   constexpr int kProducers = 64 * NPW, kThreadsAll = 256 + kProducers;
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32;
   constexpr int NOP = FLIP ? 2 : 1;            // weight operands (images per stage) = accumulator sets
