@@ -66,6 +66,10 @@ class bt_updil(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("uh", "uw", "lo_h", "hi_h", "lo_w", "hi_w")]
 
 
+class bt_dwin(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kd", "D", "sd", "dd", "pd")]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -93,6 +97,8 @@ _PROTOS = {
     "bt_flipout_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32] + _FWD_TAIL),
     "bt_reparam_conv2d_updil_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_updil), C.c_int32] + _FWD_TAIL),
     "bt_flipout_conv2d_updil_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_updil), C.c_int32] + _FWD_TAIL),
+    "bt_reparam_conv2d_dwin_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_dwin), C.c_int32] + _FWD_TAIL),
+    "bt_flipout_conv2d_dwin_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_dwin), C.c_int32] + _FWD_TAIL),
     "bt_kl_normal": (C.c_int, [C.c_int32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64),
                                C.POINTER(C.c_int32), C.c_uint32, _vp, _vp, C.c_size_t, _vp]),
     "bt_pack_sync": (C.c_int, [C.c_int32, C.POINTER(bt_pack_seg), _vp, C.c_size_t, _vp]),

@@ -5,10 +5,11 @@
 
 namespace bt {
 // The fp32 launchers by (Flipout, kind): on-chip draws, natural-layout injected draws, an input-dilated image (bt_*_conv2d_updil_fwd;
-// on-chip draws). Each launches the layer and, on BT_OK, leaves the plan that ran (tile geometry, grid) in `ran`.
+// on-chip draws), a depth-windowed input (bt_*_conv2d_dwin_fwd; on-chip draws). Each launches the layer and, on BT_OK, leaves the plan that ran (tile geometry, grid) in `ran`.
 typedef int Launcher(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);
-Launcher launch_reparam, launch_reparam_inj, launch_reparam_updil, launch_flipout, launch_flipout_inj, launch_flipout_updil;
-static Launcher* const kLaunchers[2][3] = {{launch_reparam, launch_reparam_inj, launch_reparam_updil}, {launch_flipout, launch_flipout_inj, launch_flipout_updil}};
+Launcher launch_reparam, launch_reparam_inj, launch_reparam_updil, launch_reparam_dwin, launch_flipout, launch_flipout_inj, launch_flipout_updil, launch_flipout_dwin;
+static Launcher* const kLaunchers[2][4] = {{launch_reparam, launch_reparam_inj, launch_reparam_updil, launch_reparam_dwin},
+                                           {launch_flipout, launch_flipout_inj, launch_flipout_updil, launch_flipout_dwin}};
 
 EnvKnob g_force_generic{"BT_FORCE_GENERIC", [](const char* e) { return e ? 1 : 0; }};   // the fast flavour off: every fp32 launch takes the general kernel
 static unsigned long long* g_dbg = nullptr;
@@ -16,7 +17,7 @@ static thread_local long long g_launch_info[16] = {};
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // One forward call as the C ABI hands it over. u: the input dilation and explicit padding of bt_*_conv2d_updil_fwd (g holds the REAL
-// input dims), or null.
+// input dims), or null. w: the depth window of bt_*_conv2d_dwin_fwd (g describes the launch over the VIRTUAL, unfolded operand), or null.
 struct Call {
   bool flip, linear;
   const bt_conv2d_geom& g;
@@ -31,12 +32,16 @@ struct Call {
   size_t ws_bytes;
   const char* who;   // the entry point's name, for its messages
   const bt_updil* u;
+  const bt_dwin* w;
   // an input-dilated launch convolves the VIRTUAL image: the real one with u - 1 zeros between its pixels, padded by lo / hi
   long long virt_H() const { return u ? (long long)(g.H - 1) * u->uh + 1 + u->lo_h + u->hi_h : g.H; }
   long long virt_W() const { return u ? (long long)(g.W - 1) * u->uw + 1 + u->lo_w + u->hi_w : g.W; }
   int out_H() const { return (int)((virt_H() + 2 * g.ph - (long long)g.dh * (g.kh - 1) - 1) / g.sh + 1); }
   int out_W() const { return (int)((virt_W() + 2 * g.pw - (long long)g.dw * (g.kw - 1) - 1) / g.sw + 1); }
   bool updil() const { return u && (u->uh > 1 || u->uw > 1 || u->lo_h || u->hi_h || u->lo_w || u->hi_w); }   // (else: the plain convolution, launch for launch)
+  bool dwin() const { return w && !(w->kd == 1 && w->D == 1 && w->pd == 0); }   // (else: the plain convolution, launch for launch)
+  long long out_D() const { return ((long long)w->D + 2ll * w->pd - (long long)w->dd * (w->kd - 1) - 1) / w->sd + 1; }
+  long long real_x_elems() const { return dwin() ? (long long)(g.B / out_D()) * (g.Ci / w->kd) * w->D * g.H * g.W : (long long)g.B * g.Ci * g.H * g.W; }
   bool packed_eps() const { return (d->rng.flags & BT_DRAWS_EPS_PACKED) != 0; }
   bool pooled() const { return ep && ep->pool != BT_POOL_NONE; }
 
@@ -60,6 +65,16 @@ struct Call {
       if (u->uh < 1 || u->uw < 1) return bad("input dilation must be >= 1");
       if (u->lo_h < 0 || u->hi_h < 0 || u->lo_w < 0 || u->hi_w < 0) return bad("negative explicit padding (a crop: materialise the input instead)");
       if (g.ph != 0 || g.pw != 0) return bad("ph / pw must be 0: the padding of the dilated image is explicit (lo / hi)");
+    }
+    if (w) {
+      if (w->kd < 1 || w->D < 1 || w->sd < 1 || w->dd < 1) return bad("depth taps, depth, depth stride and depth dilation must be >= 1");
+      if (w->pd < 0) return bad("negative depth padding");
+      const long long num = (long long)w->D + 2ll * w->pd - (long long)w->dd * (w->kd - 1) - 1;
+      if (num < 0 || out_D() < 1) return bad("empty output depth");
+      if (out_D() >= (1ll << 30) || g.B % out_D()) return bad("g->B is not a multiple of the output depth (B * Do launch images)");
+      if ((g.Ci / g.groups) % w->kd) return bad("g->Ci / groups is not a multiple of kd (Ci * kd launch channels)");
+      if ((long long)g.B * g.Ci * g.H * g.W >= (1ll << 30) || (long long)(g.B / out_D()) * (g.Ci / w->kd) * w->D * g.H * g.W >= (1ll << 30))
+        return bad("a real or unfolded x of 2^30 elements or more exceeds the kernel's 32-bit offsets");
     }
     if (kl_out) {
       if (!p->prior_mu_w || !p->prior_sigma_w) return bad("kl_out given but weight priors are NULL");
@@ -100,6 +115,14 @@ struct Call {
       if (d->eps_w || d->eps_b || d->sign_in || d->sign_out || eps_packed)
         return set_error(BT_ERR_UNSUPPORTED, "input-dilated launch: on-chip draws only (supplied draws take the materialised input)");
       if (pooled()) return set_error(BT_ERR_UNSUPPORTED, "input-dilated launch: no fused max-pool");
+    }
+    if (dwin()) {   // nothing is launched for what the depth-window fetch does not cover
+      auto unsupported = [&](const char* what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return set_error(BT_ERR_UNSUPPORTED, msg);
+      };
+      if (d->eps_w || d->eps_b || d->sign_in || d->sign_out || eps_packed) return unsupported("on-chip draws only (supplied draws take the unfolded input)");
+      if (pooled()) return unsupported("no fused max-pool on a depth-window launch");
     }
     if ((p->mu_packed == nullptr) != (p->sigma_packed == nullptr)) return bad("mu_packed and sigma_packed must both be given or both be NULL");
     // 32-bit index budget of the kernel (tile indices, hashed sign indices, Philox block index)
@@ -149,7 +172,8 @@ struct Call {
     const long long M = (long long)g.B * Ho * Wo;
     a.Cig = g.Ci / g.groups, a.Cog = g.Co / g.groups;
     const long long K = (long long)a.Cig * g.kh * g.kw;
-    a.x_elems = (long long)g.B * g.Ci * g.H * g.W;   // (the REAL elements of an input-dilated launch: what x holds and what the input signs index)
+    a.x_elems = real_x_elems();   // (the REAL elements of an input-dilated / depth-window launch: what x holds and what the input signs index)
+    if (dwin()) a.dwin = 1, a.KD = w->kd, a.D = w->D, a.Do = (int)out_D(), a.SD = w->sd, a.DD = w->dd, a.PD = w->pd, a.Cigr = a.Cig / w->kd;
     a.out_elems = M * g.Co;
     a.w_elems = (long long)g.Co * K;
     a.M = (int)M, a.K = (int)K, a.S = S;
@@ -175,7 +199,7 @@ struct Call {
   // Packed draws: the split chain alone (it launches nothing when it declines). Else the fp32 launcher of the call's kind; those with
   // on-chip draws try the split chain first themselves.
   int dispatch(const FwdArgs& a, FwdArgs& ran, hipStream_t stream) const {
-    if (!packed_eps()) return kLaunchers[flip][updil() ? 2 : d->eps_w ? 1 : 0](linear, a, ran, stream);
+    if (!packed_eps()) return kLaunchers[flip][dwin() ? 3 : updil() ? 2 : d->eps_w ? 1 : 0](linear, a, ran, stream);
     const int rc = flip ? launch_split_flip(a, ran, stream) : launch_split(a, ran, stream);
     if (rc != 1) return rc;
     char msg[256];
@@ -220,33 +244,44 @@ static bt_conv2d_geom linear_geom(int B, int In, int Out) {
 extern "C" int bt_reparam_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, const float* x, int64_t x_sample_stride,
                                      const bt_params* p, const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes,
                                      bt_stream_t stream) {
-  return bt::run({false, true, bt::linear_geom(B, In, Out), S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_linear_fwd", nullptr}, stream);
+  return bt::run({false, true, bt::linear_geom(B, In, Out), S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_linear_fwd", nullptr, nullptr}, stream);
 }
 extern "C" int bt_flipout_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, const float* x, int64_t x_sample_stride,
                                      const bt_params* p, const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes,
                                      bt_stream_t stream) {
-  return bt::run({true, true, bt::linear_geom(B, In, Out), S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_linear_fwd", nullptr}, stream);
+  return bt::run({true, true, bt::linear_geom(B, In, Out), S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_linear_fwd", nullptr, nullptr}, stream);
 }
 extern "C" int bt_reparam_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
                                      const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g) return bt::set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_fwd: null geometry");
-  return bt::run({false, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_conv2d_fwd", nullptr}, stream);
+  return bt::run({false, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_conv2d_fwd", nullptr, nullptr}, stream);
 }
 extern "C" int bt_flipout_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
                                      const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g) return bt::set_error(BT_ERR_BAD_ARG, "bt_flipout_conv2d_fwd: null geometry");
-  return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_fwd", nullptr}, stream);
+  return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_fwd", nullptr, nullptr}, stream);
 }
 
 extern "C" int bt_reparam_conv2d_updil_fwd(const bt_conv2d_geom* g, const bt_updil* u, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
                                            const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g || !u) return bt::set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_updil_fwd: null geometry");
-  return bt::run({false, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_conv2d_updil_fwd", u}, stream);
+  return bt::run({false, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_conv2d_updil_fwd", u, nullptr}, stream);
 }
 extern "C" int bt_flipout_conv2d_updil_fwd(const bt_conv2d_geom* g, const bt_updil* u, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
                                            const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g || !u) return bt::set_error(BT_ERR_BAD_ARG, "bt_flipout_conv2d_updil_fwd: null geometry");
-  return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_updil_fwd", u}, stream);
+  return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_updil_fwd", u, nullptr}, stream);
+}
+
+extern "C" int bt_reparam_conv2d_dwin_fwd(const bt_conv2d_geom* g, const bt_dwin* w, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
+                                          const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
+  if (!g || !w) return bt::set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_dwin_fwd: null geometry");
+  return bt::run({false, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_reparam_conv2d_dwin_fwd", nullptr, w}, stream);
+}
+extern "C" int bt_flipout_conv2d_dwin_fwd(const bt_conv2d_geom* g, const bt_dwin* w, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
+                                          const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
+  if (!g || !w) return bt::set_error(BT_ERR_BAD_ARG, "bt_flipout_conv2d_dwin_fwd: null geometry");
+  return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_dwin_fwd", nullptr, w}, stream);
 }
 
 extern "C" size_t bt_fused_scratch_bytes(const bt_conv2d_geom* g, int32_t S) {

@@ -56,14 +56,24 @@ struct FwdArgs {
   int updil;
   int UH, UW, LH, LW, Hr, Wr, HWr;
   uint32_t inv_uh, inv_uw;   // ceil(2^32 / UH), ceil(2^32 / UW) (0: divide), split_fill_inverses
+  // depth-window launches (bt_*_conv2d_dwin_fwd: Conv3d without the depth-unfolded copy). B, Ci, Cig, K above are the VIRTUAL operand's
+  // -- B = real batch x Do images, Ci = real channels x KD -- and x is the real [B / Do][Ci / KD][D][H][W]: launch image b' = b * Do + dz,
+  // launch channel c' = ci * KD + j reads depth plane z = dz * SD - PD + j * DD of real channel ci, a zero where z is outside [0, D).
+  // x_elems counts the REAL elements. Cigr: real channels per group (Cig / KD).
+  int dwin;
+  int KD, D, Do, SD, DD, PD, Cigr;
+  uint32_t inv_kd, inv_do;   // ceil(2^32 / KD), ceil(2^32 / Do) (0: divide), split_fill_inverses
 };
 
 // Plan-only digest of the argument block: every field in declaration order, without the two padding holes (behind sample0, at the end).
+// The depth-window fields behind inv_uw are folded in only when the launch is one: every other launch hashes the bytes it always did.
 inline uint64_t digest_arg(uint64_t h, const FwdArgs& a) {
   constexpr size_t hole = offsetof(FwdArgs, sample0) + sizeof(uint32_t), end = offsetof(FwdArgs, inv_uw) + sizeof(uint32_t);
-  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && sizeof(FwdArgs) == end + 4, "FwdArgs padding moved: name the holes here");
+  constexpr size_t end_dw = offsetof(FwdArgs, inv_do) + sizeof(uint32_t);
+  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && offsetof(FwdArgs, dwin) == end && sizeof(FwdArgs) == end_dw + 4, "FwdArgs padding moved: name the holes here");
   h = fnv1a(h, &a, hole);
-  return fnv1a(h, &a.call_base, end - offsetof(FwdArgs, call_base));
+  h = fnv1a(h, &a.call_base, end - offsetof(FwdArgs, call_base));
+  return a.dwin ? fnv1a(h, &a.dwin, end_dw - end) : h;
 }
 
 // The split-precision chains (bt_fused_split.hip, bt_fused_split_flip.hip), for every translation unit that calls them. Each works on

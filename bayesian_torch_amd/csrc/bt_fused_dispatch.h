@@ -1,6 +1,6 @@
 // Host dispatch of the fp32-MFMA forwards (bt_fused_fwd.h, bt_fused_fast.h). fp32_plan, a plain function, plans: form, tile, fast or
 // general kernel, x staging mode and every plan field of FwdArgs; launch_fp32 turns the plan into the instantiation fp32_exists says
-// there is. Included by bt_fused_{reparam,flipout}{,_inj,_updil}.hip, one (FLIP, INJ, UPD) each, so that their instantiations compile
+// there is. Included by bt_fused_{reparam,flipout}{,_inj,_updil,_dwin}.hip, one (FLIP, INJ, UPD, DWIN) each, so that their instantiations compile
 // in parallel. tests/test_fp32_plan_parity.py pins what is planned.
 #pragma once
 #include "bt_fused_fast.h"
@@ -131,7 +131,7 @@ static int plan_tile(FwdArgs& a, bool flip, bool inj, bool upd, bool planned, Fp
 // refusal set_error made. upd: an input-dilated launch (FwdArgs::updil). Its tile is chosen as for the launch over the virtual image,
 // among the tiles the general kernel has.
 static int fp32_plan(FwdArgs& a, bool flip, bool linear, bool inj, bool upd, Fp32Plan* p) {
-  if (upd && a.ep_pool) return set_error(BT_ERR_UNSUPPORTED, "fused max-pool: not available on an input-dilated launch");
+  if (upd && a.ep_pool) return set_error(BT_ERR_UNSUPPORTED, "fused max-pool: not available on an input-dilated or depth-window launch");
   p->linear = !upd && linear && a.w_vec && a.x_vec;   // float4 rows; any other Linear is a 1x1 conv over 1x1 images: the same memory layout
   p->trans = p->linear || a.HoWo == 1 || a.pixel_major || a.out_vec4;
   const bool onchip = !inj && !upd;
@@ -150,7 +150,9 @@ static int fp32_plan(FwdArgs& a, bool flip, bool linear, bool inj, bool upd, Fp3
 }
 
 // ---------------------------------------------------------------------------- the launch
-template <int KIND, int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD, int XMODE, bool POOL>
+// DWIN (with UPD: planned like an input-dilated launch, the general kernel alone): a depth-window launch (FwdArgs::dwin), the
+// kernel's DWIN form instead of its UPD one.
+template <int KIND, int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD, int XMODE, bool POOL, bool DWIN = false>
 static int launch_inst(const FwdArgs& a, hipStream_t stream) {
   if constexpr (!fp32_exists(KIND, BN, BM, FLIP, LINEAR, TRANS, INJ, UPD, XMODE, POOL)) {
     return set_error(BT_ERR_UNSUPPORTED, KIND ? "fused forward: the plan names a fast kernel that is not instantiated" : "fused forward: this tile exists in the fast flavour only");
@@ -160,8 +162,8 @@ static int launch_inst(const FwdArgs& a, hipStream_t stream) {
     char nm[160];   // (bt_last_kernel_name: tests and bench.py's tables parse the two formats)
     const char *fl = FLIP ? "flip" : "reparam", *li = LINEAR ? "linear" : "conv", *tr = TRANS ? "trans" : "notrans";
     if constexpr (KIND == 0) {
-      snprintf(nm, sizeof(nm), "fused_fwd_kernel<%d,%d,%d,%s,%s,%s,inj=%d%s>", BN, BM, CWN, fl, li, tr, INJ ? 1 : 0, UPD ? ",updil" : "");
-      return launch_kernel(fused_fwd_kernel<BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD>, nm, "fused forward", dim3((unsigned)a.total_blocks), dim3(kThreads),
+      snprintf(nm, sizeof(nm), "fused_fwd_kernel<%d,%d,%d,%s,%s,%s,inj=%d%s>", BN, BM, CWN, fl, li, tr, INJ ? 1 : 0, DWIN ? ",dwin" : UPD ? ",updil" : "");
+      return launch_kernel(fused_fwd_kernel<BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD && !DWIN, DWIN>, nm, "fused forward", dim3((unsigned)a.total_blocks), dim3(kThreads),
                            lds, lds, stream, a);
     } else {
       // narrow conv tiles: 8 producer waves (their accumulators leave room for 12 waves of <= 168 registers)
@@ -173,41 +175,41 @@ static int launch_inst(const FwdArgs& a, hipStream_t stream) {
   }
 }
 
-template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD>
+template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD, bool DWIN>
 static int launch_form(const FwdArgs& a, const Fp32Plan& p, hipStream_t stream) {
-  if (!p.fast) return launch_inst<0, BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD, 0, false>(a, stream);
+  if (!p.fast) return launch_inst<0, BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD, 0, false, DWIN>(a, stream);
   if (p.pool) return launch_inst<1, BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD, 1, true>(a, stream);
   if (p.xmode == 1) return launch_inst<1, BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD, 1, false>(a, stream);
   if (p.xmode == 2) return launch_inst<1, BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD, 2, false>(a, stream);
   return launch_inst<1, BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, UPD, 0, false>(a, stream);
 }
 
-template <int BN, int BM, int CWN, bool FLIP, bool INJ, bool UPD>
+template <int BN, int BM, int CWN, bool FLIP, bool INJ, bool UPD, bool DWIN>
 static int launch_tile(const FwdArgs& a, const Fp32Plan& p, hipStream_t stream) {
-  if (p.linear) return launch_form<BN, BM, CWN, FLIP, true, true, INJ, UPD>(a, p, stream);
-  if (p.trans) return launch_form<BN, BM, CWN, FLIP, false, true, INJ, UPD>(a, p, stream);
-  return launch_form<BN, BM, CWN, FLIP, false, false, INJ, UPD>(a, p, stream);
+  if (p.linear) return launch_form<BN, BM, CWN, FLIP, true, true, INJ, UPD, DWIN>(a, p, stream);
+  if (p.trans) return launch_form<BN, BM, CWN, FLIP, false, true, INJ, UPD, DWIN>(a, p, stream);
+  return launch_form<BN, BM, CWN, FLIP, false, false, INJ, UPD, DWIN>(a, p, stream);
 }
 
 // The planned kernel, among those of this translation unit's (FLIP, INJ, UPD).
-template <bool FLIP, bool INJ, bool UPD>
+template <bool FLIP, bool INJ, bool UPD, bool DWIN>
 static int launch_fp32(const FwdArgs& a, const Fp32Plan& p, hipStream_t stream) {
   switch (p.bn * 1024 + p.bm) {
-    case 128 * 1024 + 32: return launch_tile<128, 32, 4, FLIP, INJ, UPD>(a, p, stream);
-    case 64 * 1024 + 64: return launch_tile<64, 64, 2, FLIP, INJ, UPD>(a, p, stream);
-    case 32 * 1024 + 128: return launch_tile<32, 128, 1, FLIP, INJ, UPD>(a, p, stream);
-    case 64 * 1024 + 512: return launch_tile<64, 512, 1, FLIP, INJ, UPD>(a, p, stream);
-    case 128 * 1024 + 256: return launch_tile<128, 256, 2, FLIP, INJ, UPD>(a, p, stream);
-    case 64 * 1024 + 256: return launch_tile<64, 256, 1, FLIP, INJ, UPD>(a, p, stream);
-    case 128 * 1024 + 128: return launch_tile<128, 128, 2, FLIP, INJ, UPD>(a, p, stream);
-    case 64 * 1024 + 128: return launch_tile<64, 128, 2, FLIP, INJ, UPD>(a, p, stream);
+    case 128 * 1024 + 32: return launch_tile<128, 32, 4, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 64 * 1024 + 64: return launch_tile<64, 64, 2, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 32 * 1024 + 128: return launch_tile<32, 128, 1, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 64 * 1024 + 512: return launch_tile<64, 512, 1, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 128 * 1024 + 256: return launch_tile<128, 256, 2, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 64 * 1024 + 256: return launch_tile<64, 256, 1, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 128 * 1024 + 128: return launch_tile<128, 128, 2, FLIP, INJ, UPD, DWIN>(a, p, stream);
+    case 64 * 1024 + 128: return launch_tile<64, 128, 2, FLIP, INJ, UPD, DWIN>(a, p, stream);
   }
   return set_error(BT_ERR_UNSUPPORTED, "fused forward: the plan names a tile that is not instantiated");
 }
 
 // One translation unit's launcher. On-chip draws: the split-precision chain first (natural-layout injected draws never take it). Then
 // plan and launch: on BT_OK the plan that ran is in `ran`.
-template <bool FLIP, bool INJ, bool UPD = false>
+template <bool FLIP, bool INJ, bool UPD = false, bool DWIN = false>
 static int run_fp32(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream) {
   if constexpr (!INJ) {
     const int rc = FLIP ? launch_split_flip(a, ran, stream) : launch_split(a, ran, stream);
@@ -216,7 +218,7 @@ static int run_fp32(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t str
   Fp32Plan p;
   ran = a;
   if (int rc = fp32_plan(ran, FLIP, linear, INJ, UPD, &p)) return rc;
-  return launch_fp32<FLIP, INJ, UPD>(ran, p, stream);
+  return launch_fp32<FLIP, INJ, UPD, DWIN>(ran, p, stream);
 }
 
 }  // namespace bt

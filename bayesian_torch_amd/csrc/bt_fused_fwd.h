@@ -133,7 +133,11 @@ __device__ __forceinline__ double block_sum_all(double v, double* scratch) {  //
 // the point where it forms the address; a pixel between the lattice points or in the explicit padding is masked like the zero padding.
 // An instantiation of its own, so that the other forms carry none of it. Flipout's input sign is hashed over the offset that is
 // read: one sign per real element.
-template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false>
+// DWIN: x is the real [B][Ci][D][H][W] of a depth-window launch (FwdArgs::dwin: Conv3d as one Conv2d launch without the unfolded copy).
+// The gathers work on the virtual operand [B * Do][Ci * KD][H][W]; where they form an address, the launch image gives the window's first
+// plane z0 and launch channel c' = (ci, j) the plane ci * D + z0 + j * DD, masked like the zero padding where that depth is outside
+// [0, D). The same sign rule: one sign per real element.
+template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false, bool DWIN = false>
 __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   unsigned long long* const dbg_ = kStamps ? a.dbg : nullptr;  // stage stamps: diagnostic build only (make STAMPS=1)
   constexpr int CWM = 4 / CWN;
@@ -145,6 +149,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   static_assert(TN >= 1 && TM >= 1 && BN % 32 == 0 && BM % 32 == 0 && WTM * CWM == BM && WTN * CWN == BN && BM <= kProducers, "tile shape");
   static_assert(!LINEAR || TRANS, "Linear always stores with lanes along the output features");
   static_assert(!UPD || (!LINEAR && !INJ), "the input-dilated form: convolutions, on-chip draws");
+  static_assert(!DWIN || (!LINEAR && !INJ && !UPD), "the depth-window form: convolutions, on-chip draws, not input-dilated");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];  // ONE LDS object
   int4* const taptab = reinterpret_cast<int4*>(smem + 2 * BUF_WORDS);
@@ -254,6 +259,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   int hi0 = 0, wi0 = 0;
   int xoff0 = 0;  // element offsets fit 32 bits (the API rejects tensors of 2^30 elements or more)
   bool mvalid = false;
+  [[maybe_unused]] int zz0 = 0;  // DWIN: first depth plane of this thread's window
   if (!LINEAR && producer) {
     const int ml = m0 + xm;
     mvalid = ml < m_lim;
@@ -269,7 +275,18 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
     wi0 = wo * a.SW - a.PW;
     xoff0 = (b * a.Ci + g * Cig) * a.HW + hi0 * a.W + wi0;
     if constexpr (UPD) xoff0 = (b * a.Ci + g * Cig) * a.HWr;  // the image's first real element (the pixel part comes from upd_map)
+    if constexpr (DWIN) {  // launch image -> (real image, output depth); the offset is the pixel's at depth 0 of the group's first channel
+      const int bb = b / a.Do;
+      zz0 = (b - bb * a.Do) * a.SD - a.PD;
+      xoff0 = (bb * a.G + g) * a.Cigr * a.D * a.HW + hi0 * a.W + wi0;
+    }
   }
+  // DWIN: launch channel c (inside the group) of a window that starts at plane z0 -> element offset of its plane; *ok: the depth exists
+  [[maybe_unused]] auto dwin_ch = [&](int c, int z0, bool* ok) -> int {
+    const int ci = c / a.KD, z = z0 + (c - ci * a.KD) * a.DD;
+    *ok = (unsigned)z < (unsigned)a.D;
+    return (ci * a.D + z) * a.HW;
+  };
   // UPD: virtual pixel (y, x) -> offset of the real element inside its plane; -1: no element (off the lattice, explicit padding, outside)
   [[maybe_unused]] auto upd_map = [&](int y, int x) -> int {
     const int yv = y - a.LH, xw = x - a.LW;
@@ -332,6 +349,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   // patch fill: this thread owns plane positions pos = ptid + 256*i (all channels of the stage)
   constexpr int PPOS = (X_WORDS / 4 + kProducers - 1) / kProducers;
   int p_off[PPOS];
+  [[maybe_unused]] int p_z0[DWIN ? PPOS : 1];
   unsigned p_ok = 0;
   if (use_patch && producer) {
     const uint32_t inv_pimg = (uint32_t)((0x100000000ull + (unsigned)PIMG - 1) / (unsigned)PIMG);
@@ -352,6 +370,10 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
         const int m = ok ? upd_map(y, x) : -1;
         ok = m >= 0;
         p_off[i] = ok ? (b * a.Ci + g * Cig) * a.HWr + m : 0;
+      } else if constexpr (DWIN) {
+        const int bb = b / a.Do;
+        p_z0[i] = (b - bb * a.Do) * a.SD - a.PD;
+        p_off[i] = ok ? (bb * a.G + g) * a.Cigr * a.D * a.HW + y * a.W + x : 0;
       } else {
         p_off[i] = ok ? (b * a.Ci + g * Cig) * a.HW + y * a.W + x : 0;
       }
@@ -486,9 +508,15 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
         if (kProducers * i < PCH) {  // uniform: small planes need few passes
 #pragma unroll
           for (int c = 0; c < CCs; ++c) {
-            const bool ok = ((p_ok >> i) & 1u) && (c0 + c < Cig);
+            bool ok = ((p_ok >> i) & 1u) && (c0 + c < Cig);
+            int cho = (c0 + c) * HWx;  // the channel's offset from the pixel's
+            if constexpr (DWIN) {
+              bool zk;
+              cho = dwin_ch(c0 + c, p_z0[i], &zk);
+              ok = ok && zk;
+            }
             if (ok) xok |= 1ull << (i * CCs + c);
-            const uint32_t off = ok ? (uint32_t)(p_off[i] + (c0 + c) * HWx) : 0u;
+            const uint32_t off = ok ? (uint32_t)(p_off[i] + cho) : 0u;
             xv[i * CCs + c] = xs[off];
             if constexpr (FLIP) {
               xo[i * CCs + c] = off;
@@ -504,9 +532,15 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
       for (int t = 0; t < TPS; ++t) {
 #pragma unroll
         for (int c = 0; c < CPT; ++c) {
-          const bool ok = ((g_ok >> t) & 1u) && (ci0 + c * NG < Cig);
+          bool ok = ((g_ok >> t) & 1u) && (ci0 + c * NG < Cig);
+          int cho = cbase + c * NG * HWx;
+          if constexpr (DWIN) {
+            bool zk;
+            cho = dwin_ch(ci0 + c * NG, zz0, &zk);
+            ok = ok && zk;
+          }
           if (ok) xok |= 1ull << (t * CPT + c);
-          const uint32_t off = ok ? (uint32_t)(g_off[t] + cbase + c * NG * HWx) : 0u;
+          const uint32_t off = ok ? (uint32_t)(g_off[t] + cho) : 0u;
           xv[t * CPT + c] = xs[off];
           if constexpr (FLIP) {
             xo[t * CPT + c] = off;
@@ -527,8 +561,14 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
           pxo = ok ? upd_map(hi0 + e.y, wi0 + e.z) : -1;
           ok = pxo >= 0;
         }
+        int cho = ci * HWx;
+        if constexpr (DWIN) {
+          bool zk;
+          cho = dwin_ch(ci, zz0, &zk);
+          ok = ok && zk;
+        }
         if (ok) xok |= 1ull << q;
-        const uint32_t off = ok ? (uint32_t)(xoff0 + ci * HWx + pxo) : 0u;
+        const uint32_t off = ok ? (uint32_t)(xoff0 + cho + pxo) : 0u;
         xv[q] = xs[off];
         if constexpr (FLIP) {
           xo[q] = off;

@@ -424,6 +424,12 @@ __device__ __forceinline__ void split_one_pixel_tile(const FwdArgs& a, const int
 //      over the VIRTUAL image; the decode maps a virtual pixel to the real element it stands for, or -- between the lattice points and
 //      in the explicit padding -- to the out-of-range offset that reads as zero, and the stage loop steps by the REAL plane size.
 //      Flipout hashes its input signs over the real element index: one sign per element of [B][Ci][Hr][Wr], as the reference draws them.
+//   6: a depth-windowed input (FwdArgs::dwin: Conv3d as one Conv2d launch without the unfolded copy). The items are XM 0's over the
+//      virtual operand [B * Do][Ci * KD][H][W]; the decode splits the launch image into (real image, output depth) and keeps the item's
+//      offset at depth 0 next to the window's first plane z0 = dz * SD - PD. In the stage loop the 8 channels of an octet no longer
+//      step by one plane: launch channel c' = (ci, j) reads plane ci * D + z0 + j * DD, masked to the zero read where the depth is
+//      outside [0, D). (ci, j) of an octet's first channel is one multiply-high per item and stage, the other seven follow by a
+//      carry. Flipout hashes its input signs over the real element index: one sign per element of [B][Ci][D][H][W].
 //
 // FLIP: the Flipout forward  out = x*mu + s_out o ((x o s_in) * (sigma o eps))  (flipout_layers.py:conv / linear forward): two
 // contractions that share the x pieces. The producers stage mu and sigma*eps as two weight images and, next to the pieces of
@@ -796,6 +802,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     constexpr int PIT = (XM == 3 || XM == 4) ? ((XPO - 1) / 2 + kProducers - 1) / kProducers : (XPO - 1 + kProducers - 1) / kProducers;   // (XPO - 1 patch slots + the zero pixel)
     constexpr int XV = XM == 3 ? 16 : XM == 4 ? 32 : 8;
     int it_off[PIT], it_lds[PIT], it_ol[PIT];
+    [[maybe_unused]] int it_z0[XM == 6 ? PIT : 1];   // XM 6: first depth plane of the item's window (may be negative: the depth padding)
     // real input rows of the patch and 16-byte quads per row (XM 3)
     // (XM 3: the stored columns are the whole row, NXR == W -- or, x_flat, the whole plane taken as ONE row of H*W pixels; XM 4: every second column)
     const bool flat = XM == 3 && a.x_flat != 0;
@@ -867,6 +874,10 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
             const int yr = yv > 0 ? udiv_inv(yv, a.UH, a.inv_uh) : 0, xr = xw > 0 ? udiv_inv(xw, a.UW, a.inv_uw) : 0;
             const bool on = yv >= 0 && xw >= 0 && yr * a.UH == yv && xr * a.UW == xw && yr < a.Hr && xr < a.Wr;
             if (b < a.B && on) off = 4 * ((b * a.Ci + g * Cig) * a.HWr + yr * a.Wr + xr);
+          } else if constexpr (XM == 6) {  // launch image -> (real image, output depth); the offset is the pixel's at depth 0 of the group's first channel
+            const int bb = udiv_inv(b, a.Do, a.inv_do), dz = b - bb * a.Do;
+            it_z0[i] = dz * a.SD - a.PD;
+            if (b < a.B) off = 4 * ((bb * a.G + g) * a.Cigr * a.D * a.HW + y * a.W + x);
           } else if (b < a.B) {
             off = 4 * ((b * a.Ci + g * Cig) * a.HW + y * a.W + x);
           }
@@ -881,6 +892,25 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     const int HWb = 4 * HWx;
     const int wave_i0 = wave_u0;  // first item index of this wave (iteration 0)
     const int n_items_w = n_items;
+    // XM 6: byte offsets (relative to the item's) and depths of the 8 launch channels of octet oc, for the window that starts at plane z0.
+    // Channel c' = 8 oc + c is tap j = c' % KD of real channel ci = c' / KD: plane ci * D + z0 + j * DD. ok bit c: the depth exists.
+    [[maybe_unused]] auto dwin_planes = [&](int oc, int z0, uint32_t (&pb)[8]) -> uint32_t {
+      const uint32_t step = (uint32_t)(a.DD * HWb), wrap = (uint32_t)((a.D - (a.KD - 1) * a.DD) * HWb);   // next tap / first tap of the next channel
+      const int c0 = 8 * oc;
+      const int ci = udiv_inv(c0, a.KD, a.inv_kd);
+      int j = c0 - ci * a.KD, z = z0 + j * a.DD;
+      uint32_t p = (uint32_t)((ci * a.D + z) * HWb), ok = 0u;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        pb[c] = p;
+        ok |= (uint32_t)((unsigned)z < (unsigned)a.D) << c;
+        const uint32_t m = 0u - (uint32_t)(j + 1 == a.KD);   // (bit arithmetic, as guard_off)
+        p += (step & ~m) | (wrap & m);
+        z = (int)(((uint32_t)(z + a.DD) & ~m) | ((uint32_t)z0 & m));
+        j = (int)((uint32_t)(j + 1) & ~m);
+      }
+      return ok;
+    };
 
     // One stage = loads (issued one stage AHEAD, into registers that the previous stage has just consumed) -> draws (pure
     // ALU: they run while the loads are in flight) -> sampled weights -> pieces -> LDS -> activations -> pieces -> LDS.
@@ -935,6 +965,11 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
               const float4 v = ldf4(r_x, guard_off(in, (uint32_t)(it_off[i] + (8 * oc + c) * HWb)));
               xv[i][4 * c] = v.x, xv[i][4 * c + 1] = v.y, xv[i][4 * c + 2] = v.z, xv[i][4 * c + 3] = v.w;
             }
+          } else if constexpr (XM == 6) {
+            uint32_t pb[8];
+            const uint32_t zok = dwin_planes(oc, it_z0[i], pb);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) xv[i][c] = ldf(r_x, guard_off(in && ((zok >> c) & 1u), (uint32_t)it_off[i] + pb[c]));
           } else {
 #pragma unroll
             for (int c = 0; c < 8; ++c) xv[i][c] = ldf(r_x, guard_off(in, (uint32_t)(it_off[i] + (8 * oc + c) * HWb)));
@@ -964,6 +999,17 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         *reinterpret_cast<uint4*>(dst + 16) = make_uint4(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]), pack_hi16(pm[5], pm[4]), pack_hi16(pm[7], pm[6]));
       if constexpr (NP == 3)
         *reinterpret_cast<uint4*>(dst + 32) = make_uint4(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]), pack_hi16(pl[5], pl[4]), pack_hi16(pl[7], pl[6]));
+    };
+    // XM 6, Flipout: the same with one sign index per channel (the real element's offset in the sample: the channels of an octet are not
+    // a constant stride apart)
+    [[maybe_unused]] auto store_px_ix = [&](char* dst, const float (&v)[8], const uint32_t (&ix)[8]) {
+      uint32_t ph[8], pm[8], pl[8], sb[8];
+#pragma unroll
+      for (int c = 0; c < 8; ++c) split_pieces(v[c], ph[c], pm[c], pl[c]), sb[c] = sign_bit(ix[c]);
+      *reinterpret_cast<uint4*>(dst + 16 * NP) = make_uint4(pack_hi16(sb[1], sb[0]), pack_hi16(sb[3], sb[2]), pack_hi16(sb[5], sb[4]), pack_hi16(sb[7], sb[6]));
+      *reinterpret_cast<uint4*>(dst) = make_uint4(pack_hi16(ph[1], ph[0]), pack_hi16(ph[3], ph[2]), pack_hi16(ph[5], ph[4]), pack_hi16(ph[7], ph[6]));
+      *reinterpret_cast<uint4*>(dst + 16) = make_uint4(pack_hi16(pm[1], pm[0]), pack_hi16(pm[3], pm[2]), pack_hi16(pm[5], pm[4]), pack_hi16(pm[7], pm[6]));
+      *reinterpret_cast<uint4*>(dst + 32) = make_uint4(pack_hi16(pl[1], pl[0]), pack_hi16(pl[3], pl[2]), pack_hi16(pl[5], pl[4]), pack_hi16(pl[7], pl[6]));
     };
     // FLIP && INJ: the same with the pixel's sign bytes as loaded (XM 1: byte c of the two dwords; XM 0: one byte per channel)
     [[maybe_unused]] auto store_px_sg = [&](char* dst, const float (&v)[8], const auto& sg) {
@@ -1034,7 +1080,13 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
           } else {
             const float v[8] = {xv[i][0], xv[i][1], xv[i][2], xv[i][3], xv[i][4], xv[i][5], xv[i][6], xv[i][7]};
             if constexpr (SGN) store_px_sg(dst, v, sgv[i]);
-            else store_px(dst, v, e0, XM == 1 ? 1u : (uint32_t)HWx);
+            else if constexpr (XM == 6 && FLIP) {
+              uint32_t ix[8];
+              dwin_planes(st * NO + it_ol[i], it_z0[i], ix);
+#pragma unroll
+              for (int c = 0; c < 8; ++c) ix[c] = ((uint32_t)it_off[i] + ix[c]) >> 2;
+              store_px_ix(dst, v, ix);
+            } else store_px(dst, v, e0, XM == 1 ? 1u : (uint32_t)HWx);
           }
         }
       }

@@ -173,11 +173,12 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   if (inj && mode >= 2) return 1;   // (the opt-in forms have no injected instantiation)
   // An input-dilated image (bt_reparam_conv2d_updil_fwd) is read by the general kernel's xm 5 fetch alone: on-chip draws, the exact split
   // or the bf16 mode; the stem, split-K and direct kernels never take it (the fp32 general kernel serves what is left).
-  if (a.updil && (inj || mode == 2 || a.Cig <= 4)) return 1;
+  // A depth-window launch (bt_reparam_conv2d_dwin_fwd) in the same way: the xm 6 fetch alone.
+  if ((a.updil || a.dwin) && (inj || mode == 2 || a.Cig <= 4)) return 1;
   if (a.Cig <= 4) return launch_quad(a, ran, mode, stream);   // the stems
   // whole channel octets, no fused pooling
   if ((a.Cig & 7) || a.ep_pool) return 1;
-  if (mode != 2 && !a.updil) {   // (the flavours with a single live tap per slice / layer take any window size)
+  if (mode != 2 && !a.updil && !a.dwin) {   // (the flavours with a single live tap per slice / layer take any window size)
     // (the bf16 mode has no split-K instantiation: the direct / general kernels serve those launches)
     const int rck = mode == 3 ? 1 : launch_skinny(a, ran, stream);
     if (rck <= 0) return rck;
@@ -188,6 +189,7 @@ static int launch_split_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   if (split_plan<false>(a, mode, &bm, &xm)) return 1;
   ran = a;
   if (a.updil) return launch_split_updil_cfg(a, bm, mode == 3 ? 1 : 3, false, stream);
+  if (a.dwin) return launch_split_dwin_cfg(a, bm, mode == 3 ? 1 : 3, false, stream);
   if (inj) return launch_split_inj_cfg(a, bm, xm, stream);
   if (mode == 3) return launch_split_bf16_cfg(a, bm, xm, stream);
   return mode == 2 ? launch_split_general<2, false, false>(a, bm, xm, stream) : launch_split_general<3, false, false>(a, bm, xm, stream);   // (bf16x2: the generic fetch alone)

@@ -22,13 +22,14 @@ static int launch_split_flip_one(FwdArgs a, FwdArgs& ran, hipStream_t stream) {
   const int mode = contraction_mode();
   if (mode == 1 || mode == 2) return 1;
   if (!packed_ok(a)) return 1;
-  if (a.updil && (a.eps_w || a.Cig <= 4)) return 1;   // an input-dilated image: the general kernel's xm 5 fetch, on-chip draws (else the fp32 general kernel)
+  if ((a.updil || a.dwin) && (a.eps_w || a.Cig <= 4)) return 1;   // an input-dilated image / a depth window: the general kernel's xm 5 / 6 fetch, on-chip draws (else the fp32 general kernel)
   if (a.Cig <= 4) return launch_quad_flip(a, ran, stream);   // the stems
   if ((a.Cig & 7) || a.ep_pool) return 1;   // whole channel octets, no fused pooling
   int bm, xm;
   if (split_plan<true>(a, mode, &bm, &xm)) return 1;
   ran = a;
   if (a.updil) return launch_split_updil_cfg(a, bm, 3, true, stream);
+  if (a.dwin) return launch_split_dwin_cfg(a, bm, 3, true, stream);
   return a.eps_w ? launch_split_flip_inj_cfg(a, bm, xm, stream) : launch_split_general<3, true, false>(a, bm, xm, stream);
 }
 

@@ -19,7 +19,7 @@ static inline uint32_t inv_u32(long long d, long long nmax) {
 static inline void split_fill_inverses(FwdArgs& a) {
   static const bool off = getenv("BT_NO_HOST_INV") != nullptr;   // test hook: every kernel-side division takes its fallback path
   if (off) {
-    a.inv_m_tiles = a.inv_S = a.inv_n_tiles = a.inv_n_bt = a.inv_n_ct = a.inv_rw = a.inv_wt = a.inv_kw = a.inv_n_sg = a.inv_uh = a.inv_uw = 0u;
+    a.inv_m_tiles = a.inv_S = a.inv_n_tiles = a.inv_n_bt = a.inv_n_ct = a.inv_rw = a.inv_wt = a.inv_kw = a.inv_n_sg = a.inv_uh = a.inv_uw = a.inv_kd = a.inv_do = 0u;
     return;
   }
   const long long tb = a.total_blocks;
@@ -33,6 +33,7 @@ static inline void split_fill_inverses(FwdArgs& a) {
   a.inv_kw = inv_u32(a.KW, 64);
   a.inv_n_sg = inv_u32(a.n_sg, tb);
   a.inv_uh = a.updil ? inv_u32(a.UH, a.H) : 0u, a.inv_uw = a.updil ? inv_u32(a.UW, a.W) : 0u;   // (virtual pixel -> real element, XM 5)
+  a.inv_kd = a.dwin ? inv_u32(a.KD, a.Cig + 64) : 0u, a.inv_do = a.dwin ? inv_u32(a.Do, a.B + 1024) : 0u;   // (launch channel -> (ci, j), launch image -> (b, dz): XM 6)
 }
 
 // Extent of the window of taps that can meet data along one axis (the kernel's own rule: bt_fused_split.h), for the whole

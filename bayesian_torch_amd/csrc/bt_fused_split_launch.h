@@ -27,6 +27,8 @@ int launch_quad_flip_inj(const FwdArgs& a, hipStream_t stream);
 // bt_fused_split_updil.hip: the input-dilated fetch (xm 5, FwdArgs::updil) of the general kernel, on-chip draws -- np 3 / 1
 // Reparameterization (every tile), Flipout (np 3). BT_ERR_UNSUPPORTED, nothing launched, for anything else.
 int launch_split_updil_cfg(const FwdArgs& a, int bm, int np, bool flip, hipStream_t stream);
+// bt_fused_split_dwin.hip: the depth-window fetch (xm 6, FwdArgs::dwin) of the general kernel, on-chip draws -- the set xm 5 has.
+int launch_split_dwin_cfg(const FwdArgs& a, int bm, int np, bool flip, hipStream_t stream);
 
 // ---------------------------------------------------------------------------- names
 // bt_last_kernel_name's strings (tests, bench.py's tables and the tools parse them) and the `who` of the error messages.
@@ -76,13 +78,15 @@ inline SplitNames skinny_kernel_names(bool inj, int ks) {
 // xm 5 (input-dilated images) exists for every tile of the np 3 / 1 Reparameterization and of the Flipout variant with on-chip draws. No
 // other fetch can stand in for it -- the generic one would read the real image as if it were the virtual one -- so launch_split_xm never
 // reaches it: launch_split_updil_cfg names its instantiations one by one.
+// xm 6 (depth windows: Conv3d without the unfolded copy) exists for the same set and is reached the same way, through
+// launch_split_dwin_cfg alone: a missing instantiation is an error, never the generic fetch.
 // (Flipout's 128-wide xm 2 -- whole 2x2 planes of a pixel-major 3x3 -- is not instantiated: DESIGN 4.0c.)
 constexpr int split_npw(int bm, bool flip) { return flip ? (bm == 128 ? 8 : 4) : (bm == 512 ? 4 : 8); }
 constexpr bool split_exists(int bn, int bm, int np, bool flip, int xm) {
   if (flip ? (bn != 64 || bm == 512) : (bn == 32 && (bm != 128 || np == 2))) return false;
   if (xm == 0) return true;
   if (np == 2) return false;
-  if (xm == 5) return true;
+  if (xm == 5 || xm == 6) return true;
   if (flip) return bm == 128 ? xm == 1 : xm == 3;
   return bm == 128 ? xm <= 2 : bm == 256 ? xm >= 2 : xm >= 3;
 }
@@ -91,6 +95,8 @@ template <int NP, bool FLIP, bool INJ, int BN, int BM, int XM>
 int launch_split_inst(const FwdArgs& a, hipStream_t stream) {
   if constexpr (XM == 5 && (INJ || !split_exists(BN, BM, NP, FLIP, XM))) {
     return set_error(BT_ERR_UNSUPPORTED, "fused forward (split): no input-dilated instantiation of this tile and variant");
+  } else if constexpr (XM == 6 && (INJ || !split_exists(BN, BM, NP, FLIP, XM))) {
+    return set_error(BT_ERR_UNSUPPORTED, "fused forward (split): no depth-window instantiation of this tile and variant");
   } else if constexpr (!split_exists(BN, BM, NP, FLIP, XM)) {
     static_assert(XM != 0, "the generic fetch exists for every tile a variant has");
     return launch_split_inst<NP, FLIP, INJ, BN, BM, 0>(a, stream);   // a fetch mode without an instantiation: the generic fetch

@@ -36,7 +36,9 @@ def maxpool_3x3s2(x):
 
 def _geometry(x, mu_w, conv, S, shared_x):
     """-> (B, the launch's bt_conv2d_geom -- Linear as the 1 x 1 convolution --, one sample's x elements, the contraction's output tail).
-    An input-dilated conv (``conv["updil"]``): the geom holds x's own dims and no padding, the tail is the virtual image's output."""
+    An input-dilated conv (``conv["updil"]``): the geom holds x's own dims and no padding, the tail is the virtual image's output.
+    A depth-window conv (``conv["dwin"]`` = (kd, D, sd, dd, pd)): x is the real [B, Ci * D, H, W]; B and the geom are the launch's over
+    the virtual operand (B * Do images of Ci * kd channels), x elements the real ones."""
     per = 1 if shared_x else S
     if x.shape[0] % per:
         raise RuntimeError("stacked input rows are not a multiple of S")
@@ -49,6 +51,19 @@ def _geometry(x, mu_w, conv, S, shared_x):
     kh, kw = mu_w.shape[2], mu_w.shape[3]
     (sh, sw), (ph, pw), (dh, dw), groups = conv["stride"], conv["padding"], conv["dilation"], conv["groups"]
     Ci, H, W = x.shape[1], x.shape[2], x.shape[3]
+    if conv.get("dwin") is not None:        # the virtual operand of bt_*_conv2d_dwin_fwd
+        if conv.get("updil") is not None:
+            raise RuntimeError("a conv takes a depth window or an input dilation, not both")
+        dw_ = tuple(conv["dwin"])
+        if len(dw_) != 5 or any(int(v) != v for v in dw_):
+            raise RuntimeError("dwin is (kd, D, sd, dd, pd), five integers")
+        kd, D, sd, dd, pd = dw_
+        if min(kd, D, sd, dd) < 1 or pd < 0 or Ci % D:
+            raise RuntimeError("a depth-window conv takes kd, D, sd, dd >= 1, pd >= 0 and x as [B, Ci * D, H, W]")
+        Do = (D + 2 * pd - dd * (kd - 1) - 1) // sd + 1
+        if D + 2 * pd - dd * (kd - 1) - 1 < 0 or Do < 1:
+            raise RuntimeError("convolution output would be empty")
+        B, Ci = B * Do, Ci // D * kd
     if Ci != mu_w.shape[1] * groups:
         raise RuntimeError(f"input has {Ci} channels, weight expects {mu_w.shape[1] * groups}")
     Hv, Wv = H, W
@@ -132,6 +147,9 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     With ``updil=(uh, uw)`` and ``pads=(lo_h, hi_h, lo_w, hi_w)`` in it (padding (0, 0)), x is convolved as the input-dilated, explicitly
     padded image it stands for (bt_*_conv2d_updil_fwd: a transposed convolution without the upsampled copy); on-chip draws only, and a
     launch the library declines (BT_ERR_UNSUPPORTED, nothing launched) returns None instead of a result.
+    With ``dwin=(kd, D, sd, dd, pd)`` in it, x is the real input of a Conv3d as [B, Ci * D, H, W] (a view of [B, Ci, D, H, W]) and mu_w
+    the [Co, (Ci / g) * kd, kh, kw] kernel: the launch convolves the depth-unfolded operand without materialising it
+    (bt_*_conv2d_dwin_fwd) and returns out [S * B * Do, Co, Ho, Wo]; on-chip draws only, None when the library declines.
     priors: (prior_mu_w, prior_sigma_w, prior_mu_b, prior_sigma_b) -- required when want_kl.
     eps_*/sign_*: injected draws with a leading S axis, or None for the on-chip generators.
     post_scale/post_shift [Co], residual ([S*B, ...] like out, or [B, ...] shared), relu: fused output stage
@@ -172,9 +190,13 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     if conv is not None and conv.get("updil") is not None:
         updil = _lib.bt_updil(*conv["updil"], *conv["pads"])
         geo_key += (tuple(conv["updil"]), tuple(conv["pads"]))
-    split_inj = updil is None and _split_inject_wanted(tens, flip, S, x_elems, n_so, inject_path, eps_pack_state, geo_key)
+    dwin = None
+    if conv is not None and conv.get("dwin") is not None:
+        dwin = _lib.bt_dwin(*(int(v) for v in conv["dwin"]))
+        geo_key += (("dwin",) + tuple(conv["dwin"]),)
+    split_inj = updil is None and dwin is None and _split_inject_wanted(tens, flip, S, x_elems, n_so, inject_path, eps_pack_state, geo_key)
     # layers whose output map is one pixel may run split over K-slices that meet in scratch behind the workspace (include/bt_hip.h)
-    scratch = int(L.bt_fused_scratch_bytes(C.byref(geom), S)) if ((eps_w is None or split_inj) and not flip and packed is not None and updil is None) else 0
+    scratch = int(L.bt_fused_scratch_bytes(C.byref(geom), S)) if ((eps_w is None or split_inj) and not flip and packed is not None and updil is None and dwin is None) else 0
     if want_kl:
         if priors is None:
             raise ValueError("want_kl needs priors")
@@ -200,6 +222,9 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
         if updil is not None:
             fn = L.bt_flipout_conv2d_updil_fwd if flip else L.bt_reparam_conv2d_updil_fwd
             return fn(C.byref(geom), C.byref(updil), S, *tail_args)
+        if dwin is not None:
+            fn = L.bt_flipout_conv2d_dwin_fwd if flip else L.bt_reparam_conv2d_dwin_fwd
+            return fn(C.byref(geom), C.byref(dwin), S, *tail_args)
         fn = L.bt_flipout_conv2d_fwd if flip else L.bt_reparam_conv2d_fwd
         return fn(C.byref(geom), S, *tail_args)
 
@@ -209,7 +234,7 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
             if eps_pack_state is not None:
                 eps_pack_state["declined"].add(geo_key)
             rc = launch(D_nat)
-        if (pool or updil is not None) and rc == _lib.ERR_UNSUPPORTED:
+        if (pool or updil is not None or dwin is not None) and rc == _lib.ERR_UNSUPPORTED:
             return None
         _lib.check(rc)
     return out, kl

@@ -26,7 +26,19 @@ materialising path. Reparameterization results are the same bits where both path
 then draws one input sign per REAL element ([B][Ci][spatial], the reference's layout and distribution), so its samples differ from
 the materialising path's, whose stream runs over the upsampled tensor. Under the "native" setting ``_last["x_path"]`` says which path
 the call took ("native" | "upsample") and ``_last["x_shape"]`` is the shape of the x that was launched. The default is "upsample":
-every launch, and the launch record, as before. ConvTranspose3d, Conv3d's depth unfolding and the training path always materialise.
+every launch, and the launch record, as before. ConvTranspose3d and the training path always materialise.
+
+Conv3d can skip its pass in the same way: ``set_conv3d_path("native")`` (or ``BT_CONV3D_PATH=native``) hands the real x, as the view
+[B][Ci * D][H][W], and a ``dwin=(kd, D, sd, dd, pd)`` entry to the depth-window entry points (bt_*_conv2d_dwin_fwd), whose kernels
+resolve the depth window where they form their x addresses -- launch image b * Do + do, launch channel ci * kd + j reads depth plane
+do * sd - pd + j * dd, a zero outside [0, D) -- so nothing of the unfolded size (kd / sd times the activations) is written or read.
+It applies to calls without grad that draw on chip (no ``inject_draw``, rng mode not "torch") with integer padding; a call that needs
+grad or supplies draws, and any launch the library declines, unfolds as before, with the same RNG coordinates. Reparameterization
+results are the same bits where both paths run the general split-precision kernel. Flipout then draws ONE input sign per real element
+of [B][Ci][D][H][W] -- the reference's layout and distribution; the unfolding path's stream runs over the unfolded tensor, one
+independent sign per (element, depth window), which is not the reference's distribution where windows overlap.
+Under the "native" setting ``_last["x_path"]`` is "native" | "unfold" and ``_last["x_shape"]`` the launched x's shape. The default
+is "unfold": every launch and every ``_last`` key as before.
 """
 import os
 
@@ -65,6 +77,30 @@ def set_transpose_path(name):
 
 def get_transpose_path():
     return _transpose_path[0]
+
+
+CONV3D_PATHS = ("unfold", "native")
+
+
+def _check_conv3d_path(name, what):
+    if name not in CONV3D_PATHS:
+        raise ValueError(f"{what}: expected one of {CONV3D_PATHS}, got {name!r}")
+    return name
+
+
+_conv3d_path = [_check_conv3d_path(os.environ.get("BT_CONV3D_PATH", "unfold"), "BT_CONV3D_PATH")]
+
+
+def set_conv3d_path(name):
+    """How Conv3d layers feed their launch: "unfold" (default) materialises the depth-unfolded input; "native" lets the kernels read the
+    real input through the depth-window fetch where the call is eligible (module docstring). Process-wide; also the environment variable
+    BT_CONV3D_PATH, read at import. Returns the previous setting."""
+    prev, _conv3d_path[0] = _conv3d_path[0], _check_conv3d_path(name, "set_conv3d_path")
+    return prev
+
+
+def get_conv3d_path():
+    return _conv3d_path[0]
 
 
 class FamilyConvLayer(FusedBayesLayer):
@@ -152,15 +188,33 @@ class FamilyConvLayer(FusedBayesLayer):
         s, p, d, op, ks = self._geom()
         return [(d[i] * (ks[i] - 1) - p[i], d[i] * (ks[i] - 1) - p[i] + op[i]) for i in range(self._nd)]
 
+    def _native_setting(self):
+        """Is this class's path switch on "native"? (Conv3d: set_conv3d_path; the transposed classes: set_transpose_path.) Then the launch
+        record says which path the call took."""
+        if self._transposed:
+            return _transpose_path[0] == "native"
+        return self._nd == 3 and _conv3d_path[0] == "native"
+
     def _native_eligible(self, needs_grad, supplied):
         """Does this call take the input-dilated launch? ConvTranspose1d / 2d under set_transpose_path("native"), no grad, on-chip draws,
-        nothing cropped (a negative pad keeps the materialising path)."""
+        nothing cropped (a negative pad keeps the materialising path). Conv3d under set_conv3d_path("native"): the depth-window launch,
+        no grad, on-chip draws (_geom has refused string padding)."""
+        if not self._transposed:
+            return self._nd == 3 and _conv3d_path[0] == "native" and not needs_grad and not supplied
         return (self._transposed and self._nd <= 2 and _transpose_path[0] == "native" and not needs_grad and not supplied
                 and all(lo >= 0 for lo, _ in self._native_pads()))
 
     def _x_native(self, x):
-        """[N][C][spatial...] of a ConvTranspose1d / 2d -> (the real input as [N][C][H][W], the input-dilated conv dict, back)."""
+        """[N][C][spatial...] of a ConvTranspose1d / 2d -> (the real input as [N][C][H][W], the input-dilated conv dict, back);
+        of a Conv3d -> (the real input as the view [N][C * D][H][W], the depth-window conv dict, back)."""
         s, p, d, op, ks = self._geom()
+        if self._nd == 3:       # Conv3d: the real x as [N][C * D][H][W] (a view), the depth window in the conv dict
+            n0, D = x.shape[0], x.shape[2]
+            Do = (D + 2 * p[0] - d[0] * (ks[0] - 1) - 1) // s[0] + 1
+            conv = dict(stride=s[1:], padding=p[1:], dilation=d[1:], groups=self.groups, dwin=(ks[0], D, s[0], d[0], p[0]))
+            back = lambda o: o.reshape(-1, Do, o.shape[1], o.shape[2], o.shape[3]).permute(0, 2, 1, 3, 4)
+            xc = x.contiguous()
+            return xc.reshape(n0, x.shape[1] * D, x.shape[3], x.shape[4]), conv, back
         pads = self._native_pads()
         if self._nd == 1:
             conv = dict(stride=(1, 1), padding=(0, 0), dilation=(1, d[0]), groups=self.groups, updil=(1, s[0]), pads=(0, 0) + pads[0])
@@ -206,10 +260,17 @@ class FamilyConvLayer(FusedBayesLayer):
         launch's output): a transposed convolution's zero-upsampled x carries one sign per real element like the reference, Conv3d's
         depth-unfolded x one sign per (element, depth window) -- see DESIGN.md 4.6. A launch on the "native" path drew its input signs
         over the real x: they are reported as ``sign_in`` [S, B, Ci, spatial...] and ``sign_out`` [S, B, Co, spatial...], the reference's
-        own layouts (``sign_out_eq`` stays: the same values in the launch's layout)."""
+        own layouts (``sign_out_eq`` stays: the same values in the launch's layout). For a native Conv3d launch that is ``sign_in``
+        [S, B, Ci, D, H, W] (bt_rng_sign_fill over the real count) and ``sign_out`` [S, B, Co, Do, Ho, Wo]."""
         res = super().materialize_last_draw()
         if self._flip and self._last.get("x_path") == "native" and "sign_in_eq" in res:
             si, so = res.pop("sign_in_eq"), res["sign_out_eq"]
+            if self._nd == 3:
+                D = self._last["x_shape"][1] // self.in_channels
+                res["sign_in"] = si.reshape(si.shape[:2] + (self.in_channels, D) + tuple(si.shape[3:]))
+                Do = so.shape[1] // si.shape[1]
+                res["sign_out"] = so.reshape((so.shape[0], si.shape[1], Do) + tuple(so.shape[2:])).permute(0, 1, 3, 2, 4, 5).contiguous()
+                return res
             res["sign_in"], res["sign_out"] = (si.squeeze(3), so.squeeze(3)) if self._nd == 1 else (si, so)
         return res
 
@@ -225,9 +286,9 @@ class FamilyConvLayer(FusedBayesLayer):
         mu_e, rho_e = self._w_eq(self._w("mu")), self._w_eq(self._w("rho"))
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         inj = self._take_injected()
-        out, x_path = None, "upsample"
+        out, x_path = None, ("upsample" if self._transposed else "unfold")
         if self._native_eligible(needs_grad, inj is not None or rng.get_mode() == "torch"):
-            xe, conv, back = self._x_native(x)      # the real x: the kernels resolve the upsampled, padded image in their x fetch
+            xe, conv, back = self._x_native(x)      # the real x: the kernels resolve the upsampled / unfolded operand in their x fetch
             r = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, {}, self._packed()))
             if r is not None:      # (None: the library declined, nothing was launched -> the materialising path, same coordinates)
                 out, x_path = r[0], "native"
@@ -253,8 +314,8 @@ class FamilyConvLayer(FusedBayesLayer):
                 out, _ = F.fused_forward(xe, mu_e, rho_e, self.mu_bias, self.rho_bias, **self._launch_kw(conv, S, shared, coords, draw, self._packed()))
         Be = xe.shape[0] // (1 if shared else S)
         self._last = dict(draw=draw or None, rng=coords, S=S, kernel=_lib.lib().bt_last_kernel_name().decode(),
-                          w_eq_shape=tuple(mu_e.shape), x_shape=(Be,) + tuple(xe.shape[1:]), out_shape=(Be,) + tuple(out.shape[1:]))
-        if _transpose_path[0] == "native":      # (under the default setting the record stays what it was, key for key)
+                          w_eq_shape=tuple(mu_e.shape), x_shape=(Be,) + tuple(xe.shape[1:]), out_shape=(out.shape[0] // S,) + tuple(out.shape[1:]))
+        if self._native_setting():      # (under the default setting the record stays what it was, key for key)
             self._last["x_path"] = x_path
         out = back(out).contiguous()
         kl = self.kl_loss() if want_kl else None

@@ -200,6 +200,36 @@ int bt_flipout_conv2d_updil_fwd(const bt_conv2d_geom *g, const bt_updil *u, int3
                                 float *out, float *kl_out,
                                 void *workspace, size_t workspace_bytes, bt_stream_t stream);
 
+/* The same two convolutions over a DEPTH-WINDOWED input: the forward of a Conv3d as ONE Conv2d launch, without its depth-unfolded copy.
+ * g describes the launch over the virtual (unfolded) operand -- B' = B * Do images of Ci' = Ci * kd channels, with
+ *     Do = (D + 2 * pd - dd * (kd - 1) - 1) / sd + 1;
+ * H, W, spatial stride / padding / dilation and groups are the real ones -- and x is the real [B][Ci][D][H][W] (x_sample_stride in real
+ * elements). Launch image b' = b * Do + dz, launch channel c' = ci * kd + j, pixel (y, x) reads x[b][ci][dz * sd - pd + j * dd][y][x],
+ * a zero where that depth is outside [0, D); the weights are the Conv3d kernel as it lies in memory, [Co][(Ci / groups) * kd][kh][kw];
+ * out is [S][B * Do][Co][Ho][Wo]. The window is resolved where the kernels form their x addresses: nothing of the unfolded size is
+ * written or read. Tile plan, tap pruning, K order and weight-draw streams are those of bt_*_conv2d_fwd on the materialised operand, so
+ * Reparameterization results are the same bits where both run the general split-precision kernel; Flipout draws ONE input sign per real
+ * element, indexed in [B][Ci][D][H][W] (bt_rng_sign_fill, tensor 2, n = B*Ci*D*H*W) -- the reference's distribution, not the stream over
+ * the unfolded operand, where an element has one sign per window it appears in.
+ * Kernels: the general split-precision kernel (x fetch mode 6; bt_set_contraction modes 0 and 3) or the fp32 general kernel. On-chip
+ * draws only and no fused max-pool: BT_ERR_UNSUPPORTED with nothing launched otherwise. BT_ERR_BAD_ARG: kd, D, sd, dd < 1; pd < 0;
+ * Do < 1; g->B % Do != 0; (g->Ci / g->groups) % kd != 0; a real or virtual x of 2^30 elements or more. With kd == 1, D == 1 and
+ * pd == 0 the call is bt_*_conv2d_fwd, launch for launch. */
+typedef struct bt_dwin {
+  int32_t kd, D;      /* depth taps, real depth */
+  int32_t sd, dd, pd; /* depth stride / dilation / padding */
+} bt_dwin;
+int bt_reparam_conv2d_dwin_fwd(const bt_conv2d_geom *g, const bt_dwin *w, int32_t S,
+                               const float *x, int64_t x_sample_stride,
+                               const bt_params *p, const bt_draws *d, const bt_epilogue *ep /* or NULL */,
+                               float *out /* [S][B*Do][Co][Ho][Wo] */, float *kl_out,
+                               void *workspace, size_t workspace_bytes, bt_stream_t stream);
+int bt_flipout_conv2d_dwin_fwd(const bt_conv2d_geom *g, const bt_dwin *w, int32_t S,
+                               const float *x, int64_t x_sample_stride,
+                               const bt_params *p, const bt_draws *d, const bt_epilogue *ep /* or NULL */,
+                               float *out, float *kl_out,
+                               void *workspace, size_t workspace_bytes, bt_stream_t stream);
+
 /* a9: LinearFlipout.forward  (layers/flipout_layers/linear_flipout.py:145-174)
  *   out = x W_mu^T + mu_b + ((x o s_in) (sigma o eps)^T + sigma_b o eps_b) o s_out  -- both contractions share one x tile. */
 int bt_flipout_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S,
