@@ -110,6 +110,8 @@ _PROTOS = {
     "bt_rng_sign_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, _vp, _vp]),
     "bt_rng_philox_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "bt_mc_epilogue": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "bt_lstm_cell_fwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
+    "bt_lstm_cell_bwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

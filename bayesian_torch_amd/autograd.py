@@ -251,3 +251,41 @@ class KLValue(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return (None,) + (g,) * ctx.n
+
+
+class LSTMCell(torch.autograd.Function):
+    """(h, c) of one LSTM time step from the two maps' outputs a, b [rows, 4H] and c_prev [rows or rows / S, H]: one forward launch
+    that also saves the activated gates (bt_lstm_cell_fwd), one backward launch of the closed form on them (bt_lstm_cell_bwd), no host
+    synchronisation. The gradient of a c_prev shared by the S samples is the kernel's per-row result summed over them.
+    ``BACKWARD_IMPL = "aten"`` (chosen before the forward, which then keeps a and b): the checker differentiates the torch gate
+    arithmetic of the reference (rnn_variational.py:131-144) with torch autograd instead."""
+
+    @staticmethod
+    def forward(ctx, a, b, c_prev):
+        h, c, act = F.lstm_cell_fwd(a, b, c_prev, want_act=True)
+        ctx.aten = BACKWARD_IMPL != "hip"
+        ctx.save_for_backward(act, c_prev, c, *((a, b) if ctx.aten else ()))
+        ctx.set_materialize_grads(False)
+        return h, c
+
+    @staticmethod
+    def backward(ctx, gh, gc):
+        act, c_prev, c = ctx.saved_tensors[:3]
+        rows, H = c.shape
+        if gh is None and gc is None:
+            return None, None, None
+        if ctx.aten:
+            a, b = ctx.saved_tensors[3:]
+            with torch.enable_grad():
+                a_, b_, cp = a.detach().requires_grad_(), b.detach().requires_grad_(), c_prev.detach().requires_grad_()
+                z = a_ + b_
+                i, f, g, o = torch.sigmoid(z[:, :H]), torch.sigmoid(z[:, H:2 * H]), torch.tanh(z[:, 2 * H:3 * H]), torch.sigmoid(z[:, 3 * H:])
+                cn = f * (cp if cp.shape[0] == rows else cp.repeat(rows // cp.shape[0], 1)) + i * g
+                hn = o * torch.tanh(cn)
+                outs, gs = zip(*[(t, g_) for t, g_ in ((hn, gh), (cn, gc)) if g_ is not None])
+                da, db, dcp = torch.autograd.grad(outs, (a_, b_, cp), gs)
+            return da, db, dcp
+        dz, dcp = F.lstm_cell_bwd(act, c_prev, c, gh, gc)
+        if c_prev.shape[0] != rows:
+            dcp = dcp.reshape(rows // c_prev.shape[0], c_prev.shape[0], H).sum(0)
+        return dz, dz, (dcp if ctx.needs_input_grad[2] else None)

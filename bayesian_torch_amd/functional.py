@@ -1,4 +1,4 @@
-"""Functional form of the four fused forwards and of their backward: tensors in, C-ABI calls, tensors out.  The layer modules
+"""Functional form of the four fused forwards, of their backward and of the LSTM cell: tensors in, C-ABI calls, tensors out.  The layer modules
 (layers/_fused.py, _family.py) add the MC frame, the call coordinates, the pack check and the KL wiring on top of ``fused_forward``."""
 import ctypes as C
 import math
@@ -370,6 +370,77 @@ def mc_epilogue(logits):
     with _lib.on(logits.device):
         _lib.check(_lib.lib().bt_mc_epilogue(S, B, Cc, logits.data_ptr(), packed.data_ptr(), _lib.stream_ptr(logits.device)))
     return packed
+
+
+def _cell_rows(t, H, what):
+    """A [rows, H] operand the LSTM cell kernels address by row stride -> (tensor, rows, stride). A view whose rows are contiguous (one
+    time slab of a [rows, T, H] buffer) stays a view; anything else is validated, and made contiguous, by ``_lib.dev_f32``."""
+    if t is None:
+        return None, 0, H
+    if t.dim() != 2 or t.shape[1] != H:
+        raise RuntimeError(f"{what}: expected [rows, {H}], got {tuple(t.shape)}")
+    if t.is_contiguous() or t.stride(1) != 1 or t.stride(0) < H:
+        return _lib.dev_f32(t, what), t.shape[0], H
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} is on {t.device}: bayesian_torch_amd runs on a HIP (MI355X) device only; there is no CPU implementation of this path")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} must be float32, got {t.dtype}")
+    return t, t.shape[0], t.stride(0)
+
+
+def _cell_out(t, rows, H, device, what):
+    """A result of the cell forward: a fresh [rows, H] tensor, or the caller's row-strided view (written in place) -> (tensor, stride)."""
+    if t is None:
+        return torch.empty((rows, H), dtype=torch.float32, device=device), H
+    if t.dim() != 2 or tuple(t.shape) != (rows, H) or t.dtype != torch.float32 or t.device != device or (H > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < H):
+        raise RuntimeError(f"{what}: expected a float32 [{rows}, {H}] view with contiguous rows on {device}, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t, (t.stride(0) if rows > 1 else H)
+
+
+def lstm_cell_fwd(a, b, c_prev, h_out=None, c_out=None, want_act=False):
+    """The LSTM cell of one time step on its HIP kernel (bt_lstm_cell_fwd): z = a + b ([rows, 4H], gate order i, f, g, o; b may be None),
+    c = f * c_prev + i * g, h = o * tanh(c). c_prev: [c_rows, H] with c_rows = rows or a divisor of it (row r reads row r % c_rows: a
+    state shared by the MC samples); rows may be strided. h_out / c_out: row-strided [rows, H] views to write into (a slab of a
+    sequence buffer), made when None. want_act: also return the activated gates [rows, 4H] for ``lstm_cell_bwd``.
+    -> (h, c, act or None)."""
+    a, b = _lib.dev_f32(a, "a"), _lib.dev_f32(b, "b")
+    if a.dim() != 2 or a.shape[1] % 4 or a.shape[1] == 0 or (b is not None and b.shape != a.shape):
+        raise RuntimeError(f"lstm_cell_fwd: a and b are [rows, 4H], got {tuple(a.shape)} and {None if b is None else tuple(b.shape)}")
+    rows, H = a.shape[0], a.shape[1] // 4
+    dev = a.device
+    c_prev, c_rows, ld_c = _cell_rows(c_prev, H, "c_prev")
+    if c_prev is None or c_rows < 1 or rows % c_rows:
+        raise RuntimeError(f"lstm_cell_fwd: c_prev has {c_rows} rows, the gates {rows}")
+    h_out, ld_h = _cell_out(h_out, rows, H, dev, "h_out")
+    c_out, ld_o = _cell_out(c_out, rows, H, dev, "c_out")
+    if ld_h != ld_o:
+        raise RuntimeError("lstm_cell_fwd: h_out and c_out must have one row stride")
+    act = torch.empty((rows, 4 * H), dtype=torch.float32, device=dev) if want_act else None
+    with _lib.on(dev):
+        _lib.check(_lib.lib().bt_lstm_cell_fwd(rows, H, a.data_ptr(), _lib.ptr(b), c_prev.data_ptr(), c_rows, ld_c, h_out.data_ptr(), c_out.data_ptr(), ld_o,
+                                               _lib.ptr(act), _lib.stream_ptr(dev)))
+    return h_out, c_out, act
+
+
+def lstm_cell_bwd(act, c_prev, c_new, grad_h, grad_c):
+    """Gradients of ``lstm_cell_fwd`` on the HIP kernel (bt_lstm_cell_bwd), the closed form on the saved activations. grad_h / grad_c:
+    [rows, H] (rows may be strided) or None for zero. -> (dz [rows, 4H], the gradient of a and of b alike; dc_prev [rows, H], per row:
+    the caller sums a shared c_prev's over the samples)."""
+    act = _lib.dev_f32(act, "act")
+    rows, H = act.shape[0], act.shape[1] // 4
+    dev = act.device
+    c_prev, c_rows, ld_c = _cell_rows(c_prev, H, "c_prev")
+    c_new, n_rows, ld_cn = _cell_rows(c_new, H, "c_new")
+    grad_h, gh_rows, ld_gh = _cell_rows(grad_h, H, "grad_h")
+    grad_c, gc_rows, ld_gc = _cell_rows(grad_c, H, "grad_c")
+    if c_prev is None or c_new is None or c_rows < 1 or rows % c_rows or n_rows != rows or (grad_h is not None and gh_rows != rows) or (grad_c is not None and gc_rows != rows):
+        raise RuntimeError("lstm_cell_bwd: c_new, grad_h and grad_c have the gates' rows, c_prev those or a divisor of them")
+    dz = torch.empty((rows, 4 * H), dtype=torch.float32, device=dev)
+    dc_prev = torch.empty((rows, H), dtype=torch.float32, device=dev)
+    with _lib.on(dev):
+        _lib.check(_lib.lib().bt_lstm_cell_bwd(rows, H, act.data_ptr(), c_prev.data_ptr(), c_rows, ld_c, c_new.data_ptr(), ld_cn, _lib.ptr(grad_h), ld_gh,
+                                               _lib.ptr(grad_c), ld_gc, dz.data_ptr(), dc_prev.data_ptr(), _lib.stream_ptr(dev)))
+    return dz, dc_prev
 
 
 def fused_backward(x, grad_out, mu_w, rho_w, packed, *, flip=False, conv=None, S=1, shared_x=True, need_x=True, need_w=True,

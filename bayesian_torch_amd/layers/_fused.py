@@ -35,6 +35,7 @@ class FusedBayesLayer(BaseVariationalLayer_):
     _flip = False
     _wname = "weight"    # parameter suffix: mu_weight / mu_kernel
     _output_stage = True  # forward() applies post_scale / post_shift / post_relu / post_pool (what bayesian_torch_amd.fuse folds into)
+    _kl_muted = False     # set by an owner that calls this layer several times per forward and takes its KL term once (layers/_lstm.py): a collecting context gets none
 
     # ------------------------------------------------------------------ construction
     def _build(self, wshape, bias, eps_bias_last=False, n_out=None):
@@ -240,7 +241,7 @@ class FusedBayesLayer(BaseVariationalLayer_):
         if self.dnn_to_bnn_flag:
             return_kl = False
         ctx = mc.current()
-        collect = ctx is not None and ctx.collect_kl
+        collect = ctx is not None and ctx.collect_kl and not self._kl_muted
         return ctx, collect, return_kl or collect, return_kl
 
     def _call_coords(self, ctx, rows):

@@ -394,6 +394,31 @@ int bt_mc_epilogue(int32_t S, int32_t B, int32_t C, const float *logits, float *
  * (models/deterministic/resnet_large.py:120). Same comparisons as torch's max_pool2d (NaNs propagate): the same bits. */
 int bt_maxpool_3x3s2(const float *in, float *out, int64_t planes, int32_t H, int32_t W, bt_stream_t stream);
 
+/* The LSTM cell behind a time step's two Linear launches (layers LSTMReparameterization / LSTMFlipout): element-wise, memory-bound.
+ * a, b: contiguous [rows][4H], the input-to-hidden and hidden-to-hidden maps' outputs, biases included; b may be null. Gate order over
+ * the 4H columns: i, f, g, o (rnn_variational.py:107-153):
+ *   i, f, o = sigmoid(z), g = tanh(z) over z = a + b;   c = f * c_prev + i * g;   h = o * tanh(c).
+ * c_prev: c_rows rows of stride ld_c (floats); c_rows is rows or a divisor of it and row r reads row r % c_rows -- an initial state
+ * shared by the MC samples of a sample-major batch. h_out, c_out: rows rows of stride ld_out, so a step can write its slab of a
+ * sequence buffer. act: null for inference, else it receives the four activated gates as [rows][4H] for bt_lstm_cell_bwd.
+ * The transcendentals are the hardware's exp2 / rcp, written so that an overflowing exponential lands on the limit (0, 1, -1).
+ * Accesses are 16 bytes wide when H % 4 == 0, every pointer given is 16-byte aligned and ld_c, ld_out are multiples of 4, else 4
+ * bytes wide with the same values. BT_ERR_BAD_ARG, before any launch: rows < 1, H < 1, a null a / c_prev / h_out / c_out, c_rows
+ * not dividing rows, ld_c < H or ld_out < H. */
+int bt_lstm_cell_fwd(int64_t rows, int64_t H, const float *a, const float *b, const float *c_prev, int64_t c_rows, int64_t ld_c,
+                     float *h_out, float *c_out, int64_t ld_out, float *act, bt_stream_t stream);
+/* Its backward, the closed form on the saved activations act = (i, f, g, o) [rows][4H], c_prev as given to the forward and the
+ * forward's c_out as c_new (row stride ld_cn):
+ *   dc = grad_c + grad_h o (1 - tanh^2 c_new);  di = dc g i (1 - i);  df = dc c_prev f (1 - f);  dg = dc i (1 - g^2);
+ *   do = grad_h tanh(c_new) o (1 - o);  dc_prev = dc f.
+ * grad_h, grad_c (row strides ld_gh, ld_gc) may each be null: zero. dz: contiguous [rows][4H] = (di, df, dg, do), the gradient of a
+ * and of b alike. dc_prev: contiguous [rows][H], per row -- the gradient of a c_prev shared by the samples is its sum over them
+ * (the caller's). Access widths and BT_ERR_BAD_ARG as bt_lstm_cell_fwd (null act / c_prev / c_new / dz / dc_prev; the stride of a
+ * null gradient is not looked at). */
+int bt_lstm_cell_bwd(int64_t rows, int64_t H, const float *act, const float *c_prev, int64_t c_rows, int64_t ld_c, const float *c_new,
+                     int64_t ld_cn, const float *grad_h, int64_t ld_gh, const float *grad_c, int64_t ld_gc, float *dz, float *dc_prev,
+                     bt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
