@@ -18,6 +18,7 @@ KL_RHO_IS_SIGMA = 1
 KL_PRIOR_LAPLACE = 2
 PRIOR_NORMAL, PRIOR_LAPLACE = 0, 1
 DRAWS_EPS_PACKED = 1   # bt_rng.flags: eps_w holds [S] packed images (bt_pack_eps)
+LOWRANK_MAX_R = 4      # BT_LOWRANK_MAX_R: ranks the fused forward multiplies in registers (above: the bt_lowrank_mean pre-pass)
 DRAWS_SIGNS_PACKED = 2  # bt_rng.flags: sign_in / sign_out hold [S] byte images (bt_pack_signs); Flipout, with DRAWS_EPS_PACKED
 
 
@@ -110,6 +111,11 @@ _PROTOS = {
     "bt_rng_sign_fill": (C.c_int, [C.POINTER(bt_rng), C.c_uint32, C.c_int32, C.c_int64, _vp, _vp]),
     "bt_rng_philox_raw": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "bt_mc_epilogue": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "bt_lowrank_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int32, C.c_float, _vp, _vp, C.POINTER(bt_rng),
+                                        C.POINTER(bt_epilogue), _vp, _vp]),
+    "bt_lowrank_mean": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.POINTER(bt_rng), _vp, _vp]),
+    "bt_kl_lowrank_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "bt_kl_lowrank": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bt_lstm_cell_fwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
     "bt_lstm_cell_bwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
 }

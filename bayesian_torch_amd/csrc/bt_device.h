@@ -31,7 +31,7 @@ __host__ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_
   }
 }
 
-// Coordinates of one draw stream. tensor: 0 eps_w, 1 eps_b, 2 sign_in, 3 sign_out.
+// Coordinates of one draw stream. tensor: 0 eps_w, 1 eps_b, 2 sign_in, 3 sign_out, 4 z (the low-rank layers' factor draw).
 struct RngKey {
   uint32_t seed_lo, seed_hi, call, layer_tensor;  // layer_tensor = layer_id | tensor << 28
 };

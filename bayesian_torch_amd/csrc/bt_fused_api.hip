@@ -1,4 +1,5 @@
 // C-ABI entry points of the four fused forwards: argument validation, geometry, launch.
+#include <math.h>
 #include <string.h>
 
 #include "bt_fused_fwd.h"
@@ -282,6 +283,52 @@ extern "C" int bt_flipout_conv2d_dwin_fwd(const bt_conv2d_geom* g, const bt_dwin
                                           const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g || !w) return bt::set_error(BT_ERR_BAD_ARG, "bt_flipout_conv2d_dwin_fwd: null geometry");
   return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_dwin_fwd", nullptr, w}, stream);
+}
+
+namespace bt {
+int launch_lowrank(const FwdArgs& a, FwdArgs& ran, hipStream_t stream);   // bt_fused_lowrank.hip
+}
+
+extern "C" int bt_lowrank_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const float* x, int64_t x_sample_stride, const float* mean, int64_t mean_stride,
+                                     const float* L, int32_t R, float d, const float* z, const float* eps_w, const bt_rng* rng, const bt_epilogue* ep,
+                                     float* out, bt_stream_t stream) {
+  using namespace bt;
+  const char* who = "bt_lowrank_conv2d_fwd";
+  char msg[256];
+  auto bad = [&](const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return set_error(BT_ERR_BAD_ARG, msg);
+  };
+  if (!g) return bad("null geometry");
+  if (!mean || !rng) return bad("null argument");
+  if (R < 0 || R > BT_LOWRANK_MAX_R) return bad("R must be in [0, BT_LOWRANK_MAX_R]");
+  if (R > 0 && !L) return bad("R > 0 needs L");
+  if (!(d > 0.f)) return bad("d must be > 0");
+  if (mean_stride < 0) return bad("negative mean_stride");
+  if (g->groups != 1) return bad("groups must be 1");
+  if ((eps_w && R > 0 && !z) || (!eps_w && z)) return bad("supply both draws (z, eps_w) or neither");
+  if (ep && (ep->pool != BT_POOL_NONE || ep->residual || ep->relu || ep->scale || ep->shift))
+    return set_error(BT_ERR_UNSUPPORTED, "bt_lowrank_conv2d_fwd: no fused output stage (max-pool, residual, ReLU, scale / shift)");
+  // the mean-field call's checks of the geometry and the 32-bit offsets, on a parameter block whose (mu, rho) is the mean
+  bt_params p;
+  memset(&p, 0, sizeof(p));
+  p.mu_w = mean, p.rho_w = mean, p.prior_kind = BT_PRIOR_NORMAL;
+  bt_draws dr;
+  memset(&dr, 0, sizeof(dr));
+  dr.eps_w = eps_w, dr.rng = *rng;
+  dr.rng.flags = 0;
+  const Call c{false, false, *g, S, x, x_sample_stride, &p, &dr, nullptr, out, nullptr, nullptr, 0, who, nullptr, nullptr};
+  if (int rc = c.validate()) return rc;
+  FwdArgs a, r;
+  c.fill_args(false, a);
+  if (a.w_elems * (R > 0 ? R : 1) >= (1ll << 30) || (long long)(S - 1) * mean_stride + a.w_elems >= (1ll << 40))
+    return set_error(BT_ERR_UNSUPPORTED, "bt_lowrank_conv2d_fwd: L of 2^30 elements or more exceeds the kernel's 32-bit offsets");
+  a.lowrank = 1, a.lr_R = R, a.lr_L = R > 0 ? L : mean, a.lr_z = (eps_w && R > 0) ? z : nullptr, a.lr_mean_stride = mean_stride, a.lr_sd = sqrtf(d);
+  const int rc = launch_lowrank(a, r, (hipStream_t)stream);
+  if (rc != BT_OK) return rc;
+  const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, 0, 0};
+  for (int i = 0; i < 16; ++i) g_launch_info[i] = v[i];
+  return BT_OK;
 }
 
 extern "C" size_t bt_fused_scratch_bytes(const bt_conv2d_geom* g, int32_t S) {

@@ -63,17 +63,29 @@ struct FwdArgs {
   int dwin;
   int KD, D, Do, SD, DD, PD, Cigr;
   uint32_t inv_kd, inv_do;   // ceil(2^32 / KD), ceil(2^32 / Do) (0: divide), split_fill_inverses
+  // low-rank weight source (bt_lowrank_conv2d_fwd, the kernel's LOWRANK form): w = mean + sum_{j < lr_R} L[i][j] * z_s[j] + lr_sd * eps.
+  // mu_w above is the mean, read at mu_w + s * lr_mean_stride; lr_L is row-major [w_elems][lr_R] (never null: the mean when lr_R == 0);
+  // lr_z is the supplied [S][lr_R] (the injected instantiation), else null: tensor 4 of the call's draw streams, Philox block 0.
+  int lowrank;
+  const float *lr_L, *lr_z;
+  long long lr_mean_stride;
+  float lr_sd;
+  int lr_R;
 };
 
 // Plan-only digest of the argument block: every field in declaration order, without the two padding holes (behind sample0, at the end).
-// The depth-window fields behind inv_uw are folded in only when the launch is one: every other launch hashes the bytes it always did.
+// The depth-window fields behind inv_uw are folded in only when the launch is one, and the low-rank fields behind those likewise: every
+// other launch hashes the bytes it always did.
 inline uint64_t digest_arg(uint64_t h, const FwdArgs& a) {
   constexpr size_t hole = offsetof(FwdArgs, sample0) + sizeof(uint32_t), end = offsetof(FwdArgs, inv_uw) + sizeof(uint32_t);
   constexpr size_t end_dw = offsetof(FwdArgs, inv_do) + sizeof(uint32_t);
-  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && offsetof(FwdArgs, dwin) == end && sizeof(FwdArgs) == end_dw + 4, "FwdArgs padding moved: name the holes here");
+  constexpr size_t end_lr = offsetof(FwdArgs, lr_R) + sizeof(int);
+  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && offsetof(FwdArgs, dwin) == end && offsetof(FwdArgs, lowrank) == end_dw && sizeof(FwdArgs) == end_lr,
+                "FwdArgs padding moved: name the holes here");
   h = fnv1a(h, &a, hole);
   h = fnv1a(h, &a.call_base, end - offsetof(FwdArgs, call_base));
-  return a.dwin ? fnv1a(h, &a.dwin, end_dw - end) : h;
+  if (a.dwin) h = fnv1a(h, &a.dwin, end_dw - end);
+  return a.lowrank ? fnv1a(h, &a.lowrank, end_lr - end_dw) : h;
 }
 
 // The split-precision chains (bt_fused_split.hip, bt_fused_split_flip.hip), for every translation unit that calls them. Each works on

@@ -137,7 +137,12 @@ __device__ __forceinline__ double block_sum_all(double v, double* scratch) {  //
 // The gathers work on the virtual operand [B * Do][Ci * KD][H][W]; where they form an address, the launch image gives the window's first
 // plane z0 and launch channel c' = (ci, j) the plane ci * D + z0 + j * DD, masked like the zero padding where that depth is outside
 // [0, D). The same sign rule: one sign per real element.
-template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false, bool DWIN = false>
+// LOWRANK: the weight source is a low-rank multivariate normal (FwdArgs::lowrank: bt_lowrank_conv2d_fwd) instead of the mean-field
+// (mu, rho) pair: w = mean + sum_{j < R} L[i][j] * z_s[j] + sd * eps_i, j ascending, one rounding per operation. The rho load becomes the
+// load of the element's R <= 4 values of L, z_s is taken once per workgroup and sample into registers (tensor 4 of the draw streams, or
+// read), eps is the stream the other forms draw. No softplus, no bias stage, no KL sweep. An instantiation unit of its own
+// (bt_fused_lowrank.hip), so that the other forms carry none of it.
+template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false, bool DWIN = false, bool LOWRANK = false>
 __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   unsigned long long* const dbg_ = kStamps ? a.dbg : nullptr;  // stage stamps: diagnostic build only (make STAMPS=1)
   constexpr int CWM = 4 / CWN;
@@ -150,6 +155,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   static_assert(!LINEAR || TRANS, "Linear always stores with lanes along the output features");
   static_assert(!UPD || (!LINEAR && !INJ), "the input-dilated form: convolutions, on-chip draws");
   static_assert(!DWIN || (!LINEAR && !INJ && !UPD), "the depth-window form: convolutions, on-chip draws, not input-dilated");
+  static_assert(!LOWRANK || (!FLIP && !LINEAR && !UPD && !DWIN), "the low-rank form: plain convolutions, Reparameterization");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];  // ONE LDS object
   int4* const taptab = reinterpret_cast<int4*>(smem + 2 * BUF_WORDS);
@@ -395,6 +401,20 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   }
   const float* const sig_or_rho = a.rho_w;
   const bool have_sigma = false;  // the general kernel always computes softplus itself
+  // LOWRANK: the sample's mean, and z_s[0..R) in registers (entries past R are never multiplied)
+  [[maybe_unused]] const float* const lr_mean = LOWRANK ? a.mu_w + (long long)s * a.lr_mean_stride : nullptr;
+  [[maybe_unused]] const int lr_R = LOWRANK ? a.lr_R : 0;
+  [[maybe_unused]] float lr_z[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (LOWRANK) {
+    if constexpr (INJ) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lr_z[j] = j < lr_R ? a.lr_z[(long long)s * lr_R + j] : 0.f;
+    } else {
+      RngKey kz = key_w;
+      kz.layer_tensor = layer_tensor_word(a.layer_id, 4);
+      philox_normal4(kz, sample, 0u, lr_z);
+    }
+  }
 
   // One stage of producer work. All global loads of the stage (weights, then activations) are issued before any of
   // them is consumed, unconditionally on clamped offsets and with no select between them (a load under a per-lane
@@ -416,6 +436,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
     if (pst) dbg_[239] = __builtin_amdgcn_s_memtime();
     // -------- weights: loads -----------------------------------------------------------------------------------------------
     float mu[UMAX][4], rs[UMAX][4], ep[UMAX][4];
+    [[maybe_unused]] float lrl[LOWRANK ? UMAX : 1][4][4];  // LOWRANK: the element's row of L
     uint32_t ue0[UMAX];
     unsigned uval[UMAX];  // bit j: element j exists
 #pragma unroll
@@ -446,8 +467,14 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const uint32_t sb = ((val >> j) & 1u) ? base + (uint32_t)(j * T) : 0u;
-            mu[i][j] = a.mu_w[sb];
-            rs[i][j] = sig_or_rho[sb];
+            if constexpr (LOWRANK) {
+              mu[i][j] = lr_mean[sb];
+#pragma unroll
+              for (int q = 0; q < 4; ++q) lrl[i][j][q] = a.lr_L[q < lr_R ? sb * (uint32_t)lr_R + (uint32_t)q : 0u];  // (a uniform select of the offset: the loads stay unconditional)
+            } else {
+              mu[i][j] = a.mu_w[sb];
+              rs[i][j] = sig_or_rho[sb];
+            }
             if constexpr (INJ) ep[i][j] = eps_w_s[sb];
           }
         }
@@ -592,9 +619,19 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const bool ev = (uval[i] >> j) & 1u;
-            const float sg = have_sigma ? rs[i][j] : softplus(rs[i][j]);
-            const float dl = __fmul_rn(sg, ev ? ep[i][j] : 0.f);
-            const float w0 = FLIP ? mu[i][j] : __fadd_rn(mu[i][j], dl);
+            float w0, dl;
+            if constexpr (LOWRANK) {
+              w0 = mu[i][j];
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                if (q < lr_R) w0 = __fadd_rn(w0, __fmul_rn(lrl[i][j][q], lr_z[q]));
+              dl = __fmul_rn(a.lr_sd, ev ? ep[i][j] : 0.f);
+              w0 = __fadd_rn(w0, dl);
+            } else {
+              const float sg = have_sigma ? rs[i][j] : softplus(rs[i][j]);
+              dl = __fmul_rn(sg, ev ? ep[i][j] : 0.f);
+              w0 = FLIP ? mu[i][j] : __fadd_rn(mu[i][j], dl);
+            }
             Wt0[(u_kc[i] + j) * WS + u_r[i]] = ev ? w0 : 0.f;
             if (FLIP) Wt1[(u_kc[i] + j) * WS + u_r[i]] = ev ? dl : 0.f;
           }
@@ -718,7 +755,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   float* const bias1 = smem + BN;  // flipout: sigma_b*eps_b
   float* const osc = smem + 2 * BN;  // output stage: per-channel scale (1 when absent)
   float* const osh = smem + 3 * BN;  //               per-channel shift (0 when absent)
-  const bool kl_block = a.do_kl && (int)blockIdx.x < a.kl_slices;
+  const bool kl_block = !LOWRANK && a.do_kl && (int)blockIdx.x < a.kl_slices;  // (the low-rank KL is bt_kl_lowrank's)
 
   // The two roles are separate control-flow arms with the same number of workgroup barriers, so the accumulator
   // registers live only in the consumer arm and the producer arm gets the whole register budget for loads in flight.
@@ -733,7 +770,8 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
     if (stamp) dbg_[127] = __builtin_amdgcn_s_memtime();
     // bias draw for this workgroup's output channels
     if (ptid < BN) {
-      const ChannelConsts c = channel_consts<FLIP, INJ>(a, key_w, s, g, n0 + ptid);
+      ChannelConsts c = {0.f, 0.f, 1.f, 0.f};  // LOWRANK: no bias, no folded output stage
+      if constexpr (!LOWRANK) c = channel_consts<FLIP, INJ>(a, key_w, s, g, n0 + ptid);
       bias0[ptid] = c.bias0;
       if (FLIP) bias1[ptid] = c.bias1;
       osc[ptid] = c.scale;

@@ -136,7 +136,7 @@ extern "C" const char* bt_last_error_string(void) { return bt::g_err; }
 extern "C" int bt_rng_normal_fill(const bt_rng* rng, uint32_t tensor_id, int32_t S, int64_t rows, int64_t inner, int64_t taps, float* out,
                                   bt_stream_t stream) {
   using namespace bt;
-  if (!rng || !out || S <= 0 || rows <= 0 || inner <= 0 || taps <= 0 || tensor_id > 3 || S > 65535)
+  if (!rng || !out || S <= 0 || rows <= 0 || inner <= 0 || taps <= 0 || tensor_id > 4 || S > 65535)
     return set_error(BT_ERR_BAD_ARG, "bt_rng_normal_fill: bad argument");
   const long long nq = (long long)rows * taps * (((long long)inner + 3) >> 2);
   if (nq > (1ll << 32)) return set_error(BT_ERR_UNSUPPORTED, "bt_rng_normal_fill: tensor too large");

@@ -272,6 +272,80 @@ def rng_fill_sign(seed, call, layer_id, sample0, tensor_id, S, shape, device, ca
     return out
 
 
+def lowrank_mean(mu, L, S, z=None, *, seed=0, call=0, layer_id=0, sample0=0, call_base=None, out=None):
+    """The mean pre-pass of a low-rank layer whose rank exceeds the fused forward's in-kernel bound (bt_lowrank_mean):
+    m[s] = mu + L @ z_s as one fp32 chain per element, j ascending -> [S, n]. z: [S, r], or None for the on-chip stream (tensor 4 of
+    the call's coordinates). out: a contiguous fp32 [S, n] device tensor to write into (a layer's workspace), made when None."""
+    mu, L, z = _lib.dev_f32(mu, "mu"), _lib.dev_f32(L, "L"), _lib.dev_f32(z, "z")
+    n, r = L.shape
+    if mu.numel() != n or (z is not None and tuple(z.shape) != (S, r)):
+        raise RuntimeError(f"lowrank_mean: mu [{mu.numel()}], L {tuple(L.shape)}, z {None if z is None else tuple(z.shape)} do not fit S={S}")
+    if out is None:
+        out = torch.empty((S, n), dtype=torch.float32, device=mu.device)
+    elif tuple(out.shape) != (S, n) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != mu.device:
+        raise RuntimeError("lowrank_mean: out must be a contiguous fp32 [S, n] tensor on mu's device")
+    R = _rng(seed, call, layer_id, sample0, call_base)
+    with _lib.on(mu.device):
+        _lib.check(_lib.lib().bt_lowrank_mean(mu.data_ptr(), L.data_ptr(), n, r, S, _lib.ptr(z), C.byref(R), out.data_ptr(), _lib.stream_ptr(mu.device)))
+    return out
+
+
+def lowrank_conv2d(x, mean, L, d, wshape, conv, *, S=1, shared_x=True, z=None, eps_w=None, seed=0, call=0, layer_id=0, sample0=0, call_base=None):
+    """The fused forward with a low-rank multivariate weight source (bt_lowrank_conv2d_fwd): sample s convolves x with
+    w_s = mean_s + L @ z_s + sqrt(d) * eps_s, formed on chip. mean: [n] (one for all samples) or [S, n] (lowrank_mean's output);
+    L: [n, R] with R <= _lib.LOWRANK_MAX_R, or None (R = 0); d: the constant diagonal (a float > 0); wshape = (Co, Ci, kh, kw), n its
+    product; conv as in fused_forward (groups 1). z [S, R] and eps_w [S, n]: both supplied, or both None for the on-chip streams.
+    -> out [S * B, Co, Ho, Wo]."""
+    x, mean, L = _lib.dev_f32(x, "input"), _lib.dev_f32(mean, "mean"), _lib.dev_f32(L, "L")
+    z, eps_w = _lib.dev_f32(z, "z"), _lib.dev_f32(eps_w, "eps_w")
+    dev = x.device
+    wshape = tuple(int(v) for v in wshape)
+    n = math.prod(wshape)
+    R = 0 if L is None else L.shape[1]
+    if mean.numel() not in (n, S * n) or (L is not None and L.shape[0] != n):
+        raise RuntimeError(f"lowrank_conv2d: mean [{mean.numel()}] / L do not fit a kernel of {n} weights and S={S}")
+    if (eps_w is not None and R > 0 and z is None) or (eps_w is None and z is not None):
+        raise RuntimeError("lowrank_conv2d: supply both draws (z, eps_w) or neither")
+    if eps_w is not None and (eps_w.numel() != S * n or (R > 0 and tuple(z.shape) != (S, R))):
+        raise RuntimeError(f"lowrank_conv2d: the supplied draws do not hold S={S} samples")
+    B, geom, x_elems, tail = _geometry(x, _Shape(wshape), conv, S, shared_x)
+    out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev)
+    Rg = _rng(seed, call, layer_id, sample0, call_base)
+    with _lib.on(dev):
+        _lib.check(_lib.lib().bt_lowrank_conv2d_fwd(C.byref(geom), S, x.data_ptr(), 0 if shared_x else x_elems, mean.data_ptr(), n if mean.numel() == S * n and S > 1 else 0,
+                                                    _lib.ptr(L), R, float(d), _lib.ptr(z) if R > 0 else None, _lib.ptr(eps_w), C.byref(Rg), None, out.data_ptr(),
+                                                    _lib.stream_ptr(dev)))
+    return out
+
+
+class _Shape:
+    """What ``_geometry`` reads of a weight tensor: its shape."""
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+
+
+def kl_lowrank(mu, L, d, prior_mean, prior_var, owner="kl_lowrank", bad_pivots=None):
+    """KL( N(mu, L L^T + d I) || N(prior_mean, diag(prior_var)) ) on the HIP kernels (bt_kl_lowrank: an fp64 sweep and an r x r fp64
+    Cholesky, two launches, nothing synchronised) -> fp32 device tensor [2] = (KL, KL / n). bad_pivots: an int32 device tensor [1]
+    that counts the calls whose factorisation met a pivot that was not positive (their result is NaN), or None."""
+    mu, L = _lib.dev_f32(mu, "mu"), _lib.dev_f32(L, "L")
+    pm, pv = _lib.dev_f32(prior_mean, "prior_mean"), _lib.dev_f32(prior_var, "prior_var")
+    n, r = L.shape
+    if mu.numel() != n or pm.numel() != n or pv.numel() != n:
+        raise RuntimeError("kl_lowrank: mu, prior_mean and prior_var must have L's row count")
+    lib = _lib.lib()
+    need = int(lib.bt_kl_lowrank_workspace(n, r))
+    if need == 0:
+        raise NotImplementedError(f"kl_lowrank: rank {r} is above the factorisation kernel's limit")
+    ws = _lib.workspace((owner, "kl_lowrank"), mu.device, need)
+    out = torch.empty((2,), dtype=torch.float32, device=mu.device)
+    with _lib.on(mu.device):
+        _lib.check(lib.bt_kl_lowrank(mu.data_ptr(), L.data_ptr(), n, r, float(d), pm.data_ptr(), pv.data_ptr(), out.data_ptr(), _lib.ptr(bad_pivots),
+                                     ws.data_ptr() + _lib.WORKSPACE_BYTES, ws.numel() - _lib.WORKSPACE_BYTES, _lib.stream_ptr(mu.device)))
+    return out
+
+
 def pack_params(mu_w, rho_w):
     """Tap-major re-layout of a layer's (mu, softplus(rho)) -> (mu_packed, sigma_packed), each [Co, taps, Ci4]
     (include/bt_hip.h, bt_params). A cache of a pure function of the parameters; rebuild when they change."""

@@ -1,10 +1,12 @@
 """``Conv2dReparameterization`` -- drop-in for reference
 ``layers/variational_layers/conv_variational.py:234-407`` on the fused implicit-GEMM HIP kernel
 (bt_reparam_conv2d_fwd); Conv1d on the same kernel; Conv3d and ConvTranspose{1,2,3}d come from layers/_family.py (exact index
-re-arrangements around the same launch).  The Multivariate variant is outside this build's scope."""
+re-arrangements around the same launch).  ``Conv2dReparameterization_Multivariate`` (reference :409-648) runs on the same kernel's
+low-rank weight source (layers/_lowrank.py)."""
 from .._family import (Conv3dReparameterization, ConvTranspose1dReparameterization,  # noqa: F401
                        ConvTranspose2dReparameterization, ConvTranspose3dReparameterization)
 from .._fused import FusedBayesLayer
+from .._lowrank import LowRankConv2dLayer
 from ..base_variational_layer import get_kernel_size
 
 __all__ = ["Conv2dReparameterization", "Conv1dReparameterization", "Conv3dReparameterization", "ConvTranspose1dReparameterization",
@@ -54,3 +56,16 @@ class Conv1dReparameterization(FusedBayesLayer):
 
     def forward(self, input, return_kl=True, residual=None):
         return self._forward(input, return_kl, residual)
+
+
+class Conv2dReparameterization_Multivariate(LowRankConv2dLayer):
+    """Drop-in for reference ``conv_variational.py:409-648``: a Conv2d whose posterior is a low-rank multivariate normal over all of
+    its weights (``mu_kernel`` [n], ``L_param`` [n, rank], constant diagonal ``D_param``). Not in ``__all__``, as in the reference:
+    import it by name. ``bias`` is accepted and ignored, as there."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, rank=1, bias=True):
+        super().__init__()
+        self._build(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, rank, bias)
+
+    def forward(self, input, return_kl=True):
+        return self._forward(input, return_kl)

@@ -80,7 +80,7 @@ def assign_layer_ids(model, first=1):
     hand-assembled model of ``bayesian_torch_amd.layers`` modules if construction-order independence matters."""
     n = first
     for m in model.modules():
-        if hasattr(m, "_layer_id") and hasattr(m, "_kl_segments"):
+        if hasattr(m, "_layer_id") and (hasattr(m, "_kl_segments") or getattr(m, "_rng_layer", False)):
             m._layer_id = n
             n += 1
     return n - first

@@ -318,7 +318,8 @@ int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg *segs, const bt_pack_k
 
 /* The on-chip draws, materialised (test / replay hook: the fused kernels never call these).
  * They emit exactly the streams the fused kernels consume for (rng, tensor_id):
- * tensor_id 0 = eps_w, 1 = eps_b, 2 = sign_in, 3 = sign_out.
+ * tensor_id 0 = eps_w, 1 = eps_b, 2 = sign_in, 3 = sign_out, 4 = z (the low-rank layers' factor draw, bt_lowrank_conv2d_fwd:
+ * bt_rng_normal_fill(rng, 4, S, 1, r, 1, ...) gives z [S][r], element j = normal number (j & 3) of Philox block (j >> 2)).
  * Stream definition. eps element (row r, inner index c, tap t) of a [rows][inner][taps] tensor (a conv kernel
  * [Co][Ci/g][kh*kw]; Linear and bias: taps = 1) is normal number (c & 3) of Philox block (e >> 2) with
  * e = (r*taps + t)*inner4 + c,  inner4 = inner rounded up to a multiple of 4  -- tap-major and quad-aligned, so the
@@ -384,6 +385,35 @@ int bt_kl_normal_bwd_segs(int32_t n_segments, const float *const *mu, const floa
 int bt_set_contraction(int mode);
 /* The mode in force (0..3): what bt_set_contraction last set, else BT_CONTRACTION, else 0. */
 int bt_get_contraction(void);
+
+/* Conv2dReparameterization_Multivariate (layers/variational_layers/conv_variational.py:409-554): the posterior is a low-rank
+ * multivariate normal over the n = Co * Ci * kh * kw weights, and sample s convolves with
+ *   w_s[i] = mean_s[i] + sum_{j < R} L[i][j] * z_s[j] + sqrt(d) * eps_s[i]      (j ascending, one fp32 rounding per operation),
+ * formed in the producers' registers of the fp32 fused forward; w_s is never written to memory. mean_s = mean + s * mean_stride
+ * (0: one mean for all samples -- mu_kernel; n: the [S][n] output of bt_lowrank_mean). L: row-major [n][R], 0 <= R <=
+ * BT_LOWRANK_MAX_R (may be NULL when R == 0). d > 0: the constant diagonal of the covariance. Draws: z [S][R] and eps_w [S][n] (the
+ * weights' natural order) are both read, or both NULL: z_s is then the first R normals of Philox block 0 of tensor 4, eps the
+ * tensor 0 stream of the mean-field layers. groups must be 1; no bias, no KL (bt_kl_lowrank). BT_ERR_BAD_ARG: R outside the range, R > 0
+ * without L, d <= 0, one draw without the other. BT_ERR_UNSUPPORTED, nothing launched: any output stage in ep (max-pool, residual, ReLU,
+ * scale / shift). out: [S][B][Co][Ho][Wo]. */
+#define BT_LOWRANK_MAX_R 4
+int bt_lowrank_conv2d_fwd(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t x_sample_stride, const float *mean,
+                          int64_t mean_stride, const float *L, int32_t R, float d, const float *z, const float *eps_w, const bt_rng *rng,
+                          const bt_epilogue *ep, float *out, bt_stream_t stream);
+/* The mean pre-pass of a rank above BT_LOWRANK_MAX_R: m[s][i] = mu[i] + sum_{j < r} L[i][j] * z_s[j], the same fp32 chain (j ascending,
+ * one rounding per operation), for all S samples; the forward then runs with R = 0, mean = m, mean_stride = n. z: [S][r], or NULL for
+ * the tensor 4 stream of rng (sample rng->sample0 + s). m: [S][n]. L: row-major [n][r]. */
+int bt_lowrank_mean(const float *mu, const float *L, int64_t n, int32_t r, int32_t S, const float *z, const bt_rng *rng, float *m,
+                    bt_stream_t stream);
+/* KL( N(mu, L L^T + d I) || N(prior_mean, diag(prior_var)) ) in closed form, accumulated in fp64 in a fixed order:
+ *   KL = 1/2 [ sum log P_i - n log d - logdet(I_r + L^T L / d) + sum (d + sum_j L_ij^2) / P_i + sum (mu_i - m_i)^2 / P_i - n ].
+ * Two launches, no host synchronisation: a sweep over the weight index (per-chunk partials of the four sums and of the lower triangle of
+ * L^T L / d), then one workgroup that adds the partials in chunk order and factorises I + G by an fp64 Cholesky in the workspace.
+ * kl_out[0] = KL, kl_out[1] = KL / n. A pivot that is not positive gives NaN in both and adds 1 to *bad_pivots (may be NULL).
+ * workspace: bt_kl_lowrank_workspace(n, r) bytes, 8-byte aligned, contents need not be initialised (0: r above 4096, unsupported). */
+size_t bt_kl_lowrank_workspace(int64_t n, int32_t r);
+int bt_kl_lowrank(const float *mu, const float *L, int64_t n, int32_t r, float d, const float *prior_mean, const float *prior_var,
+                  float *kl_out, int32_t *bad_pivots, void *workspace, size_t workspace_bytes, bt_stream_t stream);
 
 /* MC epilogue (examples/main_bayesian_cifar_dnn2bnn.py:551-557 and :402-412): from logits [S][B][C]
  * accumulate into packed[B*C + B + B*C] = [sum_s softmax | sum_s entropy | sum_s logits] (overwrites). */
