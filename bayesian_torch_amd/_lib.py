@@ -118,6 +118,9 @@ _PROTOS = {
     "bt_kl_lowrank": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bt_lstm_cell_fwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
     "bt_lstm_cell_bwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
+    "bt_avu_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "bt_avu_fwd": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bt_avu_bwd": (C.c_int, [C.c_int32] * 3 + [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

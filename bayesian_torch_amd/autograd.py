@@ -289,3 +289,25 @@ class LSTMCell(torch.autograd.Function):
         if c_prev.shape[0] != rows:
             dcp = dcp.reshape(rows // c_prev.shape[0], c_prev.shape[0], H).sum(0)
         return dz, dz, (dcp if ctx.needs_input_grad[2] else None)
+
+
+class AvU(torch.autograd.Function):
+    """The AvUC loss of [S, B, C] logits (utils/avuc_loss.py): forward on bt_avu_fwd, backward one bt_avu_bwd launch; nothing is read
+    on the host, so a training step with this loss captures in a graph. -> (loss [1], v [1]); ``stats``, a dict, receives the
+    forward's device tensors (sums, counts, thresholds, the per-row values). Only the loss is differentiable, and only in the logits:
+    thresholds and comparisons carry no gradient, as in the reference, where they pass through ``.item()``."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, threshold, unc_type, T, beta, stats):
+        r = F.avu_forward(logits.detach(), labels, unc_type, T, threshold, beta)
+        ctx.save_for_backward(logits, r["coef"], r["workspace"])
+        ctx.unc_type, ctx.T = unc_type, T
+        if stats is not None:
+            stats.update({k: v for k, v in r.items() if k not in ("loss", "v", "coef", "workspace")})
+        ctx.mark_non_differentiable(r["v"])
+        return r["loss"], r["v"]
+
+    @staticmethod
+    def backward(ctx, g, _gv):
+        logits, coef, ws = ctx.saved_tensors
+        return (F.avu_backward(logits.detach(), ctx.unc_type, ctx.T, coef, ws, g),) + (None,) * 6

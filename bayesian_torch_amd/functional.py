@@ -592,3 +592,59 @@ def kl_backward_segs(segments, grad_kl, laplace=False):
             _lib.check(L.bt_kl_normal_bwd_segs(n, arrs[0], arrs[1], arrs[2] if not laplace else None, arrs[3] if not laplace else None, numel, g.data_ptr(),
                                                _lib.KL_PRIOR_LAPLACE if laplace else 0, arrs[4], arrs[5], _lib.stream_ptr(dev)))
     return out
+
+
+AVU_THRESHOLDS = 21   # AUAvULoss: np.linspace(0, 1, 21) between the batch's smallest and largest uncertainty
+
+
+def avu_forward(logits, labels, unc_type=0, T=1, threshold=None, beta=1.0):
+    """The AvUC loss of utils/avuc_loss.py on its HIP kernels (bt_avu_fwd: a row pass and a one-workgroup finish pass, no host
+    read). logits: [S, B, C] (S Monte Carlo samples; the reference's [B, C] is S = 1); labels: [B] integers. T = 1: AvULoss against
+    ``threshold``, a one-element device tensor; T = 21: AUAvULoss. -> dict: loss [1], v [1] (AvU, or the area under AvU), sums [T, 4]
+    (n_ac, n_au, n_ic, n_iu), counts [T, 4] int32, thresholds [T] float64, coef (for ``avu_backward``), workspace, and views of the
+    workspace: confidence, uncertainty, tanh_uncertainty [B], pred, acc, first_certain [B] int32 (a row is uncertain at the thresholds
+    below index first_certain and certain from there on; T when it never is)."""
+    logits = _lib.dev_f32(logits, "logits")
+    if logits.dim() != 3:
+        raise ValueError(f"avu_forward: logits are [S, B, C], got {tuple(logits.shape)}")
+    S, B, Cc = logits.shape
+    dev = logits.device
+    if not labels.is_cuda:
+        raise RuntimeError(f"labels are on {labels.device}: bayesian_torch_amd runs on a HIP (MI355X) device only; there is no CPU implementation of this path")
+    if labels.dim() != 1 or labels.shape[0] != B or labels.dtype.is_floating_point:
+        raise ValueError(f"avu_forward: labels are [B = {B}] integers, got {tuple(labels.shape)} {labels.dtype}")
+    labels = labels.to(torch.int64).contiguous()
+    if T == 1:
+        threshold = _lib.dev_f32(threshold, "threshold")
+        if threshold is None or threshold.numel() != 1:
+            raise ValueError("avu_forward: T = 1 takes a one-element threshold tensor")
+    L = _lib.lib()
+    nbytes = L.bt_avu_workspace_bytes(S, B, Cc, T)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    v = torch.empty(1, dtype=torch.float32, device=dev)
+    sums = torch.empty((T, 4), dtype=torch.float32, device=dev)
+    counts = torch.empty((T, 4), dtype=torch.int32, device=dev)
+    thr = torch.empty(T, dtype=torch.float64, device=dev)
+    coef = torch.empty((4, T + 1), dtype=torch.float32, device=dev)
+    with _lib.on(dev):
+        _lib.check(L.bt_avu_fwd(S, B, Cc, logits.data_ptr(), labels.data_ptr(), int(unc_type), int(T), _lib.ptr(threshold), float(beta), loss.data_ptr(),
+                                v.data_ptr(), sums.data_ptr(), counts.data_ptr(), thr.data_ptr(), coef.data_ptr(), ws.data_ptr(), nbytes, _lib.stream_ptr(dev)))
+    rec_f = ws[:12 * B].view(torch.float32).view(3, B)
+    rec_i = ws[12 * B:24 * B].view(torch.int32).view(3, B)
+    return dict(loss=loss, v=v, sums=sums, counts=counts, thresholds=thr, coef=coef, workspace=ws, confidence=rec_f[0], uncertainty=rec_f[1],
+                tanh_uncertainty=rec_f[2], pred=rec_i[0], acc=rec_i[1], first_certain=rec_i[2])
+
+
+def avu_backward(logits, unc_type, T, coef, workspace, grad_loss):
+    """d loss / d logits [S, B, C] of ``avu_forward`` times ``grad_loss`` (a one-element device tensor), one launch (bt_avu_bwd) from
+    the forward's ``coef`` and ``workspace``; the softmax is recomputed from the logits."""
+    logits = _lib.dev_f32(logits, "logits")
+    S, B, Cc = logits.shape
+    dev = logits.device
+    g = _lib.dev_f32(grad_loss.reshape(1), "grad_loss")
+    dlogits = torch.empty_like(logits)
+    with _lib.on(dev):
+        _lib.check(_lib.lib().bt_avu_bwd(S, B, Cc, logits.data_ptr(), int(unc_type), int(T), coef.data_ptr(), g.data_ptr(), workspace.data_ptr(),
+                                         workspace.numel(), dlogits.data_ptr(), _lib.stream_ptr(dev)))
+    return dlogits

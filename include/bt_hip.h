@@ -449,6 +449,32 @@ int bt_lstm_cell_bwd(int64_t rows, int64_t H, const float *act, const float *c_p
                      int64_t ld_cn, const float *grad_h, int64_t ld_gh, const float *grad_c, int64_t ld_gc, float *dz, float *dc_prev,
                      bt_stream_t stream);
 
+/* AvUC calibration losses (utils/avuc_loss.py: AvULoss with T = 1, AUAvULoss with T = 21). logits: contiguous [S][B][C], S >= 1 Monte
+ * Carlo samples; labels: [B], 8-byte aligned, only compared with the prediction (an out-of-range label is "inaccurate"). Per row:
+ *   p_s = softmax(z_s);  pbar = mean_s p_s;  c = max_k pbar_k;  pred = the first index of that maximum;  acc = (pred == label);
+ *   H(p) = -sum p log(p + 1e-10);  u = H(pbar) (unc_type 0) or H(pbar) - mean_s H(p_s) (unc_type 1, S > 1);  t = tanh(u).
+ * Thresholds, in double from the fp32 u: T = 1: *threshold, one fp32 value in DEVICE memory (never read on the host); T = 21:
+ * th_0 = min u and th_20 = max u exactly, th_j = min u + x_j (max u - min u) between them, x = linspace(0, 1, 21). A row is certain at
+ * j iff (double) u <= th_j. Per threshold the four soft sums sums[j] = (n_ac, n_au, n_ic, n_iu) = (sum c (1 - t), sum c t,
+ * sum (1 - c)(1 - t), sum (1 - c) t) over the rows of each class, the four integer counts[j], and
+ *   AvU_j = (n_ac + n_iu) / (n_ac + n_au + n_ic + n_iu + 1e-10);   *v = AvU_0 (T = 1) or the trapezoid of AvU_j over x_j (T = 21);
+ *   *loss = -beta log(*v + 1e-10).
+ * Two launches (one wave per row for C <= 64, one workgroup per row above; then one workgroup over the rows), sums in a fixed order,
+ * no atomics, no host synchronisation: capturable, and the same bits from run to run. coef: [4][T + 1], what bt_avu_bwd needs of the
+ * thresholds. workspace: bt_avu_workspace_bytes(S, B, C, T) bytes, 8-byte aligned, contents need not be initialised; afterwards it
+ * holds float [3][B] = (c, u, t), int32 [3][B] = (pred, acc, the number of thresholds below u) and each sample row's softmax
+ * max / denominator as float [S][B][2], and bt_avu_bwd reads it. thresholds: [T] doubles, 8-byte aligned.
+ * BT_ERR_BAD_ARG before any launch: a null pointer (threshold may be null for T = 21), S, B or C <= 0, T not 1 or 21, unc_type not 0
+ * or 1, unc_type 1 with S == 1, a misaligned labels / thresholds / workspace. BT_ERR_WORKSPACE: workspace_bytes too small. */
+size_t bt_avu_workspace_bytes(int32_t S, int32_t B, int32_t C, int32_t T);
+int bt_avu_fwd(int32_t S, int32_t B, int32_t C, const float *logits, const int64_t *labels, int32_t unc_type, int32_t T,
+               const float *threshold, float beta, float *loss, float *v, float *sums, int32_t *counts, double *thresholds, float *coef,
+               void *workspace, size_t workspace_bytes, bt_stream_t stream);
+/* d loss / d logits as [S][B][C] times *grad_loss (one fp32 value in device memory), one launch of the row pass's shape, from the
+ * logits, coef and the workspace of the bt_avu_fwd call. Thresholds and comparisons carry no gradient; the softmax is recomputed. */
+int bt_avu_bwd(int32_t S, int32_t B, int32_t C, const float *logits, int32_t unc_type, int32_t T, const float *coef,
+               const float *grad_loss, const void *workspace, size_t workspace_bytes, float *dlogits, bt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
