@@ -121,6 +121,9 @@ _PROTOS = {
     "bt_avu_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
     "bt_avu_fwd": (C.c_int, [C.c_int32] * 3 + [_vp, _vp, C.c_int32, C.c_int32, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bt_avu_bwd": (C.c_int, [C.c_int32] * 3 + [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "bt_kl_hier": (C.c_int, [C.c_int32] + [C.POINTER(_vp)] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bt_kl_hier_bwd": (C.c_int, [C.c_int32] + [C.POINTER(_vp)] * 7 + [C.POINTER(C.c_int64), _vp] + [C.POINTER(_vp)] * 4 + [_vp]),
+    "bt_special_eval": (C.c_int, [C.c_int32, _f32p, C.c_int64, _f32p]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -241,3 +244,51 @@ def kl_normal(segments, layer_ids=None, rho_is_sigma=False, out=None, owner="kl"
                                  res.data_ptr(), workspace(owner, dev).data_ptr(), WORKSPACE_BYTES, stream_ptr(dev)))
         total = res if total is None else total + res
     return total
+
+
+def kl_hier(segs, layer_ids=None, owner="kl_hier", per_segment=False):
+    """segs: list of (mu, rho, prior_mu, log_a, log_b, a0, b0) device tensors of equal numel: the hierarchical layers' kl_loss()
+    (bt_kl_hier: the SUM over the elements). Returns a 0-dim tensor: sum over layers of (sum over the layer's segments), one launch
+    per KL_MAX_SEGMENTS segments; per_segment: also a [len(segs)] tensor of every segment's own fp32 sum."""
+    L = lib()
+    dev = segs[0][0].device
+    total = None
+    seg_sums = torch.empty(len(segs), dtype=torch.float32, device=dev) if per_segment else None
+    for c0 in range(0, len(segs), KL_MAX_SEGMENTS):
+        chunk = segs[c0:c0 + KL_MAX_SEGMENTS]
+        n = len(chunk)
+        keep = []
+        arrs = [(_vp * n)() for _ in range(7)]
+        numel = (C.c_int64 * n)()
+        for i, seg in enumerate(chunk):
+            if len(seg) != 7:
+                raise ValueError("a hierarchical KL segment is (mu, rho, prior_mu, log_a, log_b, a0, b0)")
+            ts = [dev_f32(t, "kl segment tensor") for t in seg]
+            if not all(t.numel() == ts[0].numel() for t in ts):
+                raise ValueError("kl segment tensors must have equal numel")
+            keep.append(ts)
+            for a, t in zip(arrs, ts):
+                a[i] = t.data_ptr()
+            numel[i] = ts[0].numel()
+        lay = None
+        if layer_ids is not None:
+            lay = (C.c_int32 * n)(*layer_ids[c0:c0 + n])
+        res = torch.empty((), dtype=torch.float32, device=dev)
+        so = None if seg_sums is None else seg_sums.data_ptr() + 4 * c0
+        with on(dev):
+            check(L.bt_kl_hier(n, *arrs, numel, lay, res.data_ptr(), so, workspace(owner, dev).data_ptr(), WORKSPACE_BYTES, stream_ptr(dev)))
+        total = res if total is None else total + res
+    return (total, seg_sums) if per_segment else total
+
+
+SPECIAL_DIGAMMA, SPECIAL_TRIGAMMA, SPECIAL_LGAMMA, SPECIAL_X_TRIGAMMA_M1 = 0, 1, 2, 3
+
+
+def special_eval(kind, x):
+    """The kernels' fp32 special functions evaluated on the CPU (bt_special_eval): x a CPU float32 tensor of positive values."""
+    x = x.detach().to(torch.float32).contiguous()
+    if x.is_cuda:
+        raise RuntimeError("special_eval is the host-side check of the special functions: it takes a CPU tensor")
+    out = torch.empty_like(x)
+    check(lib().bt_special_eval(int(kind), C.cast(x.data_ptr(), _f32p), x.numel(), C.cast(out.data_ptr(), _f32p)))
+    return out

@@ -237,6 +237,30 @@ class KLNormal(torch.autograd.Function):
         return tuple(grads)
 
 
+class KLHier(torch.autograd.Function):
+    """kl = sum over the given (mu, rho, prior_mu, log_a, log_b, a0, b0) groups of SUM_i(A_i + B_i), the hierarchical layers' kl_loss()
+    (reference hiearchial_variational_layers.py:331-381), on bt_kl_hier: one launch forward, one launch backward (bt_kl_hier_bwd) for
+    all groups; gradients to mu, rho, log_a, log_b -- only the ones that require them are computed."""
+
+    @staticmethod
+    def forward(ctx, info, *tensors):
+        owner, lids = info
+        segs = [tuple(t.detach() for t in tensors[i:i + 7]) for i in range(0, len(tensors), 7)]
+        ctx.save_for_backward(*tensors)
+        return _lib.kl_hier(segs, layer_ids=list(lids), owner=owner)
+
+    @staticmethod
+    def backward(ctx, g):
+        t = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:]
+        segs = [tuple(t[i:i + 7]) for i in range(0, len(t), 7)]
+        needs = [(need[i], need[i + 1], need[i + 3], need[i + 4]) for i in range(0, len(t), 7)]
+        grads = [None]
+        for gmu, grho, gla, glb in F.kl_hier_backward(segs, g, needs):
+            grads += [gmu, grho, None, gla, glb, None, None]
+        return tuple(grads)
+
+
 class KLValue(torch.autograd.Function):
     """get_kl_loss of a training step whose layers differentiate their own KL terms (FusedForward, opts["kl"] + opts["kl_stub"]):
     the value from ONE bt_kl_normal launch over all segments; backward gives the upstream gradient to every layer's placeholder --

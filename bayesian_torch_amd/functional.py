@@ -594,6 +594,39 @@ def kl_backward_segs(segments, grad_kl, laplace=False):
     return out
 
 
+def kl_hier_backward(segments, grad_kl, needs=None):
+    """[(d kl / d mu, d rho, d log_a, d log_b) * grad_kl] for every (mu, rho, prior_mu, log_a, log_b, a0, b0) segment of bt_kl_hier's
+    sum, ONE HIP launch per BT_KL_MAX_SEGMENTS tensors (bt_kl_hier_bwd). needs: per segment four booleans -- a gradient nobody asked
+    for is neither allocated nor written (None in its place); default: all."""
+    L = _lib.lib()
+    dev = segments[0][0].device
+    g = _lib.dev_f32(grad_kl.reshape(1).contiguous(), "grad_kl")
+    out = []
+    for c0 in range(0, len(segments), _lib.KL_MAX_SEGMENTS):
+        chunk = segments[c0:c0 + _lib.KL_MAX_SEGMENTS]
+        n = len(chunk)
+        arrs = [(C.c_void_p * n)() for _ in range(11)]
+        numel = (C.c_int64 * n)()
+        keep = []
+        any_out = False
+        for i, seg in enumerate(chunk):
+            ts = [_lib.dev_f32(t.detach(), "kl segment tensor") for t in seg]
+            if len(ts) != 7 or not all(t.numel() == ts[0].numel() for t in ts):
+                raise ValueError("a hierarchical KL segment is (mu, rho, prior_mu, log_a, log_b, a0, b0) of equal numel")
+            want = (True,) * 4 if needs is None else needs[c0 + i]
+            grads = tuple(torch.empty_like(ts[0]) if w else None for w in want)
+            any_out = any_out or any(want)
+            keep.append(ts)
+            out.append(grads)
+            for a, t in zip(arrs, tuple(ts) + grads):
+                a[i] = None if t is None else t.data_ptr()
+            numel[i] = ts[0].numel()
+        if any_out:
+            with _lib.on(dev):
+                _lib.check(L.bt_kl_hier_bwd(n, *arrs[:7], numel, g.data_ptr(), *arrs[7:], _lib.stream_ptr(dev)))
+    return out
+
+
 AVU_THRESHOLDS = 21   # AUAvULoss: np.linspace(0, 1, 21) between the batch's smallest and largest uncertainty
 
 

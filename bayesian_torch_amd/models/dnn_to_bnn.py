@@ -4,7 +4,8 @@ Same contract: in-place recursive swap of leaf modules whose class name contains
 "Linear" by ``<ClassName><params['type']>`` looked up in ``bayesian_torch_amd.layers``
 (AttributeError when that class does not exist), same dict keys (KeyError when one is missing), MOPED initialisation, and
 ``dnn_to_bnn_flag = True`` on every created layer.  ``get_kl_loss`` gathers every fused layer's
-(mu, rho, prior) tensors into ONE bt_kl_normal launch instead of ~12 ATen passes per layer.
+(mu, rho, prior) tensors into ONE bt_kl_normal launch instead of ~12 ATen passes per layer; the hierarchical layers
+(layers/variational_layers/hiearchial_variational_layers.py) go into bt_kl_hier launches of their own.
 """
 import bayesian_torch_amd.layers as bayesian_layers
 from bayesian_torch_amd import _lib, rng
@@ -104,10 +105,13 @@ def get_kl_loss(m):
                 if not isinstance(layer, FusedBayesLayer) and hasattr(layer, "kl_loss"):
                     kl = kl + layer.kl_loss()
             return kl
-    segs, lids, others, lap = [], [], [], []
+    segs, lids, others, lap, hier = [], [], [], [], []
     n = 0
     for layer in m.modules():
         if isinstance(layer, FusedBayesLayer):
+            if getattr(layer, "_hier_kl", False):
+                hier.append(layer)         # the hierarchical layers: their kl_loss() is another function, on its own kernel (below)
+                continue
             if check_prior_type(getattr(layer, "prior_type", "normal")) == "laplace":
                 lap.append(layer)          # (rare) its own launch: one bt_kl_normal call takes one prior kind
                 continue
@@ -126,6 +130,14 @@ def get_kl_loss(m):
             kl = KLNormal.apply((("model", id(m)), "normal", tuple(lids)), *[t for sg in segs for t in sg])
         else:
             kl = _lib.kl_normal(segs, layer_ids=lids, owner=("model", id(m)))
+    if hier:     # sum of their kl_loss() (the weights' sums; a Linear's bias is not in it, as in the reference): one bt_kl_hier launch per 64 layers
+        hsegs = [layer._hier_segment() for layer in hier]
+        if torch.is_grad_enabled() and any(sg[i].requires_grad for sg in hsegs for i in (0, 1, 3, 4)):
+            from ..autograd import KLHier
+            k = KLHier.apply((("model", id(m), "hier"), tuple(range(len(hsegs)))), *[t for sg in hsegs for t in sg])
+        else:
+            k = _lib.kl_hier(hsegs, layer_ids=list(range(len(hsegs))), owner=("model", id(m), "hier"))
+        kl = k if kl is None else kl + k
     for layer in others:     # foreign modules with a kl_loss of their own
         kl = layer.kl_loss() if kl is None else kl + layer.kl_loss()
     return kl

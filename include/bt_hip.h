@@ -366,6 +366,33 @@ int bt_kl_normal_bwd_segs(int32_t n_segments, const float *const *mu, const floa
                           const float *const *prior_sigma, const int64_t *numel, const float *grad_kl, uint32_t flags,
                           float *const *dmu, float *const *drho, bt_stream_t stream);
 
+/* kl_loss() of the hierarchical layers (layers/variational_layers/hiearchial_variational_layers.py:331-381, :477-522): every weight
+ * has its own variational Inv-Gamma(a, b), a = exp(log_a), b = exp(log_b), over its prior variance, against the hyper-prior (a0, b0):
+ *   kl_out[0] = sum_seg SUM_i( 1/2 [ ln b - psi(a) - ln sq^2 + (a/b)(sq^2 + (mu - pm)^2) - 1 ]
+ *                              + (a - a0) psi(a) - lnGamma(a) + lnGamma(a0) + a0 (ln b - ln b0) + (b0 - b)(a/b) ),   sq = log1p(exp(rho))
+ * -- a SUM over the elements, not bt_kl_normal's mean. One launch over up to BT_KL_MAX_SEGMENTS tensors; segment arrays are HOST
+ * arrays, all seven tensors of a segment have numel[i] fp32 elements. A segment's fp64 sum is rounded to fp32; the segments of a
+ * layer (layer_of_segment as in bt_kl_normal) are added in fp32, then the layers in order. seg_out: NULL, or n_segments device
+ * floats that receive every segment's own fp32 sum. Deterministic; the workspace is left zeroed. Checked on the host before any
+ * launch: BT_ERR_BAD_ARG for a bad count, a null pointer, an empty segment or a workspace below BT_WORKSPACE_BYTES. */
+int bt_kl_hier(int32_t n_segments, const float *const *mu, const float *const *rho, const float *const *prior_mu,
+               const float *const *log_a, const float *const *log_b, const float *const *a0, const float *const *b0,
+               const int64_t *numel, const int32_t *layer_of_segment, float *kl_out, float *seg_out, void *workspace,
+               size_t workspace_bytes, bt_stream_t stream);
+/* Its gradient, element-wise, in ONE launch: d kl / d(mu, rho, log_a, log_b) * grad_kl[0] (grad_kl: device scalar). Each of the
+ * four output arrays may be NULL, and so may each of their entries: that gradient is not written. */
+int bt_kl_hier_bwd(int32_t n_segments, const float *const *mu, const float *const *rho, const float *const *prior_mu,
+                   const float *const *log_a, const float *const *log_b, const float *const *a0, const float *const *b0,
+                   const int64_t *numel, const float *grad_kl, float *const *dmu, float *const *drho, float *const *dlog_a,
+                   float *const *dlog_b, bt_stream_t stream);
+/* Host-side: the kernels' fp32 special functions (csrc/bt_special.h) evaluated on the CPU at n HOST floats x > 0, for tests on a
+ * machine without a device. */
+#define BT_SPECIAL_DIGAMMA 0       /* psi(x) */
+#define BT_SPECIAL_TRIGAMMA 1      /* psi'(x) */
+#define BT_SPECIAL_LGAMMA 2        /* ln Gamma(x) */
+#define BT_SPECIAL_X_TRIGAMMA_M1 3 /* x psi'(x) - 1, as the log_a gradient uses it (no cancellation at large x) */
+int bt_special_eval(int32_t kind, const float *x, int64_t n, float *out);
+
 /* Contraction arithmetic of the fused forwards (process-wide; read at every launch, so a captured graph keeps the kernels it was
  * captured with; default from env BT_CONTRACTION = f32 | bf16x3 | bf16x2 | bf16):
  *   0  automatic: wherever a launch is eligible, every fp32 operand is cut into three bf16 pieces (an EXACT split of the
