@@ -214,6 +214,32 @@ def workspace(key, device, scratch=0):
     return w
 
 
+def seg_chunks(segments, prepare, layer_ids=None):
+    """What the segmented entry points take, per chunk of KL_MAX_SEGMENTS segments. prepare(index, segment) -> the segment's validated
+    tensors in the C ABI's order (None: a null entry; the first one gives numel). Yields (index of the chunk's first segment, n, the
+    prepared rows -- hold them until the call is made --, one pointer array per position, the numel array, the layer array or None)."""
+    for c0 in range(0, len(segments), KL_MAX_SEGMENTS):
+        rows = [prepare(c0 + i, seg) for i, seg in enumerate(segments[c0:c0 + KL_MAX_SEGMENTS])]
+        n = len(rows)
+        arrs = [(_vp * n)(*col) for col in zip(*[[None if t is None else t.data_ptr() for t in r] for r in rows])]
+        numel = (C.c_int64 * n)(*[r[0].numel() for r in rows])
+        lay = None if layer_ids is None else (C.c_int32 * n)(*layer_ids[c0:c0 + n])
+        yield c0, n, rows, arrs, numel, lay
+
+
+def _kl_segment(_, seg):
+    ts = [dev_f32(t, "kl segment tensor") for t in seg]
+    if not all(t.numel() == ts[0].numel() for t in ts):
+        raise ValueError("kl segment tensors must have equal numel")
+    return ts
+
+
+def _kl_hier_segment(i, seg):
+    if len(seg) != 7:
+        raise ValueError("a hierarchical KL segment is (mu, rho, prior_mu, log_a, log_b, a0, b0)")
+    return _kl_segment(i, seg)
+
+
 def kl_normal(segments, layer_ids=None, rho_is_sigma=False, out=None, owner="kl", laplace=False):
     """segments: list of (mu, rho, prior_mu, prior_sigma) device tensors. Returns a 0-dim tensor:
     sum over layers of (sum over the layer's segments of the element mean).  laplace: kl_div's 'laplace' branch for
@@ -221,23 +247,7 @@ def kl_normal(segments, layer_ids=None, rho_is_sigma=False, out=None, owner="kl"
     L = lib()
     dev = segments[0][0].device
     total = None
-    for c0 in range(0, len(segments), KL_MAX_SEGMENTS):
-        chunk = segments[c0:c0 + KL_MAX_SEGMENTS]
-        n = len(chunk)
-        keep = []
-        arrs = [(_vp * n)() for _ in range(4)]
-        numel = (C.c_int64 * n)()
-        for i, seg in enumerate(chunk):
-            ts = [dev_f32(t, "kl segment tensor") for t in seg]
-            if not all(t.numel() == ts[0].numel() for t in ts):
-                raise ValueError("kl segment tensors must have equal numel")
-            keep.append(ts)
-            for a, t in zip(arrs, ts):
-                a[i] = t.data_ptr()
-            numel[i] = ts[0].numel()
-        lay = None
-        if layer_ids is not None:
-            lay = (C.c_int32 * n)(*layer_ids[c0:c0 + n])
+    for _, n, keep, arrs, numel, lay in seg_chunks(segments, _kl_segment, layer_ids):
         res = torch.empty((), dtype=torch.float32, device=dev) if (out is None or total is not None) else out
         with on(dev):
             check(L.bt_kl_normal(n, arrs[0], arrs[1], arrs[2], arrs[3], numel, lay, (KL_RHO_IS_SIGMA if rho_is_sigma else 0) | (KL_PRIOR_LAPLACE if laplace else 0),
@@ -254,25 +264,7 @@ def kl_hier(segs, layer_ids=None, owner="kl_hier", per_segment=False):
     dev = segs[0][0].device
     total = None
     seg_sums = torch.empty(len(segs), dtype=torch.float32, device=dev) if per_segment else None
-    for c0 in range(0, len(segs), KL_MAX_SEGMENTS):
-        chunk = segs[c0:c0 + KL_MAX_SEGMENTS]
-        n = len(chunk)
-        keep = []
-        arrs = [(_vp * n)() for _ in range(7)]
-        numel = (C.c_int64 * n)()
-        for i, seg in enumerate(chunk):
-            if len(seg) != 7:
-                raise ValueError("a hierarchical KL segment is (mu, rho, prior_mu, log_a, log_b, a0, b0)")
-            ts = [dev_f32(t, "kl segment tensor") for t in seg]
-            if not all(t.numel() == ts[0].numel() for t in ts):
-                raise ValueError("kl segment tensors must have equal numel")
-            keep.append(ts)
-            for a, t in zip(arrs, ts):
-                a[i] = t.data_ptr()
-            numel[i] = ts[0].numel()
-        lay = None
-        if layer_ids is not None:
-            lay = (C.c_int32 * n)(*layer_ids[c0:c0 + n])
+    for c0, n, keep, arrs, numel, lay in seg_chunks(segs, _kl_hier_segment, layer_ids):
         res = torch.empty((), dtype=torch.float32, device=dev)
         so = None if seg_sums is None else seg_sums.data_ptr() + 4 * c0
         with on(dev):

@@ -261,6 +261,25 @@ class KLHier(torch.autograd.Function):
         return tuple(grads)
 
 
+def _differentiable(tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def kl_normal(segs, layer_ids, owner, kind):
+    """The Gaussian (or 'laplace') KL of (mu, rho, prior_mu, prior_sigma) segments: differentiable (KLNormal) when gradients are on and a
+    tensor asks for one, else the plain launch."""
+    if _differentiable(t for sg in segs for t in sg):
+        return KLNormal.apply((owner, kind, tuple(layer_ids)), *[t for sg in segs for t in sg])
+    return _lib.kl_normal(segs, layer_ids=layer_ids, owner=owner, laplace=kind == "laplace")
+
+
+def kl_hier(segs, layer_ids, owner):
+    """The same choice for the hierarchical KL of (mu, rho, prior_mu, log_a, log_b, a0, b0) segments (KLHier): mu, rho, log_a, log_b count."""
+    if _differentiable(sg[i] for sg in segs for i in (0, 1, 3, 4)):
+        return KLHier.apply((owner, tuple(layer_ids)), *[t for sg in segs for t in sg])
+    return _lib.kl_hier(segs, layer_ids=layer_ids, owner=owner)
+
+
 class KLValue(torch.autograd.Function):
     """get_kl_loss of a training step whose layers differentiate their own KL terms (FusedForward, opts["kl"] + opts["kl_stub"]):
     the value from ONE bt_kl_normal launch over all segments; backward gives the upstream gradient to every layer's placeholder --

@@ -76,8 +76,8 @@ inline int raise_lds_limit(const void* kern, int bytes, const char* who) {
   return BT_OK;
 }
 
-// Launches kern with `lds` bytes of dynamic LDS after raising its limit to lds_limit; records `name` for bt_last_kernel_name
-// (null: not a fused forward, the name is left alone).
+// Launches kern with `lds` bytes of dynamic LDS after raising its limit to lds_limit (0: the kernel asks for none, nothing to raise);
+// records `name` for bt_last_kernel_name (null: not a fused forward, the name is left alone).
 template <typename... P, typename... A>
 int launch_kernel(void (*kern)(P...), const char* name, const char* who, dim3 grid, dim3 block, int lds, int lds_limit, hipStream_t stream,
                   const A&... args) {
@@ -88,7 +88,8 @@ int launch_kernel(void (*kern)(P...), const char* name, const char* who, dim3 gr
     note_launch(grid, block, lds, lds_limit, h);
     return BT_OK;
   }
-  if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kern), lds_limit, who)) return rc;
+  if (lds_limit)
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kern), lds_limit, who)) return rc;
   if (name) note_kernel(name);
   hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
   return check_launch(who);

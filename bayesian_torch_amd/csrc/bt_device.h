@@ -139,6 +139,25 @@ __device__ __forceinline__ float kl_term_laplace(float mu_q, float sigma_q) {
   return __fadd_rn(head, e_abs);
 }
 
+// (dKL/dmu, dKL/drho) of ONE element of kl_div's mean (base_variational_layer.py:70-72; 'laplace': :74-97), times gs = upstream / n.
+// The one op order of the KL gradient kernels (bt_kl.hip) and of the weight-gradient finishing pass (bt_bwd.hip): the same bits.
+__device__ __forceinline__ void kl_elem_grad(float m, float r, const float* pmu, const float* psig, long long i, int laplace, float gs, float& dm, float& dr) {
+  const float sq = softplus(r);
+  const float sg = __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __builtin_amdgcn_exp2f(__fmul_rn(-1.4426950408889634f, r))));
+  float gm, gq;
+  if (laplace) {  // d/dmu E|w| = erf(mu / (sq sqrt 2)); d/dsq = sqrt(2/pi) exp(-mu^2 / (2 sq^2)) - 1/sq
+    const float z = __fmul_rn(m, __builtin_amdgcn_rcpf(__fmul_rn(sq, 1.4142135623730951f)));
+    gm = erff(z);
+    gq = __fsub_rn(__fmul_rn(0.7978845608028654f, __builtin_amdgcn_exp2f(__fmul_rn(-1.4426950408889634f, __fmul_rn(z, z)))), __builtin_amdgcn_rcpf(sq));
+  } else {
+    const float ip = __builtin_amdgcn_rcpf(__fmul_rn(psig[i], psig[i]));
+    gm = __fmul_rn(__fsub_rn(m, pmu[i]), ip);
+    gq = __fsub_rn(__fmul_rn(sq, ip), __builtin_amdgcn_rcpf(sq));
+  }
+  dm = __fmul_rn(gm, gs);
+  dr = __fmul_rn(__fmul_rn(gq, sg), gs);
+}
+
 // ---------------------------------------------------------------------------- reductions
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

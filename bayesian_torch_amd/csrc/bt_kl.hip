@@ -3,22 +3,23 @@
 // variational_layers/linear_variational.py:146-158, models/dnn_to_bnn.py:157-165): there it is
 // ~12 full-tensor ATen passes per layer; here one pass, 16 B/element (mu, rho, prior_mu,
 // prior_sigma), HBM-bound, for up to 64 tensors (a whole model) per launch.
-#include "bt_api_internal.h"
+// Its gradient kernels live here too: one tensor per launch (bt_kl_normal_bwd) and a whole model's tensors in one (bt_kl_normal_bwd_segs).
+#include "bt_segments.h"
 
 namespace bt {
 
 struct KlSegs {
-  const float* mu[BT_KL_MAX_SEGMENTS];
-  const float* rho[BT_KL_MAX_SEGMENTS];
-  const float* pmu[BT_KL_MAX_SEGMENTS];
-  const float* psig[BT_KL_MAX_SEGMENTS];
-  long long n[BT_KL_MAX_SEGMENTS];
-  int first_block[BT_KL_MAX_SEGMENTS + 1];  // blocks [first_block[i], first_block[i+1]) work on segment i
-  unsigned long long new_layer;             // bit i: segment i starts a new layer (fp32 summation grouping)
-  int nseg;
+  const float* mu[kMaxSegs];
+  const float* rho[kMaxSegs];
+  const float* pmu[kMaxSegs];
+  const float* psig[kMaxSegs];
+  SegTable t;
   int rho_is_sigma;
   int laplace;  // 'laplace' branch of kl_div (prior tensors are ignored, as in the reference) instead of the Gaussian closed form
 };
+inline uint64_t digest_arg(uint64_t h, const KlSegs& a) {
+  return digest_arg(digest_arg(digest_segs(h, a.t, a.mu, a.rho, a.pmu, a.psig), a.rho_is_sigma), a.laplace);
+}
 
 constexpr int kKlThreads = 256;
 constexpr int kKlVecPerThread = 4;                                   // float4 loads in flight per tensor per thread
@@ -29,12 +30,9 @@ __global__ __launch_bounds__(kKlThreads) void kl_normal_kernel(KlSegs sg, float*
                                                               int total_blocks) {
   __shared__ double red[4];
   __shared__ int is_last;
-  // locate this block's segment (nseg <= 64: linear scan on scalars)
-  int seg = 0;
-  while (seg + 1 < sg.nseg && (int)blockIdx.x >= sg.first_block[seg + 1]) ++seg;
-  const int nb = sg.first_block[seg + 1] - sg.first_block[seg];
-  const int lb = blockIdx.x - sg.first_block[seg];
-  const long long n = sg.n[seg];
+  int seg, nb, lb;
+  seg_locate(sg.t, seg, nb, lb);
+  const long long n = sg.t.n[seg];
   const float* __restrict__ mu = sg.mu[seg];
   const float* __restrict__ rho = sg.rho[seg];
   const float* __restrict__ pmu = sg.pmu[seg];
@@ -79,38 +77,43 @@ __global__ __launch_bounds__(kKlThreads) void kl_normal_kernel(KlSegs sg, float*
   if (threadIdx.x == 0) is_last = publish_and_ticket_wt(slots, counter, blockIdx.x, bsum, (unsigned)total_blocks) ? 1 : 0;
   __syncthreads();
   if (!is_last) return;
-  // last arriver: fixed-ORDER finish, in parallel. A segment's block partials are summed by the 256 threads in a fixed tree (thread t
-  // adds the slots t, t + 256, ... in increasing order; then the wave butterflies and the four wave sums in index order): the same
-  // tree every time, so the result is deterministic -- and a whole model's ~2,700 slots no longer pass through ONE thread's serial
-  // chain of agent-scope loads (round 3: that chain was 429 us of a 3.95 ms ResNet18 training step, and of every get_kl_loss()).
-  // mean per segment in fp64 -> fp32, segments added in fp32 (the reference adds fp32 0-dim tensors: kl_weight + kl_bias, then += across layers).
-  __shared__ double seg_sum[BT_KL_MAX_SEGMENTS];
-  for (int s = 0; s < sg.nseg; ++s) {
-    double t = 0.0;
-    for (int b = sg.first_block[s] + (int)threadIdx.x; b < sg.first_block[s + 1]; b += kKlThreads) {
-      t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&slots[b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-    }
-    t = wave_sum(t);
-    __syncthreads();   // (red is free again)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) seg_sum[s] = (red[0] + red[1]) + (red[2] + red[3]);
+  // last arriver: the segments' means in fp64 -> fp32, grouped by layer
+  seg_finish(sg.t, slots, counter, red, kl_out, nullptr, [](double sum, long long cnt) { return (float)(sum / (double)cnt); });
+}
+
+// dKL/dmu, dKL/drho of the normal-prior KL (base_variational_layer.py:70-72), scaled by the upstream gradient g[0] / n
+__global__ __launch_bounds__(256) void kl_normal_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ rho, const float* __restrict__ pmu,
+                                                            const float* __restrict__ psig, const float* __restrict__ gup, long long n, int laplace,
+                                                            float* __restrict__ dmu, float* __restrict__ drho) {
+  const float gs = gup[0] / (float)n;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    kl_elem_grad(mu[i], rho[i], pmu, psig, i, laplace, gs, dmu[i], drho[i]);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float total = 0.0f, layer = 0.0f;
-    for (int s = 0; s < sg.nseg; ++s) {
-      const float mean = (float)(seg_sum[s] / (double)sg.n[s]);
-      if ((sg.new_layer >> s) & 1ull) {
-        if (s) total += layer;  // 0.0f + x is exact, so the first layer enters unrounded
-        layer = mean;
-      } else {
-        layer += mean;
-      }
-    }
-    kl_out[0] = total + layer;
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
+}
+
+// All tensors of a model in one launch (get_kl_loss under autograd): block b works on 1024 elements of segment seg(b).
+struct KlBwdSegs {
+  const float *mu[kMaxSegs], *rho[kMaxSegs], *pmu[kMaxSegs], *psig[kMaxSegs];
+  float *dmu[kMaxSegs], *drho[kMaxSegs];
+  SegTable t;
+  int laplace;
+};
+inline uint64_t digest_arg(uint64_t h, const KlBwdSegs& a) { return digest_arg(digest_segs(h, a.t, a.mu, a.rho, a.pmu, a.psig, a.dmu, a.drho), a.laplace); }
+static_assert(sizeof(KlSegs) <= kMaxSegArgBytes && sizeof(KlBwdSegs) <= kMaxSegArgBytes, "argument block larger than kl_hier_bwd_kernel's");
+constexpr int kKlBwdElemsPerBlock = 1024;
+
+__global__ __launch_bounds__(256) void kl_normal_bwd_segs_kernel(const KlBwdSegs a, const float* __restrict__ gup) {
+  int seg, nb, lb;
+  seg_locate(a.t, seg, nb, lb);   // uniform
+  const long long n = a.t.n[seg];
+  const float gs = gup[0] / (float)n;
+  const float *mu = a.mu[seg], *rho = a.rho[seg], *pmu = a.pmu[seg], *psig = a.psig[seg];
+  float *dmu = a.dmu[seg], *drho = a.drho[seg];
+  const long long base = (long long)lb * kKlBwdElemsPerBlock;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long long i = base + threadIdx.x + 256 * k;
+    if (i < n) kl_elem_grad(mu[i], rho[i], pmu, psig, i, a.laplace, gs, dmu[i], drho[i]);
   }
 }
 
@@ -123,33 +126,50 @@ extern "C" int bt_kl_normal(int32_t n_segments, const float* const* mu, const fl
   if (n_segments <= 0 || n_segments > BT_KL_MAX_SEGMENTS) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal: n_segments must be in [1, 64]");
   if (!mu || !rho || !prior_mu || !prior_sigma || !numel || !kl_out) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal: null argument");
   if (!workspace || workspace_bytes < BT_WORKSPACE_BYTES) return set_error(BT_ERR_WORKSPACE, "bt_kl_normal: workspace smaller than BT_WORKSPACE_BYTES");
-  KlSegs sg;
-  int blocks = 0;
+  KlSegs sg = {};
   for (int i = 0; i < n_segments; ++i) {
     if (numel[i] <= 0 || !mu[i] || !rho[i] || !prior_mu[i] || !prior_sigma[i]) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal: empty or null segment");
-    sg.mu[i] = mu[i];
-    sg.rho[i] = rho[i];
-    sg.pmu[i] = prior_mu[i];
-    sg.psig[i] = prior_sigma[i];
-    sg.n[i] = numel[i];
-    long long nb = (numel[i] + kKlElemsPerBlock - 1) / kKlElemsPerBlock;
-    if (nb > kKlMaxBlocksPerSeg) nb = kKlMaxBlocksPerSeg;
-    sg.first_block[i] = blocks;
-    blocks += (int)nb;
+    sg.mu[i] = mu[i], sg.rho[i] = rho[i], sg.pmu[i] = prior_mu[i], sg.psig[i] = prior_sigma[i], sg.t.n[i] = numel[i];
   }
-  sg.first_block[n_segments] = blocks;
-  sg.nseg = n_segments;
   sg.rho_is_sigma = (flags & BT_KL_RHO_IS_SIGMA) ? 1 : 0;
   sg.laplace = (flags & BT_KL_PRIOR_LAPLACE) ? 1 : 0;
-  sg.new_layer = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    if (layer_of_segment && i && layer_of_segment[i] < layer_of_segment[i - 1]) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal: layer_of_segment must be non-decreasing");
-    if (i == 0 || !layer_of_segment || layer_of_segment[i] != layer_of_segment[i - 1]) sg.new_layer |= 1ull << i;
+  if (int rc = seg_layers(sg.t, n_segments, layer_of_segment, "bt_kl_normal")) return rc;
+  const int blocks = seg_partition(sg.t, n_segments, numel, kKlElemsPerBlock, kKlMaxBlocksPerSeg, kMaxSlots, "bt_kl_normal");   // (a slot per block)
+  if (blocks < 0) return blocks;
+  return launch_kernel(kl_normal_kernel, nullptr, "bt_kl_normal", dim3(blocks), dim3(kKlThreads), 0, 0, (hipStream_t)stream, sg, kl_out, ws_slots(workspace),
+                       ws_counter(workspace), blocks);
+}
+
+extern "C" int bt_kl_normal_bwd(const float* mu, const float* rho, const float* prior_mu, const float* prior_sigma, const float* grad_kl, int64_t numel,
+                                uint32_t flags, float* dmu, float* drho, bt_stream_t stream) {
+  using namespace bt;
+  if (!mu || !rho || !grad_kl || !dmu || !drho || numel <= 0) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal_bwd: null argument");
+  const int lap = (flags & BT_KL_PRIOR_LAPLACE) ? 1 : 0;
+  if (!lap && (!prior_mu || !prior_sigma)) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal_bwd: priors are required for the normal prior");
+  const long long nb = (numel + 255) / 256;
+  hipLaunchKernelGGL(kl_normal_bwd_kernel, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, (hipStream_t)stream, mu, rho, prior_mu, prior_sigma, grad_kl,
+                     (long long)numel, lap, dmu, drho);
+  return check_launch("bt_kl_normal_bwd");
+}
+
+extern "C" int bt_kl_normal_bwd_segs(int32_t n_segments, const float* const* mu, const float* const* rho, const float* const* prior_mu,
+                                     const float* const* prior_sigma, const int64_t* numel, const float* grad_kl, uint32_t flags,
+                                     float* const* dmu, float* const* drho, bt_stream_t stream) {
+  using namespace bt;
+  if (n_segments <= 0 || n_segments > BT_KL_MAX_SEGMENTS || !mu || !rho || !numel || !grad_kl || !dmu || !drho)
+    return set_error(BT_ERR_BAD_ARG, "bt_kl_normal_bwd_segs: bad argument");
+  const int lap = (flags & BT_KL_PRIOR_LAPLACE) ? 1 : 0;
+  if (!lap && (!prior_mu || !prior_sigma)) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal_bwd_segs: priors are required for the normal prior");
+  KlBwdSegs a = {};
+  int i = 0;   // (stops at the first bad segment: the partition's refusal of the segments in front of it comes first)
+  for (; i < n_segments; ++i) {
+    if (!mu[i] || !rho[i] || !dmu[i] || !drho[i] || numel[i] <= 0 || (!lap && (!prior_mu[i] || !prior_sigma[i]))) break;
+    a.mu[i] = mu[i], a.rho[i] = rho[i], a.pmu[i] = lap ? nullptr : prior_mu[i], a.psig[i] = lap ? nullptr : prior_sigma[i];
+    a.dmu[i] = dmu[i], a.drho[i] = drho[i], a.t.n[i] = numel[i];
   }
-  if (blocks > kMaxSlots) {  // only possible with many huge segments: cap per-segment blocks harder
-    return set_error(BT_ERR_UNSUPPORTED, "bt_kl_normal: too many blocks for the workspace; split the call");
-  }
-  hipLaunchKernelGGL(kl_normal_kernel, dim3(blocks), dim3(kKlThreads), 0, (hipStream_t)stream, sg, kl_out, ws_slots(workspace),
-                     ws_counter(workspace), blocks);
-  return check_launch("bt_kl_normal");
+  const int blocks = seg_partition(a.t, i, numel, kKlBwdElemsPerBlock, 0, 0, "bt_kl_normal_bwd_segs");
+  if (blocks < 0) return blocks;
+  if (i < n_segments) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal_bwd_segs: null tensor or empty segment");
+  a.laplace = lap;
+  return launch_kernel(kl_normal_bwd_segs_kernel, nullptr, "bt_kl_normal_bwd_segs", dim3((unsigned)blocks), dim3(256), 0, 0, (hipStream_t)stream, a, grad_kl);
 }

@@ -7,7 +7,7 @@
 // The reference makes ~40 full-tensor ATen passes of it per layer and call; here one sweep, 28 B/element (seven tensors), for up to
 // 64 tensors per launch, and one element-wise launch for the four gradients. Reductions as in bt_kl.hip: fp64 block sums, a ticket,
 // a fixed-order finish.
-#include "bt_api_internal.h"
+#include "bt_segments.h"
 #include "bt_special.h"
 
 namespace bt {
@@ -20,11 +20,9 @@ struct KlHierSegs {
   const float* lb[BT_KL_MAX_SEGMENTS];
   const float* a0[BT_KL_MAX_SEGMENTS];
   const float* b0[BT_KL_MAX_SEGMENTS];
-  long long n[BT_KL_MAX_SEGMENTS];
-  int first_block[BT_KL_MAX_SEGMENTS + 1];  // blocks [first_block[i], first_block[i+1]) work on segment i
-  unsigned long long new_layer;             // bit i: segment i starts a new layer (fp32 summation grouping)
-  int nseg;
+  SegTable t;
 };
+inline uint64_t digest_arg(uint64_t h, const KlHierSegs& a) { return digest_segs(h, a.t, a.mu, a.rho, a.pmu, a.la, a.lb, a.a0, a.b0); }
 
 constexpr int kHierThreads = 256;
 constexpr int kHierElemsPerPass = kHierThreads * 4;      // one float4 per tensor and thread in flight: the sweep is bound by its arithmetic
@@ -52,11 +50,9 @@ __global__ __launch_bounds__(kHierThreads) void kl_hier_kernel(KlHierSegs sg, fl
                                                               int total_blocks) {
   __shared__ double red[4];
   __shared__ int is_last;
-  int seg = 0;
-  while (seg + 1 < sg.nseg && (int)blockIdx.x >= sg.first_block[seg + 1]) ++seg;
-  const int nb = sg.first_block[seg + 1] - sg.first_block[seg];
-  const int lb_ = blockIdx.x - sg.first_block[seg];
-  const long long n = sg.n[seg];
+  int seg, nb, lb_;
+  seg_locate(sg.t, seg, nb, lb_);
+  const long long n = sg.t.n[seg];
   const float* __restrict__ mu = sg.mu[seg];
   const float* __restrict__ rho = sg.rho[seg];
   const float* __restrict__ pmu = sg.pmu[seg];
@@ -86,37 +82,8 @@ __global__ __launch_bounds__(kHierThreads) void kl_hier_kernel(KlHierSegs sg, fl
   if (threadIdx.x == 0) is_last = publish_and_ticket_wt(slots, counter, blockIdx.x, bsum, (unsigned)total_blocks) ? 1 : 0;
   __syncthreads();
   if (!is_last) return;
-  // last arriver: the fixed-order parallel finish of kl_normal_kernel (bt_kl.hip). A segment's fp64 sum -> fp32; segments of one
-  // layer added in fp32, layers added in fp32 in order.
-  __shared__ double seg_sum[BT_KL_MAX_SEGMENTS];
-  for (int s = 0; s < sg.nseg; ++s) {
-    double t = 0.0;
-    for (int b = sg.first_block[s] + (int)threadIdx.x; b < sg.first_block[s + 1]; b += kHierThreads) {
-      t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&slots[b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-    }
-    t = wave_sum(t);
-    __syncthreads();   // (red is free again)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) seg_sum[s] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float total = 0.0f, layer = 0.0f;
-    for (int s = 0; s < sg.nseg; ++s) {
-      const float v = (float)seg_sum[s];
-      if (seg_out) seg_out[s] = v;
-      if ((sg.new_layer >> s) & 1ull) {
-        if (s) total += layer;  // 0.0f + x is exact, so the first layer enters unrounded
-        layer = v;
-      } else {
-        layer += v;
-      }
-    }
-    kl_out[0] = total + layer;
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
-  }
+  // last arriver: a segment's fp64 sum -> fp32, grouped by layer
+  seg_finish(sg.t, slots, counter, red, kl_out, seg_out, [](double sum, long long) { return (float)sum; });
 }
 
 // d kl / d(mu, rho, log_a, log_b) of one element, times the upstream gradient g. With r = a/b, s = sigma^2 + (mu - m)^2, c = a0 + 1/2:
@@ -127,19 +94,22 @@ struct KlHierBwdSegs {
   const float *mu[BT_KL_MAX_SEGMENTS], *rho[BT_KL_MAX_SEGMENTS], *pmu[BT_KL_MAX_SEGMENTS], *la[BT_KL_MAX_SEGMENTS], *lb[BT_KL_MAX_SEGMENTS];
   const float *a0[BT_KL_MAX_SEGMENTS], *b0[BT_KL_MAX_SEGMENTS];
   float *dmu[BT_KL_MAX_SEGMENTS], *drho[BT_KL_MAX_SEGMENTS], *dla[BT_KL_MAX_SEGMENTS], *dlb[BT_KL_MAX_SEGMENTS];      // each may be null
-  long long n[BT_KL_MAX_SEGMENTS];
-  int boff[BT_KL_MAX_SEGMENTS + 1];  // first block of every segment
-  int nseg;
+  SegTable t;
 };
+inline uint64_t digest_arg(uint64_t h, const KlHierBwdSegs& a) {
+  return digest_segs(h, a.t, a.mu, a.rho, a.pmu, a.la, a.lb, a.a0, a.b0, a.dmu, a.drho, a.dla, a.dlb);
+}
+static_assert(sizeof(KlHierSegs) <= kMaxSegArgBytes && sizeof(KlHierBwdSegs) == kMaxSegArgBytes, "kl_hier_bwd_kernel's block is the largest there is");
+constexpr int kHierBwdElemsPerBlock = 1024;
 
 __global__ __launch_bounds__(256) void kl_hier_bwd_kernel(const KlHierBwdSegs a, const float* __restrict__ gup) {
-  int seg = 0;
-  while (seg + 1 < a.nseg && (int)blockIdx.x >= a.boff[seg + 1]) ++seg;   // uniform
-  const long long n = a.n[seg];
+  int seg, nb, lb_;
+  seg_locate(a.t, seg, nb, lb_);   // uniform
+  const long long n = a.t.n[seg];
   const float g = gup[0];
   const float *mu = a.mu[seg], *rho = a.rho[seg], *pmu = a.pmu[seg], *la = a.la[seg], *lb = a.lb[seg], *a0 = a.a0[seg], *b0 = a.b0[seg];
   float *dmu = a.dmu[seg], *drho = a.drho[seg], *dla = a.dla[seg], *dlb = a.dlb[seg];
-  const long long base = (long long)((int)blockIdx.x - a.boff[seg]) * 1024;
+  const long long base = (long long)lb_ * kHierBwdElemsPerBlock;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const long long i = base + threadIdx.x + 256 * k;
@@ -184,28 +154,18 @@ extern "C" int bt_kl_hier(int32_t n_segments, const float* const* mu, const floa
   if (n_segments <= 0 || n_segments > BT_KL_MAX_SEGMENTS) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier: n_segments must be in [1, 64]");
   if (!mu || !rho || !prior_mu || !log_a || !log_b || !a0 || !b0 || !numel || !kl_out) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier: null argument");
   if (!workspace || workspace_bytes < BT_WORKSPACE_BYTES) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier: workspace smaller than BT_WORKSPACE_BYTES");
-  KlHierSegs sg;
-  int blocks = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    if (hier_null_segment(i, mu, rho, prior_mu, log_a, log_b, a0, b0, numel)) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier: empty or null segment");
+  KlHierSegs sg = {};
+  int i = 0;   // (stops at the first bad segment: the partition's refusal of the segments in front of it comes first)
+  for (; i < n_segments && !hier_null_segment(i, mu, rho, prior_mu, log_a, log_b, a0, b0, numel); ++i) {
     sg.mu[i] = mu[i], sg.rho[i] = rho[i], sg.pmu[i] = prior_mu[i], sg.la[i] = log_a[i], sg.lb[i] = log_b[i], sg.a0[i] = a0[i], sg.b0[i] = b0[i];
-    sg.n[i] = numel[i];
-    long long nb = (numel[i] + kHierElemsPerBlock - 1) / kHierElemsPerBlock;
-    if (nb > kHierMaxBlocksPerSeg) nb = kHierMaxBlocksPerSeg;
-    sg.first_block[i] = blocks;
-    blocks += (int)nb;
-    if (blocks > kMaxSlots) return set_error(BT_ERR_UNSUPPORTED, "bt_kl_hier: too many blocks for the workspace; split the call");
+    sg.t.n[i] = numel[i];
   }
-  sg.first_block[n_segments] = blocks;
-  sg.nseg = n_segments;
-  sg.new_layer = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    if (layer_of_segment && i && layer_of_segment[i] < layer_of_segment[i - 1]) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier: layer_of_segment must be non-decreasing");
-    if (i == 0 || !layer_of_segment || layer_of_segment[i] != layer_of_segment[i - 1]) sg.new_layer |= 1ull << i;
-  }
-  hipLaunchKernelGGL(kl_hier_kernel, dim3(blocks), dim3(kHierThreads), 0, (hipStream_t)stream, sg, kl_out, seg_out, ws_slots(workspace),
-                     ws_counter(workspace), blocks);
-  return check_launch("bt_kl_hier");
+  const int blocks = seg_partition(sg.t, i, numel, kHierElemsPerBlock, kHierMaxBlocksPerSeg, kMaxSlots, "bt_kl_hier");   // (a slot per block)
+  if (blocks < 0) return blocks;
+  if (i < n_segments) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier: empty or null segment");
+  if (int rc = seg_layers(sg.t, n_segments, layer_of_segment, "bt_kl_hier")) return rc;
+  return launch_kernel(kl_hier_kernel, nullptr, "bt_kl_hier", dim3(blocks), dim3(kHierThreads), 0, 0, (hipStream_t)stream, sg, kl_out, seg_out, ws_slots(workspace),
+                       ws_counter(workspace), blocks);
 }
 
 extern "C" int bt_kl_hier_bwd(int32_t n_segments, const float* const* mu, const float* const* rho, const float* const* prior_mu,
@@ -217,21 +177,17 @@ extern "C" int bt_kl_hier_bwd(int32_t n_segments, const float* const* mu, const 
   if (!mu || !rho || !prior_mu || !log_a || !log_b || !a0 || !b0 || !numel || !grad_kl) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier_bwd: null argument");
   if (!dmu && !drho && !dlog_a && !dlog_b) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier_bwd: no gradient was asked for");
   KlHierBwdSegs a = {};
-  long long blocks = 0;
-  for (int i = 0; i < n_segments; ++i) {
-    if (hier_null_segment(i, mu, rho, prior_mu, log_a, log_b, a0, b0, numel)) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier_bwd: empty or null segment");
+  int i = 0;   // (as in bt_kl_hier)
+  for (; i < n_segments && !hier_null_segment(i, mu, rho, prior_mu, log_a, log_b, a0, b0, numel); ++i) {
     a.mu[i] = mu[i], a.rho[i] = rho[i], a.pmu[i] = prior_mu[i], a.la[i] = log_a[i], a.lb[i] = log_b[i], a.a0[i] = a0[i], a.b0[i] = b0[i];
     a.dmu[i] = dmu ? dmu[i] : nullptr, a.drho[i] = drho ? drho[i] : nullptr;
     a.dla[i] = dlog_a ? dlog_a[i] : nullptr, a.dlb[i] = dlog_b ? dlog_b[i] : nullptr;
-    a.n[i] = numel[i];
-    a.boff[i] = (int)blocks;
-    blocks += (numel[i] + 1023) / 1024;
-    if (blocks > 0x7FFFFFFFll) return set_error(BT_ERR_UNSUPPORTED, "bt_kl_hier_bwd: too many elements for one launch");
+    a.t.n[i] = numel[i];
   }
-  a.boff[n_segments] = (int)blocks;
-  a.nseg = n_segments;
-  hipLaunchKernelGGL(kl_hier_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, grad_kl);
-  return check_launch("bt_kl_hier_bwd");
+  const int blocks = seg_partition(a.t, i, numel, kHierBwdElemsPerBlock, 0, 0, "bt_kl_hier_bwd");
+  if (blocks < 0) return blocks;
+  if (i < n_segments) return set_error(BT_ERR_BAD_ARG, "bt_kl_hier_bwd: empty or null segment");
+  return launch_kernel(kl_hier_bwd_kernel, nullptr, "bt_kl_hier_bwd", dim3((unsigned)blocks), dim3(256), 0, 0, (hipStream_t)stream, a, grad_kl);
 }
 
 // Host-only: the special functions of bt_special.h evaluated on the CPU (the same source the kernels compile), so that they can be

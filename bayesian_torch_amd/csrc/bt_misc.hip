@@ -18,10 +18,15 @@ void note_kernel(const char* name) {
 static std::atomic<bool> g_plan_only{false};
 bool plan_only() { return g_plan_only.load(std::memory_order_relaxed); }
 
+constexpr uint64_t kFnvBasis = 14695981039346656037ull;
 static thread_local int64_t g_launch_rec[9] = {};   // grid x y z, block x y z, lds, lds_limit, FNV-1a of the kernel arguments
+static thread_local int64_t g_launch_count = 0;     // plan-only launches since bt_debug_last_launch_record was last asked ...
+static thread_local uint64_t g_launch_chain = kFnvBasis;   // ... and an FNV-1a chain over their records (a call may launch twice)
 void note_launch(dim3 grid, dim3 block, int lds, int lds_limit, uint64_t args_digest) {
   const int64_t v[9] = {grid.x, grid.y, grid.z, block.x, block.y, block.z, lds, lds_limit, (int64_t)args_digest};
   memcpy(g_launch_rec, v, sizeof(v));
+  ++g_launch_count;
+  g_launch_chain = fnv1a(g_launch_chain, v, sizeof(v));
 }
 
 int set_error(int code, const char* msg) {
@@ -298,9 +303,11 @@ extern "C" int bt_debug_poison_lds(void* scratch_word, bt_stream_t stream) {
 // runtime, so the host dispatch -- eligibility, tile plan, instantiation choice -- runs on a machine without a GPU
 // (tools/record_split_plans.py, tests/test_split_plan_parity.py). Off by default.
 extern "C" void bt_debug_plan_only(int on) { bt::g_plan_only.store(on != 0, std::memory_order_relaxed); }
-// The launch the last plan-only launch_kernel call of this thread would have made (note_launch's nine values).
+// The launch the last plan-only launch_kernel call of this thread would have made (note_launch's nine values); [9], [10]: how many
+// such launches there were since this function was last called, and the FNV-1a chain over their records.
 extern "C" int bt_debug_last_launch_record(int64_t* out, int n) {
   if (!out || n <= 0) return bt::set_error(BT_ERR_BAD_ARG, "bt_debug_last_launch_record: bad argument");
-  for (int i = 0; i < n; ++i) out[i] = i < 9 ? bt::g_launch_rec[i] : 0;
+  for (int i = 0; i < n; ++i) out[i] = i < 9 ? bt::g_launch_rec[i] : i == 9 ? bt::g_launch_count : i == 10 ? (int64_t)bt::g_launch_chain : 0;
+  bt::g_launch_count = 0, bt::g_launch_chain = bt::kFnvBasis;
   return BT_OK;
 }

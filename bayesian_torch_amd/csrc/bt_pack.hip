@@ -13,45 +13,48 @@
 // bt_pack_sync_kl: launch 1 also reads the priors of the layers that ask for it and produces their KL terms (the fused forwards'
 // closed form and per-element order; one double partial per block, summed in block order by the last block: deterministic).
 // The forwards of those layers then run without a KL sweep of their own: 8 B/weight read here instead of 16 B/weight there.
-#include "bt_api_internal.h"
+#include "bt_segments.h"
 
 namespace bt {
 
+// pack_dirty_kernel's argument block: what it packs from and to (t.n: elements of the natural tensors).
 struct PackSegs {
-  const float* mu[BT_PACK_MAX_SEGMENTS];
-  const float* rho[BT_PACK_MAX_SEGMENTS];
-  const float* src_mu[BT_PACK_MAX_SEGMENTS];
-  const float* src_rho[BT_PACK_MAX_SEGMENTS];
-  float* mu_p[BT_PACK_MAX_SEGMENTS];
-  float* sg_p[BT_PACK_MAX_SEGMENTS];
-  unsigned long long* state[BT_PACK_MAX_SEGMENTS];
-  long long n[BT_PACK_MAX_SEGMENTS];        // elements of the natural tensors
-  long long C[BT_PACK_MAX_SEGMENTS], T[BT_PACK_MAX_SEGMENTS], np[BT_PACK_MAX_SEGMENTS];   // pack geometry: channels, taps, packed elements
-  int first_block[BT_PACK_MAX_SEGMENTS + 1];
+  const float* src_mu[kMaxSegs];
+  const float* src_rho[kMaxSegs];
+  float* mu_p[kMaxSegs];
+  float* sg_p[kMaxSegs];
+  unsigned long long* state[kMaxSegs];
+  long long C[kMaxSegs], T[kMaxSegs], np[kMaxSegs];   // pack geometry: channels, taps, packed elements
+  SegTable t;
   unsigned long long force;                 // bit i: rebuild segment i whatever its fingerprint says
-  int nseg;
 };
+inline uint64_t digest_arg(uint64_t h, const PackSegs& a) {
+  return digest_arg(digest_segs(h, a.t, a.src_mu, a.src_rho, a.mu_p, a.sg_p, a.state, a.C, a.T, a.np), a.force);
+}
 
-// The fingerprint launch's own argument block (what it reads; the pack geometry stays with pack_dirty_kernel's PackSegs).
+// The fingerprint launch's own argument block (what it reads).
 struct FpSegs {
-  const float* mu[BT_PACK_MAX_SEGMENTS];
-  const float* rho[BT_PACK_MAX_SEGMENTS];
-  unsigned long long* state[BT_PACK_MAX_SEGMENTS];
-  long long n[BT_PACK_MAX_SEGMENTS];
+  const float* mu[kMaxSegs];
+  const float* rho[kMaxSegs];
+  unsigned long long* state[kMaxSegs];
   // KL (bt_pack_sync_kl): kl_out[i] == nullptr -> segment i produces none
-  const float* pmu[BT_PACK_MAX_SEGMENTS];
-  const float* psig[BT_PACK_MAX_SEGMENTS];
-  const float* mu_b[BT_PACK_MAX_SEGMENTS];
-  const float* rho_b[BT_PACK_MAX_SEGMENTS];
-  const float* pmu_b[BT_PACK_MAX_SEGMENTS];
-  const float* psig_b[BT_PACK_MAX_SEGMENTS];
-  float* kl_out[BT_PACK_MAX_SEGMENTS];
-  int n_bias[BT_PACK_MAX_SEGMENTS];
-  int first_block[BT_PACK_MAX_SEGMENTS + 1];
+  const float* pmu[kMaxSegs];
+  const float* psig[kMaxSegs];
+  const float* mu_b[kMaxSegs];
+  const float* rho_b[kMaxSegs];
+  const float* pmu_b[kMaxSegs];
+  const float* psig_b[kMaxSegs];
+  float* kl_out[kMaxSegs];
+  int n_bias[kMaxSegs];
+  SegTable t;
   unsigned long long force;
-  int nseg;
   int any_kl;
 };
+inline uint64_t digest_arg(uint64_t h, const FpSegs& a) {
+  h = digest_segs(h, a.t, a.mu, a.rho, a.state, a.pmu, a.psig, a.mu_b, a.rho_b, a.pmu_b, a.psig_b, a.kl_out, a.n_bias);
+  return digest_arg(digest_arg(h, a.force), a.any_kl);
+}
+static_assert(sizeof(PackSegs) <= kMaxSegArgBytes && sizeof(FpSegs) <= kMaxSegArgBytes, "argument block larger than kl_hier_bwd_kernel's");
 
 constexpr int kFpThreads = 256;
 constexpr int kFpElemsPerBlock = kFpThreads * 4 * 4;
@@ -66,7 +69,7 @@ __device__ __forceinline__ unsigned long long fp_mix(unsigned long long i, float
 
 template <bool KL>
 __device__ __forceinline__ void fp_sweep(const FpSegs& sg, int seg, int nb, int lb, unsigned long long& acc, double& kacc) {
-  const long long n = sg.n[seg];
+  const long long n = sg.t.n[seg];
   const float* __restrict__ mu = sg.mu[seg];
   const float* __restrict__ rho = sg.rho[seg];
   const float* __restrict__ pm = sg.pmu[seg];
@@ -105,9 +108,8 @@ __device__ __forceinline__ void fp_sweep(const FpSegs& sg, int seg, int nb, int 
 __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg, unsigned* counter, double* slots, int total_blocks) {
   __shared__ int is_last;
   __shared__ double kred[kFpThreads / 64];
-  int seg = 0;
-  while (seg + 1 < sg.nseg && (int)blockIdx.x >= sg.first_block[seg + 1]) ++seg;
-  const int nb = sg.first_block[seg + 1] - sg.first_block[seg], lb = blockIdx.x - sg.first_block[seg];
+  int seg, nb, lb;
+  seg_locate(sg.t, seg, nb, lb);
   const bool kl = sg.kl_out[seg] != nullptr;
   unsigned long long acc = 0ull;
   double kacc = 0.0;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg,
   }
   __syncthreads();
   if (!is_last) return;
-  if ((int)threadIdx.x < sg.nseg) {
+  if ((int)threadIdx.x < sg.t.nseg) {
     unsigned long long* const st = sg.state[threadIdx.x];
     const unsigned long long fp = __hip_atomic_load(&st[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long old = __hip_atomic_load(&st[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -147,10 +149,10 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg,
   if (!sg.any_kl) return;
   // KL finish: one wave per segment, the block partials in block order (fixed lane split + fixed butterfly: deterministic)
   const int lane = threadIdx.x & 63;
-  for (int s = threadIdx.x >> 6; s < sg.nseg; s += kFpThreads / 64) {
+  for (int s = threadIdx.x >> 6; s < sg.t.nseg; s += kFpThreads / 64) {
     if (sg.kl_out[s] == nullptr) continue;
     double t = 0.0;
-    for (int b = sg.first_block[s] + lane; b < sg.first_block[s + 1]; b += 64) {
+    for (int b = sg.t.first_block[s] + lane; b < sg.t.first_block[s + 1]; b += 64) {
       t += __hip_atomic_load(&slots[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&slots[b], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // leave the workspace zeroed
     }
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg,
       for (int c = lane; c < sg.n_bias[s]; c += 64) bt_ += (double)kl_term(mb[c], softplus(rb[c]), pb[c], qb[c]);
     bt_ = wave_sum(bt_);
     if (lane == 0) {
-      float v = (float)(t / (double)sg.n[s]);
+      float v = (float)(t / (double)sg.t.n[s]);
       if (mb) v += (float)(bt_ / (double)sg.n_bias[s]);
       sg.kl_out[s][0] = v;
     }
@@ -175,10 +177,9 @@ __global__ __launch_bounds__(kFpThreads) void pack_fingerprint_kernel(FpSegs sg,
 constexpr int kPackCh = 64;
 __global__ __launch_bounds__(256) void pack_dirty_kernel(PackSegs sg) {
   extern __shared__ float2 tile[];   // [T][64 + 1] (mu, sigma)
-  int seg = 0;
-  while (seg + 1 < sg.nseg && (int)blockIdx.x >= sg.first_block[seg + 1]) ++seg;
+  int seg, nb, lb;
+  seg_locate(sg.t, seg, nb, lb);
   if (__hip_atomic_load(&sg.state[seg][2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0ull) return;
-  const int nb = sg.first_block[seg + 1] - sg.first_block[seg], lb = blockIdx.x - sg.first_block[seg];
   const long long C = sg.C[seg], T = sg.T[seg], C4 = (C + 3) & ~3ll;
   const long long Co = sg.np[seg] / (T * C4);
   const long long cchunks = (C4 + kPackCh - 1) / kPackCh, items = Co * cchunks;
@@ -297,9 +298,7 @@ extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, cons
   if (!segs) return set_error(BT_ERR_BAD_ARG, "bt_pack_sync: null argument");
   if (!workspace || workspace_bytes < BT_WORKSPACE_BYTES) return set_error(BT_ERR_WORKSPACE, "bt_pack_sync: workspace smaller than BT_WORKSPACE_BYTES");
   FpSegs fs = {};
-  PackSegs fp, pk;
-  int fblocks = 0, pblocks = 0;
-  fp.force = 0ull;
+  PackSegs pk = {};
   for (int i = 0; i < n_segments; ++i) {
     const bt_pack_kl* k = kls ? &kls[i] : nullptr;
     if (!k || !k->kl_out) continue;
@@ -313,45 +312,40 @@ extern "C" int bt_pack_sync_kl(int32_t n_segments, const bt_pack_seg* segs, cons
     fs.n_bias[i] = b ? (int)k->n_bias : 0;
     fs.any_kl = 1;
   }
+  int64_t elems[kMaxSegs], items[kMaxSegs];   // a segment's work: elements to fingerprint, (row, 64-channel chunk) items to pack
+  long long max_taps = 1;
   for (int i = 0; i < n_segments; ++i) {
     const bt_pack_seg& s = segs[i];
     if (!s.mu_w || !s.rho_w || !s.mu_packed || !s.sigma_packed || !s.state || s.Co <= 0 || s.Ci <= 0 || s.taps <= 0)
       return set_error(BT_ERR_BAD_ARG, "bt_pack_sync: null pointer or non-positive dimension in a segment");
     if ((s.src_mu == nullptr) != (s.src_rho == nullptr)) return set_error(BT_ERR_BAD_ARG, "bt_pack_sync: src_mu and src_rho must both be given or both be NULL");
-    fp.mu[i] = s.mu_w, fp.rho[i] = s.rho_w;
-    fp.src_mu[i] = s.src_mu ? s.src_mu : s.mu_w, fp.src_rho[i] = s.src_rho ? s.src_rho : s.rho_w;
-    fp.mu_p[i] = s.mu_packed, fp.sg_p[i] = s.sigma_packed;
-    fp.state[i] = reinterpret_cast<unsigned long long*>(s.state);
-    fp.n[i] = s.Co * s.Ci * s.taps;
-    fp.C[i] = s.Ci, fp.T[i] = s.taps, fp.np[i] = s.Co * s.taps * ((s.Ci + 3) & ~3ll);
-    if (s.force) fp.force |= 1ull << i;
+    const long long C4 = (s.Ci + 3) & ~3ll;
+    fs.mu[i] = s.mu_w, fs.rho[i] = s.rho_w;
+    pk.src_mu[i] = s.src_mu ? s.src_mu : s.mu_w, pk.src_rho[i] = s.src_rho ? s.src_rho : s.rho_w;
+    pk.mu_p[i] = s.mu_packed, pk.sg_p[i] = s.sigma_packed;
+    fs.state[i] = pk.state[i] = reinterpret_cast<unsigned long long*>(s.state);
+    fs.t.n[i] = pk.t.n[i] = elems[i] = s.Co * s.Ci * s.taps;
+    pk.C[i] = s.Ci, pk.T[i] = s.taps, pk.np[i] = s.Co * s.taps * C4;
+    items[i] = s.Co * ((C4 + kPackCh - 1) / kPackCh);
+    if (s.force) pk.force |= 1ull << i;
+    if (s.taps > max_taps) max_taps = s.taps;
   }
-  pk = fp;
-  long long max_taps = 1;
-  for (int i = 0; i < n_segments; ++i) {
-    const bt_pack_seg& s_ = segs[i];
-    long long nb = (fp.n[i] + kFpElemsPerBlock - 1) / kFpElemsPerBlock;
-    if (nb > 128) nb = 128;   // (more blocks are slower: every wave ends in one 64-bit atomic on the segment's accumulator -- 1024 blocks: 14 -> 25 us for 1.5 M weights)
-    if (fs.any_kl && nb > kMaxSlots / n_segments) nb = kMaxSlots / n_segments;   // one KL slot per block in the workspace
-    fp.first_block[i] = fblocks, fblocks += (int)nb;
-    const long long C4 = (s_.Ci + 3) & ~3ll;
-    long long pb = s_.Co * ((C4 + kPackCh - 1) / kPackCh);   // (row, 64-channel chunk) work items
-    if (pb > 256) pb = 256;
-    pk.first_block[i] = pblocks, pblocks += (int)pb;
-    if (s_.taps > max_taps) max_taps = s_.taps;
-  }
-  fp.first_block[n_segments] = fblocks, pk.first_block[n_segments] = pblocks;
-  fp.nseg = pk.nseg = n_segments;
-  for (int i = 0; i < n_segments; ++i) fs.mu[i] = fp.mu[i], fs.rho[i] = fp.rho[i], fs.state[i] = fp.state[i], fs.n[i] = fp.n[i], fs.first_block[i] = fp.first_block[i];
-  fs.first_block[n_segments] = fblocks, fs.force = fp.force, fs.nseg = n_segments;
+  fs.force = pk.force;
+  // At most 128 fingerprint blocks per segment (more are slower: every wave ends in one 64-bit atomic on the segment's accumulator --
+  // 1024 blocks: 14 -> 25 us for 1.5 M weights), and with a KL one slot per block in the workspace; at most 256 pack blocks.
+  const int fcap = fs.any_kl && kMaxSlots / n_segments < 128 ? kMaxSlots / n_segments : 128;
+  const int fblocks = seg_partition(fs.t, n_segments, elems, kFpElemsPerBlock, fcap, 0, "bt_pack_sync");
+  const int pblocks = seg_partition(pk.t, n_segments, items, 1, 256, 0, "bt_pack_sync");
   // Everything that can refuse the call is checked before the first launch: the fingerprint launch stores every segment's new
   // fingerprint and dirty flag, so a refusal after it would leave the packs stale against fingerprints that say they are current.
   const size_t lds = (size_t)max_taps * (kPackCh + 1) * sizeof(float2);
   if (max_taps > 128) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_sync: kernels larger than 128 taps are not supported");
   const int lds_limit = 128 * (kPackCh + 1) * (int)sizeof(float2);   // (above the default dynamic-LDS limit: 11 x 11 kernels and larger)
-  if (int rc = raise_lds_limit(reinterpret_cast<const void*>(pack_dirty_kernel), lds_limit, "bt_pack_sync")) return rc;
-  hipLaunchKernelGGL(pack_fingerprint_kernel, dim3(fblocks), dim3(kFpThreads), 0, (hipStream_t)stream, fs, ws_counter(workspace), ws_slots(workspace), fblocks);
-  if (int rc = check_launch("bt_pack_sync (fingerprint)")) return rc;
+  if (!plan_only())
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(pack_dirty_kernel), lds_limit, "bt_pack_sync")) return rc;
+  if (int rc = launch_kernel(pack_fingerprint_kernel, nullptr, "bt_pack_sync (fingerprint)", dim3(fblocks), dim3(kFpThreads), 0, 0, (hipStream_t)stream, fs,
+                             ws_counter(workspace), ws_slots(workspace), fblocks))
+    return rc;
   return launch_kernel(pack_dirty_kernel, nullptr, "bt_pack_sync (pack)", dim3(pblocks), dim3(256), (int)lds, lds_limit, (hipStream_t)stream, pk);
 }
 

@@ -572,22 +572,15 @@ def kl_backward_segs(segments, grad_kl, laplace=False):
     dev = segments[0][0].device
     g = _lib.dev_f32(grad_kl.reshape(1).contiguous(), "grad_kl")
     out = []
-    for c0 in range(0, len(segments), _lib.KL_MAX_SEGMENTS):
-        chunk = segments[c0:c0 + _lib.KL_MAX_SEGMENTS]
-        n = len(chunk)
-        arrs = [(C.c_void_p * n)() for _ in range(6)]
-        numel = (C.c_int64 * n)()
-        keep = []
-        for i, (mu, rho, pm, ps) in enumerate(chunk):
-            mu, rho = _lib.dev_f32(mu.detach(), "mu"), _lib.dev_f32(rho.detach(), "rho")
-            pm = None if laplace else _lib.dev_f32(pm, "prior_mu")
-            ps = None if laplace else _lib.dev_f32(ps, "prior_sigma")
-            dmu, drho = torch.empty_like(mu), torch.empty_like(mu)
-            keep.append((mu, rho, pm, ps))
-            out.append((dmu, drho))
-            for a, t in zip(arrs, (mu, rho, pm, ps, dmu, drho)):
-                a[i] = None if t is None else t.data_ptr()
-            numel[i] = mu.numel()
+
+    def prepare(_, seg):
+        mu, rho = _lib.dev_f32(seg[0].detach(), "mu"), _lib.dev_f32(seg[1].detach(), "rho")
+        pm = None if laplace else _lib.dev_f32(seg[2], "prior_mu")
+        ps = None if laplace else _lib.dev_f32(seg[3], "prior_sigma")
+        out.append((torch.empty_like(mu), torch.empty_like(mu)))
+        return (mu, rho, pm, ps) + out[-1]
+
+    for _, n, keep, arrs, numel, _ in _lib.seg_chunks(segments, prepare):
         with _lib.on(dev):
             _lib.check(L.bt_kl_normal_bwd_segs(n, arrs[0], arrs[1], arrs[2] if not laplace else None, arrs[3] if not laplace else None, numel, g.data_ptr(),
                                                _lib.KL_PRIOR_LAPLACE if laplace else 0, arrs[4], arrs[5], _lib.stream_ptr(dev)))
@@ -602,26 +595,17 @@ def kl_hier_backward(segments, grad_kl, needs=None):
     dev = segments[0][0].device
     g = _lib.dev_f32(grad_kl.reshape(1).contiguous(), "grad_kl")
     out = []
-    for c0 in range(0, len(segments), _lib.KL_MAX_SEGMENTS):
-        chunk = segments[c0:c0 + _lib.KL_MAX_SEGMENTS]
-        n = len(chunk)
-        arrs = [(C.c_void_p * n)() for _ in range(11)]
-        numel = (C.c_int64 * n)()
-        keep = []
-        any_out = False
-        for i, seg in enumerate(chunk):
-            ts = [_lib.dev_f32(t.detach(), "kl segment tensor") for t in seg]
-            if len(ts) != 7 or not all(t.numel() == ts[0].numel() for t in ts):
-                raise ValueError("a hierarchical KL segment is (mu, rho, prior_mu, log_a, log_b, a0, b0) of equal numel")
-            want = (True,) * 4 if needs is None else needs[c0 + i]
-            grads = tuple(torch.empty_like(ts[0]) if w else None for w in want)
-            any_out = any_out or any(want)
-            keep.append(ts)
-            out.append(grads)
-            for a, t in zip(arrs, tuple(ts) + grads):
-                a[i] = None if t is None else t.data_ptr()
-            numel[i] = ts[0].numel()
-        if any_out:
+
+    def prepare(j, seg):
+        ts = [_lib.dev_f32(t.detach(), "kl segment tensor") for t in seg]
+        if len(ts) != 7 or not all(t.numel() == ts[0].numel() for t in ts):
+            raise ValueError("a hierarchical KL segment is (mu, rho, prior_mu, log_a, log_b, a0, b0) of equal numel")
+        want = (True,) * 4 if needs is None else needs[j]
+        out.append(tuple(torch.empty_like(ts[0]) if w else None for w in want))
+        return tuple(ts) + out[-1]
+
+    for c0, n, keep, arrs, numel, _ in _lib.seg_chunks(segments, prepare):
+        if any(t is not None for grads in out[c0:c0 + n] for t in grads):
             with _lib.on(dev):
                 _lib.check(L.bt_kl_hier_bwd(n, *arrs[:7], numel, g.data_ptr(), *arrs[7:], _lib.stream_ptr(dev)))
     return out

@@ -147,10 +147,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
             return KLValue.apply((segs, [0] * len(segs), ("layer", self._ws_id), self._prior_kind() == "laplace"), live[0])
         kind = self._prior_kind()
         segs = self._kl_segments()
-        if torch.is_grad_enabled() and any(t.requires_grad for sg in segs for t in sg):
-            from ..autograd import KLNormal
-            return KLNormal.apply((("layer", self._ws_id), kind), *[t for sg in segs for t in sg])
-        return _lib.kl_normal(segs, layer_ids=[0] * len(segs), owner=("layer", self._ws_id), laplace=kind == "laplace")
+        from ..autograd import kl_normal
+        return kl_normal(segs, [0] * len(segs), ("layer", self._ws_id), kind)
 
     # ------------------------------------------------------------------ forward
     def _pack_source(self):

@@ -18,7 +18,7 @@ The two non-weightwise classes raise NotImplementedError from their constructors
 import torch
 from torch.nn import Parameter
 
-from ... import _lib, mc
+from ... import mc
 from .conv_variational import Conv2dReparameterization
 from .linear_variational import LinearReparameterization
 
@@ -66,21 +66,14 @@ class _HierarchicalKL:
 
     def kl_loss(self):
         """The weights' hierarchical KL (a sum over the elements; the bias is not part of it, as in the reference)."""
-        seg = self._hier_segment()
-        owner = ("layer", self._ws_id)
-        if torch.is_grad_enabled() and any(seg[i].requires_grad for i in (0, 1, 3, 4)):
-            from ...autograd import KLHier
-            return KLHier.apply((owner, (0,)), *seg)
-        return _lib.kl_hier([seg], layer_ids=[0], owner=owner)
+        from ...autograd import kl_hier
+        return kl_hier([self._hier_segment()], [0], ("layer", self._ws_id))
 
     def _bias_kl(self):
         """kl_div of the bias against its Gaussian (or Laplace) prior: the parent's mean KL, on the parent's kernels."""
+        from ...autograd import kl_normal
         seg = (self.mu_bias, self.rho_bias, self.prior_bias_mu, self.prior_bias_sigma)
-        kind, owner = self._prior_kind(), ("layer", self._ws_id)
-        if torch.is_grad_enabled() and (self.mu_bias.requires_grad or self.rho_bias.requires_grad):
-            from ...autograd import KLNormal
-            return KLNormal.apply((owner, kind), *seg)
-        return _lib.kl_normal([seg], layer_ids=[0], owner=owner, laplace=kind == "laplace")
+        return kl_normal([seg], [0], ("layer", self._ws_id), self._prior_kind())
 
     def _forward_kl(self):
         kl = self.kl_loss()

@@ -8,7 +8,7 @@ Same contract: in-place recursive swap of leaf modules whose class name contains
 (layers/variational_layers/hiearchial_variational_layers.py) go into bt_kl_hier launches of their own.
 """
 import bayesian_torch_amd.layers as bayesian_layers
-from bayesian_torch_amd import _lib, rng
+from bayesian_torch_amd import rng
 from bayesian_torch_amd.layers._fused import FusedBayesLayer
 from bayesian_torch_amd.layers.base_variational_layer import check_prior_type
 from bayesian_torch_amd.utils.util import get_rho
@@ -123,20 +123,11 @@ def get_kl_loss(m):
             others.append(layer)
     others = lap + others
     kl = None
-    if segs:
-        import torch
-        if torch.is_grad_enabled() and any(t.requires_grad for sg in segs for t in sg):   # training: differentiable, still ONE forward launch
-            from ..autograd import KLNormal
-            kl = KLNormal.apply((("model", id(m)), "normal", tuple(lids)), *[t for sg in segs for t in sg])
-        else:
-            kl = _lib.kl_normal(segs, layer_ids=lids, owner=("model", id(m)))
+    from .. import autograd
+    if segs:     # differentiable in training, ONE forward launch either way
+        kl = autograd.kl_normal(segs, lids, ("model", id(m)), "normal")
     if hier:     # sum of their kl_loss() (the weights' sums; a Linear's bias is not in it, as in the reference): one bt_kl_hier launch per 64 layers
-        hsegs = [layer._hier_segment() for layer in hier]
-        if torch.is_grad_enabled() and any(sg[i].requires_grad for sg in hsegs for i in (0, 1, 3, 4)):
-            from ..autograd import KLHier
-            k = KLHier.apply((("model", id(m), "hier"), tuple(range(len(hsegs)))), *[t for sg in hsegs for t in sg])
-        else:
-            k = _lib.kl_hier(hsegs, layer_ids=list(range(len(hsegs))), owner=("model", id(m), "hier"))
+        k = autograd.kl_hier([layer._hier_segment() for layer in hier], list(range(len(hier))), ("model", id(m), "hier"))
         kl = k if kl is None else kl + k
     for layer in others:     # foreign modules with a kl_loss of their own
         kl = layer.kl_loss() if kl is None else kl + layer.kl_loss()
