@@ -95,6 +95,19 @@ int launch_kernel(void (*kern)(P...), const char* name, const char* who, dim3 gr
   return check_launch(who);
 }
 
+// Output extent of a convolution along one axis (the one place the formula is written), and a bt_conv2d_geom's.
+inline long long conv_out(long long in, int k, int s, int p, int d) { return (in + 2ll * p - (long long)d * (k - 1) - 1) / s + 1; }
+inline long long conv_out_h(const bt_conv2d_geom& g) { return conv_out(g.H, g.kh, g.sh, g.ph, g.dh); }
+inline long long conv_out_w(const bt_conv2d_geom& g) { return conv_out(g.W, g.kw, g.sw, g.pw, g.dw); }
+// What every entry point refuses in a geometry before it divides by any of it: null, or the forward's text (in the forward's order).
+// An empty output (conv_out_h / conv_out_w <= 0) is the caller's next question.
+inline const char* geom_error(const bt_conv2d_geom& g) {
+  if (g.B <= 0 || g.Ci <= 0 || g.H <= 0 || g.W <= 0 || g.Co <= 0 || g.kh <= 0 || g.kw <= 0) return "non-positive dimension";
+  if (g.sh <= 0 || g.sw <= 0 || g.dh <= 0 || g.dw <= 0 || g.ph < 0 || g.pw < 0 || g.groups <= 0) return "bad stride / padding / dilation / groups";
+  if (g.Ci % g.groups || g.Co % g.groups) return "invalid in_channels size";  // conv_variational.py:270-273
+  return nullptr;
+}
+
 inline RngKey make_key(const bt_rng& r, uint32_t tensor) {
   RngKey k;
   k.seed_lo = (uint32_t)r.seed;

@@ -312,13 +312,10 @@ extern "C" int bt_avu_fwd(int32_t S, int32_t B, int32_t C, const float* logits, 
   if (workspace_bytes < avu_ws_bytes(S, B)) return set_error(BT_ERR_WORKSPACE, "bt_avu_fwd: workspace smaller than bt_avu_workspace_bytes");
   const hipStream_t st = (hipStream_t)stream;
   const long long* lab = reinterpret_cast<const long long*>(labels);
-  if (C <= 64)
-    hipLaunchKernelGGL(avu_rows_kernel<64>, dim3((B + 3) / 4), dim3(256), 0, st, S, B, C, unc_type, logits, lab, workspace);
-  else
-    hipLaunchKernelGGL(avu_rows_kernel<256>, dim3(B), dim3(256), 0, st, S, B, C, unc_type, logits, lab, workspace);
-  if (int rc = check_launch("bt_avu_fwd")) return rc;
-  hipLaunchKernelGGL(avu_finish_kernel, dim3(1), dim3(1024), 0, st, B, T, threshold, beta, workspace, loss, v, sums, counts, thresholds, coef);
-  return check_launch("bt_avu_fwd");
+  if (int rc = launch_kernel(C <= 64 ? avu_rows_kernel<64> : avu_rows_kernel<256>, nullptr, "bt_avu_fwd", dim3(C <= 64 ? (B + 3) / 4 : B), dim3(256), 0, 0, st, S, B, C,
+                             unc_type, logits, lab, workspace))
+    return rc;
+  return launch_kernel(avu_finish_kernel, nullptr, "bt_avu_fwd", dim3(1), dim3(1024), 0, 0, st, B, T, threshold, beta, workspace, loss, v, sums, counts, thresholds, coef);
 }
 
 extern "C" int bt_avu_bwd(int32_t S, int32_t B, int32_t C, const float* logits, int32_t unc_type, int32_t T, const float* coef,
@@ -329,9 +326,6 @@ extern "C" int bt_avu_bwd(int32_t S, int32_t B, int32_t C, const float* logits, 
   if ((uintptr_t)workspace & 7u) return set_error(BT_ERR_BAD_ARG, "bt_avu_bwd: bad argument: workspace must be 8-byte aligned");
   if (workspace_bytes < avu_ws_bytes(S, B)) return set_error(BT_ERR_WORKSPACE, "bt_avu_bwd: workspace smaller than bt_avu_workspace_bytes");
   const hipStream_t st = (hipStream_t)stream;
-  if (C <= 64)
-    hipLaunchKernelGGL(avu_bwd_kernel<64>, dim3((B + 3) / 4), dim3(256), 0, st, S, B, C, unc_type, T, logits, workspace, coef, grad_loss, dlogits);
-  else
-    hipLaunchKernelGGL(avu_bwd_kernel<256>, dim3(B), dim3(256), 0, st, S, B, C, unc_type, T, logits, workspace, coef, grad_loss, dlogits);
-  return check_launch("bt_avu_bwd");
+  return launch_kernel(C <= 64 ? avu_bwd_kernel<64> : avu_bwd_kernel<256>, nullptr, "bt_avu_bwd", dim3(C <= 64 ? (B + 3) / 4 : B), dim3(256), 0, 0, st, S, B, C, unc_type, T,
+                       logits, workspace, coef, grad_loss, dlogits);
 }

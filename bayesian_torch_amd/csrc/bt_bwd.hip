@@ -15,7 +15,7 @@
 // wgrad splits the samples over `groups` workgroups per tile (enough to fill the chip), writes one partial per group, and
 // a finishing kernel adds the partials in index order (deterministic), multiplies by sigmoid(rho) and un-permutes the
 // tap-major draw layout into the parameters' own [Co][Ci/g][kh][kw].
-#include "bt_api_internal.h"
+#include "bt_bwd_plan.h"
 
 namespace bt {
 
@@ -43,7 +43,6 @@ struct BwdArgs {
   int kl_laplace;
 };
 
-constexpr int kBK = 16;   // reduction steps per LDS stage
 constexpr int kLS = 68;   // LDS row stride (floats): 64 + 4 keeps the float4 stores aligned and the row reads conflict-free
 
 __device__ __forceinline__ RngKey bwd_key(const BwdArgs& a, uint32_t tensor) {
@@ -356,59 +355,24 @@ __global__ __launch_bounds__(256) void bwd_finish_pair_kernel(const BwdArgs a) {
   else dgrad_finish_body(a, (int)blockIdx.x - a.fin_nw, (int)gridDim.x - a.fin_nw);
 }
 
-// Workgroups per output tile: first the samples (each group keeps whole samples), then chunks of the reduction axis
-// M = B*Ho*Wo (a training step has ONE sample: layer1's 9 output tiles would otherwise be 9 workgroups on 256 CUs).
-// Chunks are multiples of the LDS stage and at least 8 stages long.
-static int wgrad_groups(const bt_conv2d_geom& g, int S, int* sgroups = nullptr, int* mchunk = nullptr) {
-  const int Cig = g.Ci / g.groups, Cog = g.Co / g.groups, Cig4 = (Cig + 3) & ~3, T = g.kh * g.kw;
-  const long long tiles = (long long)((T * Cig4 + 63) / 64) * ((Cog + 63) / 64) * g.groups;
-  static const int w_target = [] { const char* e = getenv("BT_WGRAD_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();   // measurement knob
-  // One workgroup per CU: the pass runs beside dgrad in one launch (bwd_pair_kernel) and every group costs a partial that the finishing
-  // pass reads back (ResNet18 step, env sweep: 512 -> 3.14 ms, 256 -> 2.97, 192 -> 2.98, 128 -> 3.24, 1024 -> 3.22).
-  long long gr = (w_target + tiles - 1) / tiles;
-  if (gr < 1) gr = 1;
-  const long long gs = gr > S ? S : gr;
-  const int Ho = (g.H + 2 * g.ph - g.dh * (g.kh - 1) - 1) / g.sh + 1, Wo = (g.W + 2 * g.pw - g.dw * (g.kw - 1) - 1) / g.sw + 1;
-  const long long M = (long long)g.B * Ho * Wo;
-  long long gm = (gr + gs - 1) / gs;
-  const long long max_gm = (M + 8 * kBK - 1) / (8 * kBK);
-  if (gm > max_gm) gm = max_gm;
-  if (gm < 1) gm = 1;
-  long long chunk = (M + gm - 1) / gm;
-  chunk = (chunk + kBK - 1) / kBK * kBK;
-  gm = (M + chunk - 1) / chunk;
-  if (sgroups) *sgroups = (int)gs;
-  if (mchunk) *mchunk = (int)chunk;
-  return (int)(gs * gm);
-}
-
-// dgrad: pieces of the output-channel reduction, so that a launch offers ~512 workgroups (layer4 of a CIFAR ResNet at one
-// sample: 16 tiles); pieces are multiples of the LDS stage and at least 32 channels.
-static int dgrad_chunks(const bt_conv2d_geom& g, int S, int* dchunk = nullptr) {
-  const int Cig = g.Ci / g.groups, Cog = g.Co / g.groups;
-  const long long M = (long long)g.B * g.H * g.W;
-  const long long tiles = ((M + 63) / 64) * ((Cig + 63) / 64) * S * g.groups;
-  static const int d_target = [] { const char* e = getenv("BT_DGRAD_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();   // measurement knob
-  long long c = (d_target + tiles - 1) / tiles;
-  const long long max_c = (Cog + 31) / 32;
-  if (c > max_c) c = max_c;
-  if (c < 1) c = 1;
-  long long per = (Cog + c - 1) / c;
-  per = (per + kBK - 1) / kBK * kBK;
-  c = (Cog + per - 1) / per;
-  if (dchunk) *dchunk = (int)per;
-  return (int)c;
+// Plan-only digest of the argument block: what it means, not its bytes (the struct has tail padding). Pointers, then every scalar, in this order.
+uint64_t digest_arg(uint64_t h, const BwdArgs& a) {
+  for (const void* p : std::initializer_list<const void*>{a.x, a.g, a.mu_pk, a.sig_pk, a.rho_w, a.eps_w, a.sign_in, a.sign_out, a.dx, a.dmu, a.drho, a.part, a.part_d,
+                                                          a.call_base, a.mu_w, a.pmu_w, a.psig_w, a.gkl})
+    h = digest_arg(h, p);
+  for (long long v : {a.x_sample_stride, a.x_elems, a.out_elems, a.w_elems}) h = digest_arg(h, v);
+  for (int v : {a.pair_wx, a.pair_wy, a.pair_nw, a.pair_dx, a.pair_dy, a.fin_nw, a.B, a.Ci, a.H, a.W, a.Co, a.KH, a.KW, a.SH, a.SW, a.PH, a.PW, a.DH, a.DW, a.G,
+                a.Ho, a.Wo, a.Cig, a.Cog, a.Cig4, a.T, a.S, a.flip, a.groups, a.dchunks, a.dchunk, a.sgroups, a.mchunk, a.kl_laplace})
+    h = digest_arg(h, v);
+  for (uint32_t v : {a.seed_lo, a.seed_hi, a.call, a.layer_id, a.sample0}) h = digest_arg(h, v);
+  return h;
 }
 
 }  // namespace bt
 
 extern "C" size_t bt_conv2d_bwd_workspace(const bt_conv2d_geom* g, int32_t S) {
-  if (!g || S <= 0 || g->groups <= 0) return 0;
-  const int Cig = g->Ci / g->groups, Cig4 = (Cig + 3) & ~3, T = g->kh * g->kw;
-  const size_t wg = (size_t)2 * bt::wgrad_groups(*g, S) * g->Co * T * Cig4 * sizeof(float);
-  const int dc = bt::dgrad_chunks(*g, S);
-  const size_t dg = dc > 1 ? (size_t)dc * S * g->B * g->Ci * g->H * g->W * sizeof(float) : 0;
-  return wg + dg;   // (wgrad's partials, then dgrad's: the two passes run side by side in one launch when both are asked for)
+  bt::BwdPlan pl;
+  return g && bt::bwd_plan(*g, S, true, true, &pl) == bt::kBwdOk ? pl.wgrad_bytes + pl.dgrad_bytes : 0;
 }
 
 static int conv2d_bwd_impl(const bt_conv2d_geom* g, int32_t S, int32_t flipout, const float* x, int64_t x_sample_stride, const float* grad_out,
@@ -424,74 +388,46 @@ static int conv2d_bwd_impl(const bt_conv2d_geom* g, int32_t S, int32_t flipout, 
   if (!p->mu_packed || !p->sigma_packed || !p->rho_w) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: needs rho_w and the packed parameters (bt_pack_params)");
   // dgrad reads the packs as float4 quads (the one access of this file wider than 4 bytes); a pack is a buffer of its own, never a slice
   if ((((uintptr_t)p->mu_packed | (uintptr_t)p->sigma_packed) & 15u) != 0) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: mu_packed / sigma_packed must be 16-byte aligned");
-  if (S <= 0 || g->B <= 0 || g->Ci <= 0 || g->Co <= 0 || g->groups <= 0 || g->Ci % g->groups || g->Co % g->groups) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: bad geometry");
+  BwdPlan pl;
+  const int refused = bwd_plan(*g, S, dx != nullptr, dmu_w != nullptr, &pl);
+  if (refused == kBwdBadGeometry || x_sample_stride < 0) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: bad geometry");
   if ((dmu_w == nullptr) != (drho_w == nullptr)) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: dmu_w and drho_w go together");
   const bool inj = d->eps_w != nullptr;
   if (flipout && inj != (d->sign_in != nullptr && d->sign_out != nullptr)) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: inject all draws or none");
+  if (refused == kBwdEmptyOutput) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: empty output");
+  if (refused == kBwdTooLarge) return set_error(BT_ERR_UNSUPPORTED, "bt_conv2d_bwd: tensor too large for the 32-bit sign / draw indices");
+  if (((dx && pl.dchunks > 1) || dmu_w) && (!workspace || workspace_bytes < pl.wgrad_bytes + pl.dgrad_bytes))
+    return set_error(BT_ERR_WORKSPACE, "bt_conv2d_bwd: workspace smaller than bt_conv2d_bwd_workspace()");
   BwdArgs a = {};
   a.x = x, a.g = grad_out, a.mu_pk = p->mu_packed, a.sig_pk = p->sigma_packed, a.rho_w = p->rho_w;
   a.eps_w = d->eps_w, a.sign_in = flipout ? d->sign_in : nullptr, a.sign_out = flipout ? d->sign_out : nullptr;
   a.dx = dx, a.dmu = dmu_w, a.drho = drho_w, a.part = (float*)workspace;
+  a.part_d = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pl.part_d_offset);   // dgrad's partials live behind wgrad's
   if (grad_kl) a.gkl = grad_kl, a.mu_w = p->mu_w, a.pmu_w = p->prior_mu_w, a.psig_w = p->prior_sigma_w, a.kl_laplace = p->prior_kind == BT_PRIOR_LAPLACE ? 1 : 0;
   a.B = g->B, a.Ci = g->Ci, a.H = g->H, a.W = g->W, a.Co = g->Co, a.KH = g->kh, a.KW = g->kw;
   a.SH = g->sh, a.SW = g->sw, a.PH = g->ph, a.PW = g->pw, a.DH = g->dh, a.DW = g->dw, a.G = g->groups;
-  a.Ho = (g->H + 2 * g->ph - g->dh * (g->kh - 1) - 1) / g->sh + 1;
-  a.Wo = (g->W + 2 * g->pw - g->dw * (g->kw - 1) - 1) / g->sw + 1;
-  if (a.Ho <= 0 || a.Wo <= 0) return set_error(BT_ERR_BAD_ARG, "bt_conv2d_bwd: empty output");
-  a.Cig = g->Ci / g->groups, a.Cog = g->Co / g->groups, a.Cig4 = (a.Cig + 3) & ~3, a.T = g->kh * g->kw, a.S = S, a.flip = flipout ? 1 : 0;
-  a.x_sample_stride = x_sample_stride;
-  a.x_elems = (long long)g->B * g->Ci * g->H * g->W;
-  a.out_elems = (long long)g->B * g->Co * a.Ho * a.Wo;
-  a.w_elems = (long long)g->Co * a.Cig * a.T;
-  if (a.x_elems >= (1ll << 31) || a.out_elems >= (1ll << 31) || a.w_elems * 4 >= (1ll << 31)) return set_error(BT_ERR_UNSUPPORTED, "bt_conv2d_bwd: tensor too large for the 32-bit sign / draw indices");
+  a.Ho = pl.Ho, a.Wo = pl.Wo, a.Cig = pl.Cig, a.Cog = pl.Cog, a.Cig4 = pl.Cig4, a.T = pl.T, a.S = S, a.flip = flipout ? 1 : 0;
+  a.x_sample_stride = x_sample_stride, a.x_elems = pl.x_elems, a.out_elems = pl.out_elems, a.w_elems = pl.w_elems;
+  if (dx) a.dchunks = pl.dchunks, a.dchunk = pl.dchunk;
+  if (dmu_w) a.groups = pl.groups, a.sgroups = pl.sgroups, a.mchunk = pl.mchunk;
   a.seed_lo = (uint32_t)d->rng.seed, a.seed_hi = (uint32_t)(d->rng.seed >> 32);
   a.call = d->rng.call, a.call_base = d->rng.call_base_dev, a.layer_id = d->rng.layer_id, a.sample0 = d->rng.sample0;
   hipStream_t st = (hipStream_t)stream;
-  const size_t need_ws = bt_conv2d_bwd_workspace(g, S);
-  dim3 dgrid(1, 1, 1), wgrid(1, 1, 1);
-  long long n_dfin = 0, n_wfin = 0;
-  if (dx) {
-    const long long M = (long long)g->B * g->H * g->W;
-    a.dchunks = dgrad_chunks(*g, S, &a.dchunk);
-    if (a.dchunks > 1 && (!workspace || workspace_bytes < need_ws))
-      return set_error(BT_ERR_WORKSPACE, "bt_conv2d_bwd: workspace smaller than bt_conv2d_bwd_workspace()");
-    dgrid = dim3((unsigned)((M + 63) / 64), (unsigned)((a.Cig + 63) / 64), (unsigned)(S * g->groups * a.dchunks));
-    if (a.dchunks > 1) n_dfin = ((long long)S * a.x_elems + 255) / 256 > 4096 ? 4096 : ((long long)S * a.x_elems + 255) / 256;
-  }
-  if (dmu_w) {
-    a.groups = wgrad_groups(*g, S, &a.sgroups, &a.mchunk);
-    if (!workspace || workspace_bytes < need_ws) return set_error(BT_ERR_WORKSPACE, "bt_conv2d_bwd: workspace smaller than bt_conv2d_bwd_workspace()");
-    wgrid = dim3((unsigned)((a.T * a.Cig4 + 63) / 64), (unsigned)((a.Cog + 63) / 64), (unsigned)(a.groups * g->groups));
-    n_wfin = (a.w_elems + 255) / 256 > 4096 ? 4096 : (a.w_elems + 255) / 256;
-  }
-  // dgrad's partials live behind wgrad's
-  a.part_d = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)2 * wgrad_groups(*g, S) * g->Co * a.T * a.Cig4 * sizeof(float));
-  const long long nwb = (long long)wgrid.x * wgrid.y * wgrid.z, ndb = (long long)dgrid.x * dgrid.y * dgrid.z;
-  static const bool no_pair = [] { const char* e = getenv("BT_NO_BWD_PAIR"); return e && *e && *e != '0'; }();   // measurement knob: the two passes as launches of their own
-  if (!no_pair && dx && dmu_w && nwb + ndb < 0x7FFFFFFFll) {   // both passes: ONE launch, and one for the two finishing passes
-    a.pair_wx = (int)wgrid.x, a.pair_wy = (int)wgrid.y, a.pair_nw = (int)nwb, a.pair_dx = (int)dgrid.x, a.pair_dy = (int)dgrid.y;
-    if (flipout) hipLaunchKernelGGL(bwd_pair_kernel<true>, dim3((unsigned)(nwb + ndb)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(bwd_pair_kernel<false>, dim3((unsigned)(nwb + ndb)), dim3(256), 0, st, a);
-    if (int rc = check_launch("bt_conv2d_bwd (wgrad + dgrad)")) return rc;
-    a.fin_nw = (int)n_wfin;
-    hipLaunchKernelGGL(bwd_finish_pair_kernel, dim3((unsigned)(n_wfin + n_dfin)), dim3(256), 0, st, a);
-    return check_launch("bt_conv2d_bwd (finish)");
+  const dim3 wgrid(pl.wgrid[0], pl.wgrid[1], pl.wgrid[2]), dgrid(pl.dgrid[0], pl.dgrid[1], pl.dgrid[2]), block(256);
+  if (pl.pair) {   // both passes: ONE launch, and one for the two finishing passes
+    a.pair_wx = (int)wgrid.x, a.pair_wy = (int)wgrid.y, a.pair_nw = (int)pl.wblocks, a.pair_dx = (int)dgrid.x, a.pair_dy = (int)dgrid.y;
+    if (int rc = launch_kernel(flipout ? bwd_pair_kernel<true> : bwd_pair_kernel<false>, nullptr, "bt_conv2d_bwd (wgrad + dgrad)", dim3((unsigned)(pl.wblocks + pl.dblocks)), block, 0, 0, st, a)) return rc;
+    a.fin_nw = pl.n_wfin;
+    return launch_kernel(bwd_finish_pair_kernel, nullptr, "bt_conv2d_bwd (finish)", dim3((unsigned)(pl.n_wfin + pl.n_dfin)), block, 0, 0, st, a);
   }
   if (dx) {
-    if (flipout) hipLaunchKernelGGL(dgrad_kernel<true>, dgrid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(dgrad_kernel<false>, dgrid, dim3(256), 0, st, a);
-    if (int rc = check_launch("bt_conv2d_bwd (dgrad)")) return rc;
-    if (a.dchunks > 1) {
-      hipLaunchKernelGGL(dgrad_finish_kernel, dim3((unsigned)n_dfin), dim3(256), 0, st, a);
-      if (int rc = check_launch("bt_conv2d_bwd (dgrad finish)")) return rc;
-    }
+    if (int rc = launch_kernel(flipout ? dgrad_kernel<true> : dgrad_kernel<false>, nullptr, "bt_conv2d_bwd (dgrad)", dgrid, block, 0, 0, st, a)) return rc;
+    if (pl.n_dfin)
+      if (int rc = launch_kernel(dgrad_finish_kernel, nullptr, "bt_conv2d_bwd (dgrad finish)", dim3((unsigned)pl.n_dfin), block, 0, 0, st, a)) return rc;
   }
   if (dmu_w) {
-    if (flipout) hipLaunchKernelGGL(wgrad_kernel<true>, wgrid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(wgrad_kernel<false>, wgrid, dim3(256), 0, st, a);
-    if (int rc = check_launch("bt_conv2d_bwd (wgrad)")) return rc;
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)n_wfin), dim3(256), 0, st, a);
-    if (int rc = check_launch("bt_conv2d_bwd (finish)")) return rc;
+    if (int rc = launch_kernel(flipout ? wgrad_kernel<true> : wgrad_kernel<false>, nullptr, "bt_conv2d_bwd (wgrad)", wgrid, block, 0, 0, st, a)) return rc;
+    if (int rc = launch_kernel(wgrad_finish_kernel, nullptr, "bt_conv2d_bwd (finish)", dim3((unsigned)pl.n_wfin), block, 0, 0, st, a)) return rc;
   }
   return BT_OK;
 }
@@ -507,3 +443,7 @@ extern "C" int bt_conv2d_bwd_kl(const bt_conv2d_geom* g, int32_t S, int32_t flip
                                 size_t workspace_bytes, bt_stream_t stream) {
   return conv2d_bwd_impl(g, S, flipout, x, x_sample_stride, grad_out, p, d, grad_kl, dx, dmu_w, drho_w, workspace, workspace_bytes, stream);
 }
+
+// Test hooks (not part of include/bt_hip.h): the workgroup targets of the two passes (<= 0: the default), and pairing on / off.
+extern "C" void bt_debug_bwd_targets(int wgrad, int dgrad) { bt::g_wgrad_wgs.set(wgrad > 0 ? wgrad : bt::kWgradWgs), bt::g_dgrad_wgs.set(dgrad > 0 ? dgrad : bt::kDgradWgs); }
+extern "C" void bt_debug_bwd_pair(int on) { bt::g_no_bwd_pair.set(on ? 0 : 1); }

@@ -37,11 +37,11 @@ struct Call {
   // an input-dilated launch convolves the VIRTUAL image: the real one with u - 1 zeros between its pixels, padded by lo / hi
   long long virt_H() const { return u ? (long long)(g.H - 1) * u->uh + 1 + u->lo_h + u->hi_h : g.H; }
   long long virt_W() const { return u ? (long long)(g.W - 1) * u->uw + 1 + u->lo_w + u->hi_w : g.W; }
-  int out_H() const { return (int)((virt_H() + 2 * g.ph - (long long)g.dh * (g.kh - 1) - 1) / g.sh + 1); }
-  int out_W() const { return (int)((virt_W() + 2 * g.pw - (long long)g.dw * (g.kw - 1) - 1) / g.sw + 1); }
+  int out_H() const { return (int)conv_out(virt_H(), g.kh, g.sh, g.ph, g.dh); }
+  int out_W() const { return (int)conv_out(virt_W(), g.kw, g.sw, g.pw, g.dw); }
   bool updil() const { return u && (u->uh > 1 || u->uw > 1 || u->lo_h || u->hi_h || u->lo_w || u->hi_w); }   // (else: the plain convolution, launch for launch)
   bool dwin() const { return w && !(w->kd == 1 && w->D == 1 && w->pd == 0); }   // (else: the plain convolution, launch for launch)
-  long long out_D() const { return ((long long)w->D + 2ll * w->pd - (long long)w->dd * (w->kd - 1) - 1) / w->sd + 1; }
+  long long out_D() const { return conv_out(w->D, w->kd, w->sd, w->pd, w->dd); }
   long long real_x_elems() const { return dwin() ? (long long)(g.B / out_D()) * (g.Ci / w->kd) * w->D * g.H * g.W : (long long)g.B * g.Ci * g.H * g.W; }
   bool packed_eps() const { return (d->rng.flags & BT_DRAWS_EPS_PACKED) != 0; }
   bool pooled() const { return ep && ep->pool != BT_POOL_NONE; }
@@ -58,9 +58,7 @@ struct Call {
     if (!p->mu_w || !p->rho_w) return bad("mu_w / rho_w are required");
     if ((p->mu_b == nullptr) != (p->rho_b == nullptr)) return bad("mu_b and rho_b must both be given or both be NULL");
     if (S <= 0) return bad("S must be >= 1");
-    if (g.B <= 0 || g.Ci <= 0 || g.H <= 0 || g.W <= 0 || g.Co <= 0 || g.kh <= 0 || g.kw <= 0) return bad("non-positive dimension");
-    if (g.sh <= 0 || g.sw <= 0 || g.dh <= 0 || g.dw <= 0 || g.ph < 0 || g.pw < 0 || g.groups <= 0) return bad("bad stride / padding / dilation / groups");
-    if (g.Ci % g.groups || g.Co % g.groups) return bad("invalid in_channels size");  // conv_variational.py:270-273
+    if (const char* e = geom_error(g)) return bad(e);
     if (x_sample_stride < 0) return bad("negative x_sample_stride");
     if (u) {
       if (u->uh < 1 || u->uw < 1) return bad("input dilation must be >= 1");

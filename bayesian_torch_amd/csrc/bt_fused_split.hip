@@ -141,8 +141,8 @@ static bool skinny_plan(int B, int Ci, int H, int W, int Co, int KH, int KW, int
   return true;
 }
 long long skinny_scratch_bytes(const bt_conv2d_geom& g, int S) {
-  if (g.B <= 0 || g.Ci <= 0 || g.Co <= 0 || g.groups <= 0 || g.Ci % g.groups || g.Co % g.groups || g.sh <= 0 || g.sw <= 0 || g.dh <= 0 || g.dw <= 0) return 0;
-  const int Ho = (g.H + 2 * g.ph - g.dh * (g.kh - 1) - 1) / g.sh + 1, Wo = (g.W + 2 * g.pw - g.dw * (g.kw - 1) - 1) / g.sw + 1;
+  if (geom_error(g)) return 0;
+  const int Ho = (int)conv_out_h(g), Wo = (int)conv_out_w(g);
   SkinnyPlan p;
   return skinny_plan(g.B, g.Ci, g.H, g.W, g.Co, g.kh, g.kw, g.ph, g.pw, g.dh, g.dw, g.groups, Ho, Wo, S, &p) ? p.scratch : 0;
 }

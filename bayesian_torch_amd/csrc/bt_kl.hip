@@ -147,9 +147,8 @@ extern "C" int bt_kl_normal_bwd(const float* mu, const float* rho, const float* 
   const int lap = (flags & BT_KL_PRIOR_LAPLACE) ? 1 : 0;
   if (!lap && (!prior_mu || !prior_sigma)) return set_error(BT_ERR_BAD_ARG, "bt_kl_normal_bwd: priors are required for the normal prior");
   const long long nb = (numel + 255) / 256;
-  hipLaunchKernelGGL(kl_normal_bwd_kernel, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, (hipStream_t)stream, mu, rho, prior_mu, prior_sigma, grad_kl,
-                     (long long)numel, lap, dmu, drho);
-  return check_launch("bt_kl_normal_bwd");
+  return launch_kernel(kl_normal_bwd_kernel, nullptr, "bt_kl_normal_bwd", dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, 0, (hipStream_t)stream, mu, rho, prior_mu,
+                       prior_sigma, grad_kl, (long long)numel, lap, dmu, drho);
 }
 
 extern "C" int bt_kl_normal_bwd_segs(int32_t n_segments, const float* const* mu, const float* const* rho, const float* const* prior_mu,

@@ -243,9 +243,8 @@ extern "C" int bt_lowrank_mean(const float* mu, const float* L, int64_t n, int32
   bt_rng none = {};
   const bt_rng& R = rng ? *rng : none;
   const dim3 grid((unsigned)((n + kLrThreads - 1) / kLrThreads), (unsigned)((S + kLrSC - 1) / kLrSC));
-  hipLaunchKernelGGL(lowrank_mean_kernel, grid, dim3(kLrThreads), 0, (hipStream_t)stream, mu, L, (long long)n, (int)r, (int)S, z, make_key(R, 4), R.call_base_dev,
-                     R.sample0, m);
-  return check_launch("bt_lowrank_mean");
+  return launch_kernel(lowrank_mean_kernel, nullptr, "bt_lowrank_mean", grid, dim3(kLrThreads), 0, 0, (hipStream_t)stream, mu, L, (long long)n, (int)r, (int)S, z,
+                       make_key(R, 4), R.call_base_dev, R.sample0, m);
 }
 
 extern "C" size_t bt_kl_lowrank_workspace(int64_t n, int32_t r) {
@@ -265,18 +264,12 @@ extern "C" int bt_kl_lowrank(const float* mu, const float* L, int64_t n, int32_t
   double* const part = reinterpret_cast<double*>(workspace);
   double* const A = part + (long long)p.C * p.stride;
   const dim3 grid((unsigned)(p.nt * p.nt + 1), (unsigned)p.C);
-  if (p.T == 16)
-    hipLaunchKernelGGL(kl_lowrank_sweep_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, mu, L, prior_mean, prior_var, (long long)n, (int)r, (double)d, p.nt,
-                       p.chunk, p.stride, part);
-  else
-    hipLaunchKernelGGL(kl_lowrank_sweep_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, mu, L, prior_mean, prior_var, (long long)n, (int)r, (double)d, p.nt,
-                       p.chunk, p.stride, part);
-  if (int rc = check_launch("bt_kl_lowrank (sweep)")) return rc;
+  if (int rc = launch_kernel(p.T == 16 ? kl_lowrank_sweep_kernel<16> : kl_lowrank_sweep_kernel<4>, nullptr, "bt_kl_lowrank (sweep)", grid, dim3(256), 0, 0,
+                             (hipStream_t)stream, mu, L, prior_mean, prior_var, (long long)n, (int)r, (double)d, p.nt, p.chunk, p.stride, part))
+    return rc;
   int NB = kFinPanelDoubles / r;
   NB = NB > 16 ? 16 : NB;
   const int lds = NB * r * (int)sizeof(double);   // <= 64 KiB
-  if (int rc = raise_lds_limit(reinterpret_cast<const void*>(kl_lowrank_finish_kernel), kFinPanelDoubles * (int)sizeof(double), "bt_kl_lowrank")) return rc;
-  hipLaunchKernelGGL(kl_lowrank_finish_kernel, dim3(1), dim3(kFinThreads), (size_t)lds, (hipStream_t)stream, part, p.C, p.stride, (long long)n, (int)r, NB, (double)d, A,
-                     kl_out, bad_pivots);
-  return check_launch("bt_kl_lowrank (finish)");
+  return launch_kernel(kl_lowrank_finish_kernel, nullptr, "bt_kl_lowrank (finish)", dim3(1), dim3(kFinThreads), lds, kFinPanelDoubles * (int)sizeof(double),
+                       (hipStream_t)stream, part, p.C, p.stride, (long long)n, (int)r, NB, (double)d, A, kl_out, bad_pivots);
 }

@@ -147,9 +147,8 @@ extern "C" int bt_rng_normal_fill(const bt_rng* rng, uint32_t tensor_id, int32_t
   if (nq > (1ll << 32)) return set_error(BT_ERR_UNSUPPORTED, "bt_rng_normal_fill: tensor too large");
   int gx = (int)((nq + 255) / 256);
   if (gx > 2048) gx = 2048;
-  hipLaunchKernelGGL(rng_normal_fill_kernel, dim3(gx, S), dim3(256), 0, (hipStream_t)stream, make_key(*rng, tensor_id), rng->call_base_dev,
-                     rng->sample0, (long long)rows, (long long)inner, (long long)taps, out);
-  return check_launch("bt_rng_normal_fill");
+  return launch_kernel(rng_normal_fill_kernel, nullptr, "bt_rng_normal_fill", dim3(gx, S), dim3(256), 0, 0, (hipStream_t)stream, make_key(*rng, tensor_id),
+                       rng->call_base_dev, rng->sample0, (long long)rows, (long long)inner, (long long)taps, out);
 }
 
 extern "C" int bt_rng_sign_fill(const bt_rng* rng, uint32_t tensor_id, int32_t S, int64_t n, float* out, bt_stream_t stream) {
@@ -157,8 +156,8 @@ extern "C" int bt_rng_sign_fill(const bt_rng* rng, uint32_t tensor_id, int32_t S
   if (!rng || !out || S <= 0 || n <= 0 || tensor_id > 3 || S > 65535 || n > 0xFFFFFFFFll) return set_error(BT_ERR_BAD_ARG, "bt_rng_sign_fill: bad argument");
   int gx = (int)((n + 255) / 256);
   if (gx > 2048) gx = 2048;
-  hipLaunchKernelGGL(rng_sign_fill_kernel, dim3(gx, S), dim3(256), 0, (hipStream_t)stream, make_key(*rng, tensor_id), rng->call_base_dev, rng->sample0, (long long)n, out);
-  return check_launch("bt_rng_sign_fill");
+  return launch_kernel(rng_sign_fill_kernel, nullptr, "bt_rng_sign_fill", dim3(gx, S), dim3(256), 0, 0, (hipStream_t)stream, make_key(*rng, tensor_id), rng->call_base_dev,
+                       rng->sample0, (long long)n, out);
 }
 
 extern "C" int bt_rng_philox_raw(uint64_t seed, const uint32_t ctr[4], uint32_t out_host[4]) {
@@ -206,11 +205,8 @@ __global__ __launch_bounds__(256) void mc_epilogue_small_kernel(int S, int B, in
 extern "C" int bt_mc_epilogue(int32_t S, int32_t B, int32_t C, const float* logits, float* packed, bt_stream_t stream) {
   using namespace bt;
   if (S <= 0 || B <= 0 || C <= 0 || !logits || !packed) return set_error(BT_ERR_BAD_ARG, "bt_mc_epilogue: bad argument");
-  if (C <= 64)
-    hipLaunchKernelGGL(mc_epilogue_small_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, B, C, logits, packed);
-  else
-    hipLaunchKernelGGL(mc_epilogue_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, S, B, C, logits, packed);
-  return check_launch("bt_mc_epilogue");
+  return launch_kernel(C <= 64 ? mc_epilogue_small_kernel : mc_epilogue_kernel, nullptr, "bt_mc_epilogue", dim3(C <= 64 ? (B + 3) / 4 : B), dim3(256), 0, 0,
+                       (hipStream_t)stream, S, B, C, logits, packed);
 }
 
 // MaxPool2d(3, 2, 1) over NCHW planes -- the stem's pooling when the fused launch could not hold whole output images in a tile (the
@@ -266,8 +262,8 @@ extern "C" int bt_maxpool_3x3s2(const float* in, float* out, int64_t planes, int
   const long long items = (long long)planes * Ho * Wq;
   long long blocks = (items + 255) / 256;
   if (blocks > (1ll << 22)) blocks = 1ll << 22;   // grid-stride beyond that
-  hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, out, items, (int)H, (int)W, Ho, Wo, Wq);
-  return check_launch("bt_maxpool_3x3s2");
+  return launch_kernel(maxpool3x3s2_kernel, nullptr, "bt_maxpool_3x3s2", dim3((unsigned)blocks), dim3(256), 0, 0, (hipStream_t)stream, in, out, items, (int)H, (int)W, Ho,
+                       Wo, Wq);
 }
 
 extern "C" int bt_pack_params(const float* mu_w, const float* rho_w, int64_t Co, int64_t Ci, int64_t taps, float* mu_packed,
@@ -277,9 +273,8 @@ extern "C" int bt_pack_params(const float* mu_w, const float* rho_w, int64_t Co,
   const long long n = (long long)Co * taps * ((Ci + 3) & ~3ll);
   int gx = (int)((n + 255) / 256);
   if (gx > 4096) gx = 4096;
-  hipLaunchKernelGGL(pack_params_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, mu_w, rho_w, (long long)Co, (long long)Ci, (long long)taps,
-                     mu_packed, sigma_packed);
-  return check_launch("bt_pack_params");
+  return launch_kernel(pack_params_kernel, nullptr, "bt_pack_params", dim3(gx), dim3(256), 0, 0, (hipStream_t)stream, mu_w, rho_w, (long long)Co, (long long)Ci,
+                       (long long)taps, mu_packed, sigma_packed);
 }
 
 // Test hook (not part of include/bt_hip.h): fills the whole LDS of every CU with NaN patterns (fp32 quiet NaNs = bf16 NaN pairs).

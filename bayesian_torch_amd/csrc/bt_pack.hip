@@ -268,13 +268,12 @@ extern "C" int bt_pack_signs(const float* signs, int32_t S, int64_t n, uint8_t* 
   if ((((uintptr_t)signs_packed) & 15u) != 0) return set_error(BT_ERR_BAD_ARG, "bt_pack_signs: signs_packed must be 16-byte aligned");
   if (n >= (1ll << 30)) return set_error(BT_ERR_UNSUPPORTED, "bt_pack_signs: a sample of 2^30 elements or more exceeds the kernels' 32-bit offsets");
   const long long wps = BT_SIGNS_PACKED_STRIDE(n) / 4, words = (long long)S * wps;
-  if (hipMemsetAsync(not_pm1_count, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
+  if (!plan_only() && hipMemsetAsync(not_pm1_count, 0, sizeof(uint32_t), (hipStream_t)stream) != hipSuccess)
     return set_error(BT_ERR_HIP_BASE, "bt_pack_signs: hipMemsetAsync failed");
   long long blocks = (words + 255) / 256;
   if (blocks > 4096) blocks = 4096;   // (the rest in the kernel's loop)
-  hipLaunchKernelGGL(pack_signs_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, signs, reinterpret_cast<uint32_t*>(signs_packed), (long long)n, wps,
-                     words, not_pm1_count);
-  return check_launch("bt_pack_signs");
+  return launch_kernel(pack_signs_kernel, nullptr, "bt_pack_signs", dim3((unsigned)blocks), dim3(256), 0, 0, (hipStream_t)stream, signs,
+                       reinterpret_cast<uint32_t*>(signs_packed), (long long)n, wps, words, not_pm1_count);
 }
 
 extern "C" int bt_pack_eps(const float* eps_w, int32_t S, int64_t Co, int64_t Ci, int64_t taps, float* eps_packed, bt_stream_t stream) {

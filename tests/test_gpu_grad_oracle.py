@@ -292,6 +292,31 @@ def test_deferred_wgrad_on_supplied_draws_equals_the_paired_launch(row_id):
     _same_bits(f"row {row_id}: deferred vs paired", split, paired)
 
 
+@pytest.mark.parametrize("row_id", ["A", "C"])
+def test_unpaired_launches_equal_the_paired_launch(row_id):
+    """bt_debug_bwd_pair(0): dgrad, its finishing pass, wgrad and its finishing pass as four launches instead of two -- the same
+    bodies, block decode and finishing order, so the same bits (A: two reduction chunks, three dgrad pieces; C: Flipout, stride 2,
+    groups 2).  Both steps read the same supplied draws."""
+    import ctypes as C
+    from bayesian_torch_amd import _lib, mc, rng
+    hooks = C.CDLL(_lib.LIB_PATH)      # the bt_debug_* hooks are outside include/bt_hip.h
+    rng.set_mode("philox")
+    rng.manual_seed(11)
+    layer, x0, S, B = _layer_and_input(row_id, False)
+    with torch.no_grad(), mc.mc_samples(S, B):
+        layer(x0, return_kl=False)
+    layer.inject_draw = layer.materialize_last_draw()
+    try:
+        hooks.bt_debug_bwd_pair(1)
+        _, gout, paired = _step(layer, x0, S, B)
+        hooks.bt_debug_bwd_pair(0)
+        _, _, unpaired = _step(layer, x0, S, B, gout)
+    finally:
+        hooks.bt_debug_bwd_pair(1)
+    assert all(g is not None for g in paired[:3])
+    _same_bits(f"row {row_id}: unpaired vs paired", unpaired, paired)
+
+
 # ------------------------------------------------------------------------------------------------------------ C. LSTM through time
 @pytest.mark.parametrize("name", ["lstm_reparam_7x5", "lstm_flipout_7x5"])
 def test_lstm_gradients_through_time_match_fp64_autograd(name):

@@ -105,3 +105,32 @@ def test_supplied_draw_rows_reach_the_planned_splits(row_id):
     Cig4 = (Ci // G + 3) // 4 * 4
     want = 4 * (2 * groups * Co * kh * kw * Cig4 + (pieces * S * B * Ci * H * W if pieces > 1 else 0))
     assert int(_lib.lib().bt_conv2d_bwd_workspace(C.byref(geom), S)) == want
+
+
+@pytest.mark.parametrize("row_id", ["A", "D", "E", "G"])
+def test_rows_with_dgrad_pieces_pair_when_both_gradients_are_asked_for(row_id):
+    """Through the plan-only record (no device): with dx and the weight gradients asked for, the rows whose dgrad runs in pieces launch
+    twice -- wgrad + dgrad in one grid, then the two finishing passes in one grid of n_wfin + n_dfin blocks of 256 threads (at most
+    4096 each) -- and four times with pairing off, the last launch being wgrad's finishing pass alone."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("record_bwd_launches", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "record_bwd_launches.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    case, geom, S = next(t for t in rec.draw_row_geoms() if t[0] == "row" + row_id)
+    B, Ci, H, W, Co, kh, kw = geom[:7]
+    assert DRAW_ROW_PLANS[row_id][1] > 1
+    n_wfin = min(4096, (Co * (Ci // geom[13]) * kh * kw + 255) // 256)
+    n_dfin = min(4096, (S * B * Ci * H * W + 255) // 256)
+    r = rec.Recorder()
+    r.h.bt_debug_plan_only(1)
+    try:
+        for pair, launches, last in ((1, 2, n_wfin + n_dfin), (0, 4, n_wfin)):
+            r.h.bt_debug_bwd_pair(pair)
+            r.call(case, geom, S, "both", flip="Flipout" in GC.DRAW_ROW[row_id][1])
+            line = r.lines["bt_conv2d_bwd"][-1].split("|")
+            assert line[2] == "0" and int(line[4]) == launches, line
+            assert list(r.rec[:6]) == [last, 1, 1, 256, 1, 1], (pair, list(r.rec[:9]))
+    finally:
+        r.h.bt_debug_bwd_pair(1)
+        r.h.bt_debug_plan_only(0)
