@@ -71,6 +71,15 @@ class bt_dwin(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kd", "D", "sd", "dd", "pd")]
 
 
+class bt_q8_pair(C.Structure):
+    _fields_ = [("scale", C.c_double), ("zero_point", C.c_int32), ("reserved", C.c_int32)]
+
+
+class bt_q8_params(C.Structure):
+    _fields_ = [(n, bt_q8_pair) for n in ("eps", "mul", "add", "inp", "out")] + [("s_mu", C.c_double), ("s_sigma", C.c_double)] \
+        + [(n, _vp) for n in ("mu_packed", "sigma_packed", "mu_b", "sigma_b")]
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -124,6 +133,9 @@ _PROTOS = {
     "bt_kl_hier": (C.c_int, [C.c_int32] + [C.POINTER(_vp)] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32), _vp, _vp, _vp, C.c_size_t, _vp]),
     "bt_kl_hier_bwd": (C.c_int, [C.c_int32] + [C.POINTER(_vp)] * 7 + [C.POINTER(C.c_int64), _vp] + [C.POINTER(_vp)] * 4 + [_vp]),
     "bt_special_eval": (C.c_int, [C.c_int32, _f32p, C.c_int64, _f32p]),
+    "bt_q8_pack": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "bt_q8_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_q8_linear_fwd": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -665,3 +665,60 @@ def avu_backward(logits, unc_type, T, coef, workspace, grad_loss):
         _lib.check(_lib.lib().bt_avu_bwd(S, B, Cc, logits.data_ptr(), int(unc_type), int(T), coef.data_ptr(), g.data_ptr(), workspace.data_ptr(),
                                          workspace.numel(), dlogits.data_ptr(), _lib.stream_ptr(dev)))
     return dlogits
+
+
+def _dev_i8(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} is on {t.device}: the INT8 forward runs on a HIP (MI355X) device only; there is no CPU implementation of this path")
+    if t.dtype != torch.int8:
+        raise TypeError(f"{what} must be int8, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def q8_pack(q_mu, q_sigma):
+    """The [Co][taps][Ci16] int8 packs of a quantised layer's two parameter images (bt_q8_pack; Ci16: Ci rounded up to a multiple of
+    16, padding 0). q_mu, q_sigma: int8 [Co, Ci, kh, kw] or [Out, In] -> (mu_packed, sigma_packed), each [Co, taps, Ci16]."""
+    q_mu, q_sigma = _dev_i8(q_mu, "q_mu"), _dev_i8(q_sigma, "q_sigma")
+    if q_mu.shape != q_sigma.shape or q_mu.dim() not in (2, 4):
+        raise RuntimeError("q8_pack: q_mu and q_sigma must be two int8 tensors of one shape, [Co, Ci, kh, kw] or [Out, In]")
+    Co, Ci = q_mu.shape[0], q_mu.shape[1]
+    taps = math.prod(q_mu.shape[2:])
+    Ci16 = (Ci + 15) // 16 * 16
+    mp = torch.empty((Co, taps, Ci16), dtype=torch.int8, device=q_mu.device)
+    sp = torch.empty_like(mp)
+    with _lib.on(q_mu.device):
+        _lib.check(_lib.lib().bt_q8_pack(q_mu.data_ptr(), q_sigma.data_ptr(), Co, Ci, taps, mp.data_ptr(), sp.data_ptr(), _lib.stream_ptr(q_mu.device)))
+    return mp, sp
+
+
+def q8_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, *, conv=None, S=1, shared_x=True, eps_w=None, eps_b=None,
+               seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False):
+    """The INT8 fused forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd; the arithmetic is include/bt_hip.h's). x: fp32 [B, Ci, H, W]
+    (conv: dict(stride, padding, dilation, groups)) or [B, In] (conv None); packs: q8_pack's; wshape: the weight's natural shape;
+    pairs: five (scale, zero point) -- eps, mul, add, in, out; eps_w [S, *wshape] and eps_b [S, Co] supplied, or None for the on-chip
+    streams. -> (out fp32 [S * B, Co, ...], the u8 image or None)."""
+    x = _lib.dev_f32(x, "input")
+    mu_b, sigma_b = _lib.dev_f32(mu_b, "mu_b"), _lib.dev_f32(sigma_b, "sigma_b")
+    eps_w, eps_b = _lib.dev_f32(eps_w, "eps_w"), _lib.dev_f32(eps_b, "eps_b")
+    mp, sp = _dev_i8(packs[0], "mu_packed"), _dev_i8(packs[1], "sigma_packed")
+    wshape = tuple(int(v) for v in wshape)
+    n = math.prod(wshape)
+    if eps_w is not None and eps_w.numel() != S * n:
+        raise RuntimeError(f"q8_forward: eps_w holds {eps_w.numel()} elements, S={S} samples of {n} weights need {S * n}")
+    if eps_b is not None and eps_b.numel() != S * wshape[0]:
+        raise RuntimeError(f"q8_forward: eps_b must be [S={S}, {wshape[0]}]")
+    dev = x.device
+    B, geom, x_elems, tail = _geometry(x, _Shape(wshape), conv, S, shared_x)
+    out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev)
+    out_q = torch.empty((S * B,) + tail, dtype=torch.uint8, device=dev) if want_q else None
+    pr = [_lib.bt_q8_pair(float(s), int(z), 0) for s, z in pairs]
+    P = _lib.bt_q8_params(pr[0], pr[1], pr[2], pr[3], pr[4], float(s_mu), float(s_sigma), mp.data_ptr(), sp.data_ptr(), _lib.ptr(mu_b), _lib.ptr(sigma_b))
+    Rg = _rng(seed, call, layer_id, sample0, call_base)
+    tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), _lib.ptr(eps_w), _lib.ptr(eps_b), C.byref(Rg), out.data_ptr(), _lib.ptr(out_q),
+                 _lib.stream_ptr(dev))
+    with _lib.on(dev):
+        if conv is None:
+            _lib.check(_lib.lib().bt_q8_linear_fwd(B, wshape[1], wshape[0], S, *tail_args))
+        else:
+            _lib.check(_lib.lib().bt_q8_conv2d_fwd(C.byref(geom), S, *tail_args))
+    return out, out_q

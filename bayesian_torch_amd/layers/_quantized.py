@@ -1,0 +1,291 @@
+"""INT8 post-training-quantised Reparameterization layers -- ``QuantizedLinearReparameterization`` and
+``QuantizedConv2dReparameterization`` of the reference (layers/variational_layers/quantize_linear_variational.py:44-224,
+quantize_conv_variational.py:303-552) on the fused int8 MFMA forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd, csrc/bt_q8.hip).
+
+The reference's forward is a chain of ``torch.ops.quantized.*`` calls, which exist on the CPU only. Here the chain -- quantise eps,
+quantised mul and add (the sampled int8 weight), quantise x, the int8 contraction, requantise -- is ONE launch for all S Monte-Carlo
+samples, and the result is the reference's bit for bit: integer accumulation has no order (tests/_q8_model.py
+is the arithmetic in plain torch).
+
+``quantize()`` is plain torch on the parameters' device (it also runs on CPU tensors); the forward needs a HIP device. Storage after
+``quantize()``: int8 buffers ``quantized_mu_weight`` / ``quantized_sigma_weight`` with their scales as buffers
+(``quantized_mu_scale`` / ``quantized_sigma_scale``), and the fp32 ``quantized_mu_bias`` / ``quantized_sigma_bias`` (the reference
+does not quantise the bias either). ROCm tensors have no quantised dtype: ``get_quantized_tensor`` returns ``(int8 tensor, scale)``.
+
+Deviations from the reference: the conv layer returns the DEQUANTISED fp32 output where the reference returns a quint8 tensor (the
+Linear layer dequantises there too); ``_last["out_q"]`` holds the u8 image when ``want_q`` is set. ``enable_int8_compute=False`` (the
+reference's deprecated dequantise-and-run-fp32 branch) raises NotImplementedError -- with the reference's precedence: a layer that has a
+``quant_dict`` takes the calibrated int8 branch whatever ``enable_int8_compute`` says, there and here -- and so does ``prepare()``: a ``quant_dict`` is
+supplied by the caller as a list of five ``{'scale', 'zero_point'}`` entries (eps, mul, add, in, out). The layers are not
+``FusedBayesLayer``s: ``fuse.py`` leaves them alone, and their KL is 0 as in the reference.
+"""
+import torch
+
+from .. import _lib, rng
+from .. import functional as F
+from ._fused import FusedBayesLayer
+from .base_variational_layer import BaseVariationalLayer_, get_kernel_size
+
+
+def _softplus(rho):
+    return torch.log1p(torch.exp(rho))       # the reference's two fp32 operations (their last bit follows the host's exp / log1p)
+
+
+def _sqrt(t):
+    """The IEEE (correctly rounded) fp32 square root: taken in double and rounded once. torch's CPU fp32 sqrt is not correctly rounded
+    on every host: one ulp in one BatchNorm coefficient moved a folded layer's scale between two machines."""
+    return torch.sqrt(t.double()).to(t.dtype)
+
+
+class _QuantizedLayer(BaseVariationalLayer_):
+    _kl_muted = True       # the KL of a quantised layer is 0: an mc_samples context collects nothing from it
+    _rng_layer = True      # rng.assign_layer_ids numbers it with the other Bayesian layers
+    _mc_frame = FusedBayesLayer._mc_frame
+    _call_coords = FusedBayesLayer._call_coords
+    _take_injected = FusedBayesLayer._take_injected
+
+    def _init_common(self, wshape, bias):
+        self._wshape = tuple(wshape)
+        self.bias = bias
+        self.quant_prepare = False
+        self.is_dequant = False
+        self.quant_dict = None
+        self.register_buffer("quantized_mu_weight", torch.zeros(self._wshape, dtype=torch.int8))
+        self.register_buffer("quantized_sigma_weight", torch.zeros(self._wshape, dtype=torch.int8))
+        self.register_buffer("quantized_mu_scale", torch.full((1,), 0.1))
+        self.register_buffer("quantized_sigma_scale", torch.full((1,), 0.1))
+        self.register_buffer("quantized_mu_bias", None)        # fp32 [Co] once quantize() gives the layer a bias
+        self.register_buffer("quantized_sigma_bias", None)     # (None beside a mu: a bias that came from BatchNorm folding)
+        self._layer_id = rng.new_layer_id()
+        self._last = None
+        self._cache = None         # (key, s_mu, s_sigma, packs): the scales as Python floats and the [Co][taps][Ci16] packs
+        self.inject_draw = None    # test hook: dict(eps_w [S, *wshape], eps_b [S, Co] or None) consumed instead of a fresh draw (or a list)
+        self.want_q = False        # keep the u8 output image of every forward in _last["out_q"]
+
+    # ------------------------------------------------------------------ conversion
+    def get_scale_and_zero_point(self, x, upper_bound=100, target_range=255):
+        """Per-tensor symmetric quantiser of x: scale = clamp(max|x|, 0, upper_bound) * 2 / target_range, zero point 0 (tensors)."""
+        zero_point = torch.zeros(1).to(x.device)
+        xmax = torch.clamp(x.abs().max(), 0, upper_bound)
+        return xmax * 2 / target_range, zero_point
+
+    def get_quantized_tensor(self, x, default_scale=0.1):
+        """-> (the int8 image of x, its scale as a 0-dim fp32 tensor); a zero scale is replaced by ``default_scale``."""
+        scale, _ = self.get_scale_and_zero_point(x.detach())
+        scale = scale.to(torch.float32)
+        if scale == 0:
+            scale = torch.tensor(default_scale, dtype=torch.float32, device=x.device)
+        inv = torch.ones((), dtype=torch.float32, device=x.device) / scale      # quantize_per_tensor multiplies by the fp32 reciprocal
+        q = torch.clamp(torch.round(x.detach().to(torch.float32) * inv), -128, 127).to(torch.int8)
+        return q, scale
+
+    def _store(self, mu_w, sigma_w, mu_b, sigma_b):
+        """What quantize() leaves behind: the int8 images and scales of the two weight tensors, the fp32 bias tensors."""
+        q, s = self.get_quantized_tensor(mu_w)
+        self.quantized_mu_weight, self.quantized_mu_scale = q, s.reshape(1)
+        q, s = self.get_quantized_tensor(sigma_w)
+        self.quantized_sigma_weight, self.quantized_sigma_scale = q, s.reshape(1)
+        self.quantized_mu_bias = None if mu_b is None else mu_b.detach().to(torch.float32).clone()
+        self.quantized_sigma_bias = None if sigma_b is None else sigma_b.detach().to(torch.float32).clone()
+        self._cache = None
+
+    def _source(self, src):
+        """The float layer quantize() reads: the argument, or what the converter left in ``_float`` (the reference copies the float
+        layer's __dict__ into the new one; here the parameters are read from the float layer and never registered)."""
+        src = self.__dict__.pop("_float", None) if src is None else src
+        if src is None:
+            raise RuntimeError(f"{type(self).__name__}.quantize(): no float layer to convert (use bnn_to_qbnn, or pass the layer)")
+        return src
+
+    def prepare(self):
+        raise NotImplementedError("the observer / calibration pipeline (QuantStub observers) is not part of this package: supply quant_dict, "
+                                  "a list of five {'scale', 'zero_point'} entries (eps, mul, add, in, out)")
+
+    def dequantize(self):
+        raise NotImplementedError("the dequantise-and-run-fp32 branch of the reference is deprecated there and not implemented here")
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        self._cache = None
+        for name in ("quantized_mu_bias", "quantized_sigma_bias"):      # a bias exists exactly when the checkpoint has one
+            t = state_dict.get(prefix + name)
+            setattr(self, name, None if t is None else torch.empty_like(t, device=self.quantized_mu_weight.device))
+        self.bias = self.quantized_mu_bias is not None
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._cache = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_cache"] = None
+        return d
+
+    # ------------------------------------------------------------------ forward
+    def kl_loss(self):
+        """0: the reference disables the KL of its quantised layers (their forward returns the literal 0)."""
+        return torch.zeros((), dtype=torch.float32, device=self.quantized_mu_weight.device)
+
+    def _frozen(self):
+        """-> (s_mu, s_sigma as Python floats, the packs). Read once per conversion / load / move (it synchronises), never inside a
+        graph capture: a captured step runs its warm-up first."""
+        qm, qs = self.quantized_mu_weight, self.quantized_sigma_weight
+        key = (qm.data_ptr(), qs.data_ptr(), qm.device)
+        if self._cache is None or self._cache[0] != key:
+            if qm.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}: converted, loaded or moved since the last eager call; run one forward outside the capture")
+            packs = F.q8_pack(qm, qs)
+            self._cache = (key, float(self.quantized_mu_scale.item()), float(self.quantized_sigma_scale.item()), packs)
+        return self._cache[1:]
+
+    def _pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
+        """The five (scale, zero point) pairs of this call: eps, mul, add, in, out."""
+        if self.quant_dict is not None:
+            if len(self.quant_dict) != 5:
+                raise ValueError("quant_dict must hold five {'scale', 'zero_point'} entries: eps, mul, add, in, out")
+            return [(float(d["scale"]), int(d["zero_point"])) for d in self.quant_dict]
+        s_mul = s_sigma * float(normal_scale)
+        return [(float(normal_scale), 0), (s_mul, 0), (max(s_mul, s_mu), 0), (float(default_scale), int(default_zero_point)),
+                (float(default_scale), int(default_zero_point))]
+
+    def _conv(self):
+        return None
+
+    def _q8_forward(self, x, enable_int8_compute, normal_scale, default_scale, default_zero_point, return_kl):
+        if not enable_int8_compute and self.quant_dict is None:
+            raise NotImplementedError("enable_int8_compute=False (dequantise and run in fp32) is deprecated in the reference and not implemented here")
+        ctx, _, _, return_kl = self._mc_frame(return_kl)
+        x = _lib.dev_f32(x, "input")
+        conv = self._conv()
+        lead = None
+        if conv is None:
+            if x.shape[-1] != self._wshape[1]:
+                raise RuntimeError(f"{type(self).__name__}: expected last dim {self._wshape[1]}, got {tuple(x.shape)}")
+            if x.dim() != 2:
+                if ctx is not None:
+                    raise RuntimeError("MC batching needs [N, features] inputs for Linear layers")
+                lead = tuple(x.shape[:-1])
+                x = x.reshape(-1, self._wshape[1])
+        elif x.dim() != 4 or x.shape[1] != self._wshape[1]:
+            raise RuntimeError(f"{type(self).__name__}: expected [N, {self._wshape[1]}, H, W], got {tuple(x.shape)}")
+        if x.shape[0] == 0:
+            raise RuntimeError("empty batch")
+        s_mu, s_sigma, packs = self._frozen()
+        pairs = self._pairs(s_mu, s_sigma, normal_scale, default_scale, default_zero_point)
+        S, shared, coords = self._call_coords(ctx, x.shape[0])
+        mu_b, sigma_b = self.quantized_mu_bias, self.quantized_sigma_bias
+        inj = self._take_injected()
+        eps_w = eps_b = None
+        if inj is not None:
+            eps_w = inj["eps_w"]
+            eps_b = inj.get("eps_b")
+            if eps_w.shape[0] != S:
+                raise RuntimeError(f"inject_draw holds {eps_w.shape[0]} samples, this call computes {S}")
+        elif rng.get_mode() == "torch":          # eps_w then eps_b per sample: the reference's draw order
+            eps_w = torch.empty((S,) + self._wshape, device=x.device)
+            eps_b = torch.empty((S, self._wshape[0]), device=x.device) if (mu_b is not None and sigma_b is not None) else None
+            for s in range(S):
+                eps_w[s].normal_()
+                if eps_b is not None:
+                    eps_b[s].normal_()
+        out, out_q = F.q8_forward(x, packs, self._wshape, s_mu, s_sigma, pairs, mu_b, sigma_b, conv=conv, S=S, shared_x=shared, eps_w=eps_w, eps_b=eps_b,
+                                  seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
+                                  want_q=self.want_q)
+        self._last = dict(draw=None if eps_w is None else dict(eps_w=eps_w, eps_b=eps_b), rng=coords, S=S, shared_x=shared, pairs=pairs, out_q=out_q,
+                          kernel=_lib.lib().bt_last_kernel_name().decode())
+        if lead is not None:
+            out = out.reshape(lead + (self._wshape[0],))
+        return (out, 0) if return_kl else out
+
+    def materialize_last_draw(self):
+        """The draw the last forward used: ``eps_w`` [S, *weight shape] and ``eps_b`` [S, Co] (None without a sampled bias) -- the
+        tensors that were read, or, after an on-chip draw, the streams regenerated from the call's coordinates (bt_rng_normal_fill,
+        tensors 0 and 1)."""
+        if self._last is None:
+            raise RuntimeError("no forward has run yet")
+        st = self._last
+        if st["draw"] is not None:
+            return dict(st["draw"])
+        if st["rng"].call_base is not None:
+            raise RuntimeError("draws made under a graph call_base cannot be replayed after the word advanced")
+        seed, call_base, call, lid, sample0 = st["rng"]
+        dev = self.quantized_mu_weight.device
+        eps_w = F.rng_fill_normal(seed, call, lid, sample0, 0, st["S"], self._wshape, dev)
+        eps_b = None
+        if self.quantized_mu_bias is not None and self.quantized_sigma_bias is not None:
+            eps_b = F.rng_fill_normal(seed, call, lid, sample0, 1, st["S"], (self._wshape[0],), dev)
+        return dict(eps_w=eps_w, eps_b=eps_b)
+
+
+class QuantizedLinearReparameterization(_QuantizedLayer):
+    """Drop-in for reference ``quantize_linear_variational.py:44-224``. Build it with ``bnn_to_qbnn``."""
+
+    def __init__(self, in_features, out_features):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self._init_common((out_features, in_features), True)
+
+    def quantize(self, src=None):
+        """Take over the parameters of ``src`` (a LinearReparameterization; default: the layer ``bnn_to_qbnn`` attached): int8 images of
+        mu and log1p(exp(rho)), fp32 bias."""
+        src = self._source(src)
+        has_b = src.mu_bias is not None
+        self.bias = has_b
+        self._store(src.mu_weight, _softplus(src.rho_weight.detach()), src.mu_bias if has_b else None, _softplus(src.rho_bias.detach()) if has_b else None)
+
+    def forward(self, input, enable_int8_compute=True, normal_scale=6 / 255, default_scale=0.2, default_zero_point=128, return_kl=True):
+        return self._q8_forward(input, enable_int8_compute, normal_scale, default_scale, default_zero_point, return_kl)
+
+
+class QuantizedConv2dReparameterization(_QuantizedLayer):
+    """Drop-in for reference ``quantize_conv_variational.py:303-552``; returns the dequantised fp32 output (the reference: a quint8
+    tensor). ``bn_*``: set by ``batch_norm_folding`` before ``quantize()`` folds the BatchNorm into the int8 images and the bias."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=False):
+        super().__init__()
+        if in_channels % groups != 0 or out_channels % groups != 0:
+            raise ValueError('invalid in_channels size')
+        if groups != 1:
+            raise NotImplementedError(f"{type(self).__name__}: groups must be 1 on the INT8 forward, got {groups}")
+        self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
+        self.stride, self.padding, self.dilation, self.groups = stride, padding, dilation, groups
+        self.bn_weight = self.bn_bias = self.bn_running_mean = self.bn_running_var = self.bn_eps = None
+        kh, kw = get_kernel_size(kernel_size, 2)
+        self._init_common((out_channels, in_channels, kh, kw), bias)
+
+    def _conv(self):
+        two = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        if isinstance(self.padding, str):
+            raise NotImplementedError("string padding modes are not supported")
+        return dict(stride=two(self.stride), padding=two(self.padding), dilation=two(self.dilation), groups=1)
+
+    def quantize(self, src=None):
+        """Take over the parameters of ``src`` (a Conv2dReparameterization; default: the layer ``bnn_to_qbnn`` attached), folding the
+        BatchNorm given in ``bn_*`` if there is one: the expressions of quantize_conv_variational.py:405-435 in their order, with one
+        difference -- the square root of ``running_var + eps`` is the IEEE (correctly rounded) fp32 value (``_sqrt``), where the
+        reference takes whatever the host's fp32 ``torch.sqrt`` gives."""
+        src = self._source(src)
+        mu, sigma = src.mu_kernel.detach(), _softplus(src.rho_kernel.detach())
+        has_b = src.mu_bias is not None
+        mu_b = sigma_b = None
+        if self.bn_weight is None:
+            if has_b:
+                mu_b, sigma_b = src.mu_bias.detach(), _softplus(src.rho_bias.detach())
+        else:
+            bn_coef = self.bn_weight.detach() / _sqrt(self.bn_running_var + self.bn_eps)
+            mu = mu * (bn_coef.view(-1, 1, 1, 1).expand(mu.shape))
+            sigma = sigma * (bn_coef.view(-1, 1, 1, 1).expand(sigma.shape))
+            if has_b:
+                mu_b = (src.mu_bias.detach() - self.bn_running_mean) * bn_coef + self.bn_bias.detach()
+                sigma_b = _softplus(src.rho_bias.detach()) * bn_coef
+            else:
+                mu_b = self.bn_weight.detach() / _sqrt(self.bn_running_var + self.bn_eps) * (-self.bn_running_mean) + self.bn_bias.detach()
+        self.bias = mu_b is not None
+        self._store(mu, sigma, mu_b, sigma_b)
+        self.bn_weight = self.bn_bias = self.bn_running_mean = self.bn_running_var = self.bn_eps = None
+
+    def forward(self, input, enable_int8_compute=True, normal_scale=6 / 255, default_scale=0.1, default_zero_point=128, return_kl=True):
+        return self._q8_forward(input, enable_int8_compute, normal_scale, default_scale, default_zero_point, return_kl)
+
+
+__all__ = ["QuantizedLinearReparameterization", "QuantizedConv2dReparameterization"]

@@ -502,6 +502,50 @@ int bt_avu_fwd(int32_t S, int32_t B, int32_t C, const float *logits, const int64
 int bt_avu_bwd(int32_t S, int32_t B, int32_t C, const float *logits, int32_t unc_type, int32_t T, const float *coef,
                const float *grad_loss, const void *workspace, size_t workspace_bytes, float *dlogits, bt_stream_t stream);
 
+/* INT8 post-training-quantised Reparameterization layers (layers/variational_layers/quantize_linear_variational.py:115-224,
+ * quantize_conv_variational.py:405-552) on v_mfma_i32_32x32x32_i8: one fused forward, bit for bit what torch's CPU quantised
+ * operators give (integer accumulation has no order). With `1 / s` the fp32 reciprocal of the fp32 scale, every multiplication and
+ * addition ONE fp32 rounding, rne = round to nearest even, and products / quotients of scales taken in double and rounded once:
+ *   e   = clamp(rne(eps * (1 / s_eps)), -128, 127)
+ *   p   = clamp(rne(float(q_sigma * e) * float(s_sigma * s_eps / s_mul)), -128, 127)
+ *   w   = clamp(rne((float(p) * s_mul + float(q_mu) * s_mu) * (1 / s_add)), -128, 127)          the sampled int8 weight, never in HBM
+ *   xq  = clamp(rne(x * (1 / s_in)) + z_in, 0, 255)                                             x is quantised where it is fetched
+ *   acc = sum_k (xq - z_in) * w                                                                 int32; padding contributes 0
+ *   b   = mu_b + sigma_b * eps_b          (mu_b NULL: no bias; sigma_b NULL: b = mu_b, a bias that came from BatchNorm folding)
+ *   oq  = clamp(rne(float(acc) * float(s_in * s_add / s_out) + b * (1 / s_out)) + z_out, 0, 255)
+ *   out = float(oq - z_out) * s_out
+ * The MFMA is signed x signed: the kernel feeds xq - 128 (padding: z_in - 128) and adds (128 - z_in) * sum_k w[s][co][k].
+ * A (scale, zero point) pair; the five of a forward are the reference's eps, mul, add, in and out quantisers. */
+typedef struct bt_q8_pair {
+  double scale;       /* what q_scale() returns in the reference: a double */
+  int32_t zero_point;
+  int32_t reserved;
+} bt_q8_pair;
+typedef struct bt_q8_params {
+  bt_q8_pair eps, mul, add, in, out;
+  double s_mu, s_sigma;                   /* the scales of the two int8 parameter images */
+  const int8_t *mu_packed, *sigma_packed; /* [Co][taps][Ci16] int8 (bt_q8_pack), Ci16 = Ci rounded up to a multiple of 16, padding 0 */
+  const float *mu_b, *sigma_b;            /* fp32 [Co]; mu_b NULL: no bias (sigma_b is then ignored); sigma_b NULL: b = mu_b */
+} bt_q8_params;
+/* packed[(co * taps + t) * Ci16 + c] = natural[co][c][t] for both tensors (c >= Ci: 0). Once per conversion: the quantised
+ * parameters are frozen. */
+int bt_q8_pack(const int8_t *q_mu, const int8_t *q_sigma, int64_t Co, int64_t Ci, int64_t taps, int8_t *mu_packed, int8_t *sigma_packed,
+               bt_stream_t stream);
+/* The forward. x: fp32 [B][Ci][H][W] (sample s reads x + s * x_sample_stride; 0: one x for all samples). Draws: eps_w fp32
+ * [S][Co][Ci][taps] (the weight's natural order) and eps_b [S][Co] are read, or eps_w NULL: both come from rng -- tensor 0 with
+ * bt_rng_normal_fill's index rule e = (co * taps + t) * inner4 + c, tensor 1 for the bias, sample rng->sample0 + s -- so a launch fed
+ * bt_rng_normal_fill's output gives the same bytes. out: fp32 [S][B][Co][Ho][Wo]; out_q: the u8 image oq in the same layout, or NULL.
+ * BT_ERR_BAD_ARG before any launch: a null x / p / out / pack, a pack that is not 16-byte aligned, eps_w without eps_b when the bias
+ * has a sigma, neither eps_w nor rng, a scale <= 0, an in or out zero point outside 0..255, an empty output. BT_ERR_UNSUPPORTED, nothing
+ * launched: groups != 1, a nonzero eps, mul or add zero point, Ci * taps * 32640 >= 2^31 (the int32 accumulator's bound), S > 65535,
+ * 2^31 or more output pixels, 2^40 or more elements of one sample's x, Co * taps * ceil(Ci / 4) > 2^32 (the draw stream's block index),
+ * Co > 65535 * 64. */
+int bt_q8_conv2d_fwd(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t x_sample_stride, const bt_q8_params *p,
+                     const float *eps_w, const float *eps_b, const bt_rng *rng, float *out, uint8_t *out_q, bt_stream_t stream);
+/* Linear as the 1 x 1 map: x [B][In], out [S][B][Out], eps_w [S][Out][In]. */
+int bt_q8_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, const float *x, int64_t x_sample_stride, const bt_q8_params *p,
+                     const float *eps_w, const float *eps_b, const bt_rng *rng, float *out, uint8_t *out_q, bt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,156 @@
+"""What the q8 host and GPU tests share: the golden fixtures of tools/make_q8_goldens.py (tests/golden/q8_*.npz), rebuilt into float
+layers of this package, and the model's answer (tests/_q8_model.py) for a layer, an input and a draw."""
+import glob
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+import _q8_model as M
+from conftest import GOLD
+
+GOLDENS = sorted(os.path.basename(p)[3:-4] for p in glob.glob(os.path.join(GOLD, "q8_*.npz")))
+EXPECTED_GOLDENS = ["conv_c19x10k3s2p1_z0", "conv_c5x7k3p1", "conv_c6x5k3d2p2_z57", "conv_c8x12k3p1_bn", "conv_c8x12k3p1_bnb_z57", "linear_33x10_z0", "linear_70x9"]
+
+
+def load(tag):
+    g = np.load(os.path.join(GOLD, f"q8_{tag}.npz"))
+    return {k: (torch.from_numpy(g[k]) if g[k].ndim else g[k].item()) for k in g.files}
+
+
+def pairs_of(g):
+    return [(float(s), int(z)) for s, z in zip(g["pair_scales"].tolist(), g["pair_zeros"].tolist())]
+
+
+def conv_of(tag):
+    """The conv descriptor a golden's tag spells (None: Linear)."""
+    if tag.startswith("linear"):
+        return None
+    num = lambda key, default: next((int(p[len(key):]) for p in _parts(tag) if p.startswith(key) and p[len(key):].isdigit()), default)
+    return dict(stride=(num("s", 1),) * 2, padding=(num("p", 0),) * 2, dilation=(num("d", 1),) * 2, groups=1)
+
+
+def _parts(tag):
+    """'conv_c6x5k3d2p2_z57' -> ['k3', 'd2', 'p2'] (the geometry letters behind the channel counts)."""
+    body = tag.split("_")[1]
+    body = body[body.index("k"):]
+    out, cur = [], ""
+    for ch in body:
+        if ch.isalpha() and cur:
+            out.append(cur)
+            cur = ""
+        cur += ch
+    return out + [cur]
+
+
+def float_layer(tag, g):
+    """The golden's float layer (and its BatchNorm or None) rebuilt from the recorded parameters, on the CPU."""
+    import bayesian_torch_amd.layers as L
+    has_b = "mu_b" in g
+    if tag.startswith("linear"):
+        out_f, in_f = g["mu_w"].shape
+        d = L.LinearReparameterization(in_f, out_f, bias=has_b)
+        names = ("mu_weight", "rho_weight")
+    else:
+        Co, Ci, k, _ = g["mu_w"].shape
+        c = conv_of(tag)
+        d = L.Conv2dReparameterization(Ci, Co, k, stride=c["stride"][0], padding=c["padding"][0], dilation=c["dilation"][0], bias=has_b)
+        names = ("mu_kernel", "rho_kernel")
+    with torch.no_grad():
+        getattr(d, names[0]).copy_(g["mu_w"]), getattr(d, names[1]).copy_(g["rho_w"])
+        if has_b:
+            d.mu_bias.copy_(g["mu_b"]), d.rho_bias.copy_(g["rho_b"])
+    bn = None
+    if "bn_weight" in g:
+        bn = nn.BatchNorm2d(g["mu_w"].shape[0], eps=float(g["bn_eps"]))
+        with torch.no_grad():
+            bn.weight.copy_(g["bn_weight"]), bn.bias.copy_(g["bn_bias"]), bn.running_mean.copy_(g["bn_mean"]), bn.running_var.copy_(g["bn_var"])
+        bn.eval()
+    return d, bn
+
+
+def converted(tag, g):
+    """The golden's layer converted by this package's bnn_to_qbnn machinery (on the CPU), with the golden's quant_dict installed."""
+    from bayesian_torch_amd.models import bnn_to_qbnn as Q
+    d, bn = float_layer(tag, g)
+    q = Q.batch_norm_folding(d, bn) if bn is not None else (Q.qbnn_linear_layer(d) if tag.startswith("linear") else Q.qbnn_conv_layer(d))
+    if "_z" in tag:               # the tags of the calibrated-branch fixtures name their input zero point
+        q.quant_dict = [dict(scale=s, zero_point=z) for s, z in pairs_of(g)]
+    return q
+
+
+def model_of_layer(q, x, eps_w, eps_b, pairs, conv):
+    """The model's (u8 image, fp32 output) of a converted layer ``q`` for ONE sample's draw, on the CPU."""
+    cpu = lambda t: None if t is None else t.detach().cpu()
+    return M.forward(cpu(x), cpu(q.quantized_mu_weight), cpu(q.quantized_sigma_weight), float(q.quantized_mu_scale.item()), float(q.quantized_sigma_scale.item()),
+                     pairs, cpu(eps_w), cpu(q.quantized_mu_bias), cpu(q.quantized_sigma_bias), cpu(eps_b), conv)
+
+
+def from_golden(tag, g):
+    """A quantised layer holding the golden's RECORDED int8 images, scales and fp32 bias tensors (a checkpoint load: nothing is
+    converted on this host), with the golden's quant_dict installed."""
+    import bayesian_torch_amd.layers as L
+    if tag.startswith("linear"):
+        q = L.QuantizedLinearReparameterization(g["q_mu"].shape[1], g["q_mu"].shape[0])
+    else:
+        c = conv_of(tag)
+        q = L.QuantizedConv2dReparameterization(g["q_mu"].shape[1], g["q_mu"].shape[0], g["q_mu"].shape[2], c["stride"][0], c["padding"][0], c["dilation"][0])
+    sd = dict(quantized_mu_weight=g["q_mu"], quantized_sigma_weight=g["q_sigma"], quantized_mu_scale=torch.tensor([g["s_mu"]], dtype=torch.float32),
+              quantized_sigma_scale=torch.tensor([g["s_sigma"]], dtype=torch.float32))
+    for name, key in (("quantized_mu_bias", "q_mu_b"), ("quantized_sigma_bias", "q_sigma_b")):
+        if key in g:
+            sd[name] = g[key]
+    q.load_state_dict(sd)
+    if "_z" in tag:
+        q.quant_dict = [dict(scale=s, zero_point=z) for s, z in pairs_of(g)]
+    return q
+
+
+# ---------------------------------------------------------------------------- the scales of the GPU tests' synthetic cases and model
+GPU_S_MU, GPU_S_SIGMA = 0.003, 0.0009                         # tests/test_gpu_q8.py: the int8 images' scales of its random cases ...
+GPU_PAIRS3 = [(0.0291, 0), (0.0011, 0), (0.0031, 0)]          # ... and their eps, mul, add pairs
+MODEL2_DICTS = [((0.0291, 0), (0.0009, 0), (0.004, 0), (0.04, 120), (0.03, 100)), ((0.0291, 0), (0.0009, 0), (0.004, 0), (0.03, 0), (0.05, 128))]
+
+
+def two_layer_model():
+    """The converted two-layer model of the mc_forward / McGraph test, on the CPU: conv 3 -> 6 (3x3, pad 1, bias) - ReLU - Flatten -
+    Linear 150 -> 4, seeded, each layer with its quant_dict."""
+    import bayesian_torch_amd.layers as L
+    from bayesian_torch_amd import rng
+    from bayesian_torch_amd.models.bnn_to_qbnn import bnn_to_qbnn
+    torch.manual_seed(21)
+    net = nn.Sequential(L.Conv2dReparameterization(3, 6, 3, padding=1, bias=True), nn.ReLU(), nn.Flatten(), L.LinearReparameterization(6 * 5 * 5, 4))
+    with torch.no_grad():
+        net[0].rho_kernel.fill_(-2.0), net[3].rho_weight.fill_(-2.0)
+    net[0].dnn_to_bnn_flag = net[3].dnn_to_bnn_flag = True      # (the layers return the output alone: nn.Sequential chains them)
+    rng.assign_layer_ids(net)
+    bnn_to_qbnn(net)
+    for layer, pairs in zip((net[0], net[3]), MODEL2_DICTS):
+        layer.quant_dict = [dict(scale=sc, zero_point=z) for sc, z in pairs]
+    return net.eval()
+
+
+def scale_sets():
+    """Every (s_mu, s_sigma, s_eps, s_mul, s_add) a fixture or a GPU case runs the weight chain at -> {name: set}: the seven goldens,
+    the GPU tests' synthetic cases, the two layers of the two-layer model."""
+    out = {}
+    for tag in EXPECTED_GOLDENS:
+        g = load(tag)
+        ps = g["pair_scales"].tolist()
+        out["golden " + tag] = (g["s_mu"], g["s_sigma"], ps[0], ps[1], ps[2])
+    out["gpu cases"] = (GPU_S_MU, GPU_S_SIGMA) + tuple(p[0] for p in GPU_PAIRS3)
+    net = two_layer_model()
+    for i, layer in ((0, net[0]), (3, net[3])):
+        ps = [float(d["scale"]) for d in layer.quant_dict]
+        out[f"two-layer model [{i}]"] = (float(layer.quantized_mu_scale.item()), float(layer.quantized_sigma_scale.item()), ps[0], ps[1], ps[2])
+    return out
+
+
+GPU_S_IN = 0.0437                                              # tests/test_gpu_q8.py: the input scale of its random cases, at z_in 128, 0 and 57
+
+
+def in_sets():
+    """Every input (scale, zero point) pair a fixture or a GPU case quantises x at."""
+    out = {pairs_of(load(tag))[3] for tag in EXPECTED_GOLDENS} | {(GPU_S_IN, z) for z in (128, 0, 57)} | {d[3] for d in MODEL2_DICTS}
+    return sorted(out)

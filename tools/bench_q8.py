@@ -1,0 +1,125 @@
+"""INT8 quantised ResNet18 against the float Bayesian ResNet18 it was converted from: ``mc_forward`` rates in one process -- DESIGN.md 4.6f.
+
+Models (bench.py's cfg3: the harness ResNet18 via dnn_to_bnn, CIFAR 3x32x32, batch 128, S = 32, eval mode, seeded parameters):
+  float         the converted model as dnn_to_bnn leaves it, on its default path (split-precision bf16x3 kernels; BatchNorm / ReLU / add
+                are torch modules);
+  float_fused   the same model after harness.fuse_inference (BatchNorm, ReLU and the residual add in the conv kernels' output stage):
+                the benchmark's flagship form, reported for scale;
+  int8          a copy converted by bnn_to_qbnn(fuse_conv_bn=True): every conv and the Linear run on the int8 MFMA forward
+                (bt_q8_conv2d_fwd / bt_q8_linear_fwd), BatchNorm folded into the int8 images, ReLU / add / max-pool as torch modules,
+                activations fp32 between layers.
+
+Protocol: WARMUP calls of each model, then the models ALTERNATE over windows of at least ``--window`` seconds (whole mc_forward calls, a
+synchronise at each end of a window), ``--repeats`` windows each; a rate is images x samples per second of one window. Printed: per
+model the median, min and max rate over the windows, then the kernel every Bayesian layer of the int8 and the float model ran, and each
+int8 layer's own time (HIP events around its launch, median of ``--n``) beside the float layer's.
+
+    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10]
+"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PRIOR = {"prior_mu": 0.0, "prior_sigma": 1.0, "posterior_mu_init": 0.0, "posterior_rho_init": -3.0, "type": "Reparameterization",
+         "moped_enable": False, "moped_delta": 0.5}
+
+
+def window(fn, seconds):
+    """Whole calls of fn for at least ``seconds`` -> (calls, elapsed seconds)."""
+    torch.cuda.synchronize()
+    t0, n = time.perf_counter(), 0
+    while True:
+        fn()
+        n += 1
+        if n % 2 == 0 or n == 1:
+            torch.cuda.synchronize()
+            if time.perf_counter() - t0 >= seconds:
+                break
+    torch.cuda.synchronize()
+    return n, time.perf_counter() - t0
+
+
+def layer_times(net, x, S, n):
+    """Per Bayesian layer: (name, kernel, median microseconds of the layer's own forward) from HIP events in forward hooks."""
+    from bayesian_torch_amd import mc
+    layers = [(nm, m) for nm, m in net.named_modules() if hasattr(m, "_last") and hasattr(m, "_layer_id")]
+    ev = {nm: [] for nm, _ in layers}
+    hooks = []
+    for nm, m in layers:
+        def pre(mod, inp, nm=nm):
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            ev[nm].append([e, None])
+
+        def post(mod, inp, out, nm=nm):
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            ev[nm][-1][1] = e
+        hooks += [m.register_forward_pre_hook(pre), m.register_forward_hook(post)]
+    for _ in range(n):
+        mc.mc_forward(net, x, S)
+    torch.cuda.synchronize()
+    for h in hooks:
+        h.remove()
+    return [(nm, m._last["kernel"], round(statistics.median(a.elapsed_time(b) * 1e3 for a, b in ev[nm]), 1)) for nm, m in layers]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=128)
+    ap.add_argument("--S", type=int, default=32)
+    ap.add_argument("--window", type=float, default=1.0)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--n", type=int, default=10)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_q8 needs a GPU: a CPU run measures nothing")
+    from bayesian_torch_amd import mc, rng
+    from bayesian_torch_amd.harness import resnet as H
+    from bayesian_torch_amd.models.bnn_to_qbnn import bnn_to_qbnn
+    from bayesian_torch_amd.models.dnn_to_bnn import dnn_to_bnn
+
+    rng.set_mode("philox")
+    torch.manual_seed(0)
+    net = H.resnet18(10, 64)
+    dnn_to_bnn(net, PRIOR)
+    with torch.no_grad():
+        H.fill_bayes_params(net, 1)
+    net = net.cuda().eval()
+    q = copy.deepcopy(net)
+    bnn_to_qbnn(q, fuse_conv_bn=True)
+    fused = H.fuse_inference(copy.deepcopy(net))
+    models = {"float": net, "float_fused": fused, "int8": q}
+    B, S = args.B, args.S
+    x = torch.randn(B, 3, 32, 32, device="cuda")
+    run = {k: (lambda m=m: mc.mc_forward(m, x, S, with_kl=False)) for k, m in models.items()}
+    with torch.no_grad():
+        for k in models:
+            for _ in range(args.warmup):
+                run[k]()
+        rates = {k: [] for k in models}
+        for _ in range(args.repeats):
+            for k in models:
+                n, dt = window(run[k], args.window)
+                rates[k].append(n * B * S / dt)
+        for k, r in rates.items():
+            print(json.dumps(dict(what="mc_forward", model=k, B=B, S=S, unit="image-samples/s", median=round(statistics.median(r)), min=round(min(r)), max=round(max(r)),
+                                  windows=len(r), window_s=args.window)), flush=True)
+        print(json.dumps(dict(what="ratio", int8_over_float=round(statistics.median(rates["int8"]) / statistics.median(rates["float"]), 3),
+                              int8_over_float_fused=round(statistics.median(rates["int8"]) / statistics.median(rates["float_fused"]), 3))), flush=True)
+        tq, tf = layer_times(q, x, S, args.n), layer_times(net, x, S, args.n)
+        for (nm, kq, uq), (nf, kf, uf) in zip(tq, tf):
+            print(json.dumps(dict(what="layer", layer=nm, int8_us=uq, float_us=uf, int8_kernel=kq, float_kernel=kf)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
