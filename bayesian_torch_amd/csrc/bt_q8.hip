@@ -51,7 +51,7 @@ struct Q8Args {
   int pruned;           // z_in == 128 and some tap reads padding for every output pixel: such a tap contributes 0 and is skipped
   uint64_t live_taps;   // pruned: the live taps in ascending order, four bits each (taps <= 16)
   long long npix;   // B * Ho * Wo
-  float inv_eps, m_mul, s_mul, s_mu, inv_add, inv_in, m_out, inv_out, s_out;
+  float inv_eps, m_mul, s_mul, s_mu, inv_add, inv_in, m_out, inv_atw, s_out;   // inv_atw: 1 / (s_in * s_add); m_out: s_in * s_add / s_out -- fp32 operations
   int z_in, z_out;
 };
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kQ8Threads) void q8_fwd_kernel(Q8Args a) {
   }
   const uint32_t sample = a.sample0 + (uint32_t)s;
 
-  // the bias of this sample's channels, already divided by the output scale: b * (1 / s_out)
+  // the bias of this sample's channels, b = mu_b + sigma_b * eps_b (0 without one): the output stage takes it into the accumulator's scale
   if (tid < kQ8TM) {
     const int co = co0 + tid;
     float bt = 0.f;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kQ8Threads) void q8_fwd_kernel(Q8Args a) {
         }
         b = __fadd_rn(b, __fmul_rn(a.sigma_b[co], eb));
       }
-      bt = __fmul_rn(b, a.inv_out);
+      bt = b;
     }
     bias_term[tid] = bt;
   }
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kQ8Threads) void q8_fwd_kernel(Q8Args a) {
       const int co = co0 + row;
       if (co >= a.Co) continue;
       const int acc = (blk ? acc1[i] : acc0[i]) + zc * row_sum[row];
-      const float t = __fadd_rn(__fmul_rn((float)acc, a.m_out), bias_term[row]);
+      const float t = __fmul_rn(__fmaf_rn(bias_term[row], a.inv_atw, (float)acc), a.m_out);   // fbgemm's: ONE rounding of b * (1 / a) + float(acc)
       const float oq = fminf(fmaxf(__fadd_rn(rintf(t), (float)a.z_out), 0.f), 255.f);
       const long long o = base + (long long)co * hw;
       a.out[o] = __fmul_rn(__fsub_rn(oq, (float)a.z_out), a.s_out);
@@ -378,8 +378,10 @@ static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const flo
   a.m_mul = (float)(p->s_sigma * p->eps.scale / p->mul.scale);
   a.s_mul = (float)p->mul.scale, a.s_mu = (float)p->s_mu;
   a.inv_add = 1.0f / s_add, a.inv_in = 1.0f / s_in;
-  a.m_out = (float)(p->in.scale * p->add.scale / p->out.scale);
-  a.inv_out = 1.0f / s_out, a.s_out = s_out;
+  const float atw = s_in * s_add;   // fbgemm's act_times_w_scale and output multiplier: fp32 operations on the fp32 scales
+  if (!(atw > 0.f) || !(atw / s_out > 0.f)) return fail(BT_ERR_BAD_ARG, "in scale * add scale (/ out scale) underflows fp32");
+  a.m_out = atw / s_out;
+  a.inv_atw = 1.0f / atw, a.s_out = s_out;
   a.z_in = p->in.zero_point, a.z_out = p->out.zero_point;
   const dim3 grid((unsigned)((npix + kQ8TN - 1) / kQ8TN), (unsigned)((g.Co + kQ8TM - 1) / kQ8TM), (unsigned)S);
   if (grid.y > 65535u) return fail(BT_ERR_UNSUPPORTED, "more than 65535 * 64 output channels");

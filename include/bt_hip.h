@@ -505,14 +505,16 @@ int bt_avu_bwd(int32_t S, int32_t B, int32_t C, const float *logits, int32_t unc
 /* INT8 post-training-quantised Reparameterization layers (layers/variational_layers/quantize_linear_variational.py:115-224,
  * quantize_conv_variational.py:405-552) on v_mfma_i32_32x32x32_i8: one fused forward, bit for bit what torch's CPU quantised
  * operators give (integer accumulation has no order). With `1 / s` the fp32 reciprocal of the fp32 scale, every multiplication and
- * addition ONE fp32 rounding, rne = round to nearest even, and products / quotients of scales taken in double and rounded once:
+ * addition ONE fp32 rounding (but for the one fma of the output stage), rne = round to nearest even, and the quotient of scales of the
+ * weight chain taken in double and rounded once; the output stage is fbgemm's, whose scales are rounded to fp32 FIRST:
  *   e   = clamp(rne(eps * (1 / s_eps)), -128, 127)
  *   p   = clamp(rne(float(q_sigma * e) * float(s_sigma * s_eps / s_mul)), -128, 127)
  *   w   = clamp(rne((float(p) * s_mul + float(q_mu) * s_mu) * (1 / s_add)), -128, 127)          the sampled int8 weight, never in HBM
  *   xq  = clamp(rne(x * (1 / s_in)) + z_in, 0, 255)                                             x is quantised where it is fetched
  *   acc = sum_k (xq - z_in) * w                                                                 int32; padding contributes 0
  *   b   = mu_b + sigma_b * eps_b          (mu_b NULL: no bias; sigma_b NULL: b = mu_b, a bias that came from BatchNorm folding)
- *   oq  = clamp(rne(float(acc) * float(s_in * s_add / s_out) + b * (1 / s_out)) + z_out, 0, 255)
+ *   a   = float(s_in) * float(s_add),  m = a / float(s_out)                                     fp32 operations
+ *   oq  = clamp(rne(fmaf(b, 1 / a, float(acc)) * m) + z_out, 0, 255)                            ONE rounding of b * (1 / a) + float(acc)
  *   out = float(oq - z_out) * s_out
  * The MFMA is signed x signed: the kernel feeds xq - 128 (padding: z_in - 128) and adds (128 - z_in) * sum_k w[s][co][k].
  * A (scale, zero point) pair; the five of a forward are the reference's eps, mul, add, in and out quantisers. */

@@ -110,6 +110,14 @@ def from_golden(tag, g):
 # ---------------------------------------------------------------------------- the scales of the GPU tests' synthetic cases and model
 GPU_S_MU, GPU_S_SIGMA = 0.003, 0.0009                         # tests/test_gpu_q8.py: the int8 images' scales of its random cases ...
 GPU_PAIRS3 = [(0.0291, 0), (0.0011, 0), (0.0031, 0)]          # ... and their eps, mul, add pairs
+# Scale sets whose roundings meet exact ties (the decimal sets above never do): all five scales powers of two, and a set whose
+# float(s_sigma * s_eps / s_mul) is exactly 0.5 with a dyadic eps scale and s_mu / s_add = 0.5
+TIE_SETS = {"dyadic 2^-k": (2.0 ** -8, 2.0 ** -10, 2.0 ** -5, 2.0 ** -12, 2.0 ** -7),
+            "dyadic eps, multipliers 0.5": (0.003, 0.0009, 0.03125, 2 * 0.0009 * 0.03125, 0.006),
+            # decimal scales in dyadic ratios (s_sigma * s_eps / s_mul = 1/8, s_mul / s_add = 1/2, s_mu = s_add): every pre-rounding value sits ON
+            # or one ulp beside a half step, so a fused sum or a division by the scale moves it across
+            "decimal, dyadic ratios": (0.003, 0.00625, 0.03, 0.0015, 0.003)}
+DYADIC_S_IN = 2.0 ** -4                                        # the input scale of the tie cases (tests/_q8_edges.py), at z_in 128, 0 and 57
 MODEL2_DICTS = [((0.0291, 0), (0.0009, 0), (0.004, 0), (0.04, 120), (0.03, 100)), ((0.0291, 0), (0.0009, 0), (0.004, 0), (0.03, 0), (0.05, 128))]
 
 
@@ -133,7 +141,7 @@ def two_layer_model():
 
 def scale_sets():
     """Every (s_mu, s_sigma, s_eps, s_mul, s_add) a fixture or a GPU case runs the weight chain at -> {name: set}: the seven goldens,
-    the GPU tests' synthetic cases, the two layers of the two-layer model."""
+    the GPU tests' synthetic cases, the two layers of the two-layer model, the two tie-producing sets (TIE_SETS)."""
     out = {}
     for tag in EXPECTED_GOLDENS:
         g = load(tag)
@@ -144,6 +152,7 @@ def scale_sets():
     for i, layer in ((0, net[0]), (3, net[3])):
         ps = [float(d["scale"]) for d in layer.quant_dict]
         out[f"two-layer model [{i}]"] = (float(layer.quantized_mu_scale.item()), float(layer.quantized_sigma_scale.item()), ps[0], ps[1], ps[2])
+    out.update(TIE_SETS)
     return out
 
 
@@ -152,5 +161,5 @@ GPU_S_IN = 0.0437                                              # tests/test_gpu_
 
 def in_sets():
     """Every input (scale, zero point) pair a fixture or a GPU case quantises x at."""
-    out = {pairs_of(load(tag))[3] for tag in EXPECTED_GOLDENS} | {(GPU_S_IN, z) for z in (128, 0, 57)} | {d[3] for d in MODEL2_DICTS}
+    out = {pairs_of(load(tag))[3] for tag in EXPECTED_GOLDENS} | {(GPU_S_IN, z) for z in (128, 0, 57)} | {d[3] for d in MODEL2_DICTS} | {(DYADIC_S_IN, z) for z in (128, 0, 57)}
     return sorted(out)

@@ -1,9 +1,11 @@
 """The arithmetic of the INT8 quantised Bayesian layers in plain torch: the oracle of the q8 tests.
 
-Every multiplication and addition below is ONE fp32 rounding (never fused); ``rne`` is round-to-nearest-even (torch.round); ``1 / s``
-is the fp32 reciprocal of the fp32 scale. A scale arrives as a Python float (a double, what ``q_scale()`` returns in the reference);
-products and quotients of scales are taken in double and rounded to fp32 once. tests/test_q8_model_host.py holds every step to
-torch's CPU quantised operators with exact equality.
+Every multiplication and addition below is ONE fp32 rounding, never fused -- except the ONE ``fma`` of the output stage, which is
+fbgemm's; ``rne`` is round-to-nearest-even (torch.round); ``1 / s`` is the fp32 reciprocal of the fp32 scale. A scale arrives as a
+Python float (a double, what ``q_scale()`` returns in the reference). In the weight chain the quotient of scales is taken in double
+and rounded to fp32 once (torch's quantized.mul); in the output stage the scales are rounded to fp32 FIRST and every operation on them
+is an fp32 one (fbgemm's conv and linear). tests/test_q8_model_host.py holds every step to torch's CPU quantised operators with exact
+equality, the output stage on exact and near ties where the two readings of either choice differ.
 
     e   = clamp(rne(eps * (1 / s_eps)), -128, 127)
     p   = clamp(rne(float(q_sigma * e) * float(s_sigma * s_eps / s_mul)), -128, 127)
@@ -11,7 +13,8 @@ torch's CPU quantised operators with exact equality.
     xq  = clamp(rne(x * (1 / s_in)) + z_in, 0, 255)
     acc = sum_k (xq - z_in) * w          int32, exact; padding contributes 0
     b   = mu_b + sigma_b * eps_b
-    oq  = clamp(rne(float(acc) * float(s_in * s_add / s_out) + b * (1 / s_out)) + z_out, 0, 255)
+    a   = f32(s_in) * f32(s_add)         (fp32), m = a / f32(s_out) (fp32)
+    oq  = clamp(rne(fma(b, 1 / a, float(acc)) * m) + z_out, 0, 255)         fma: b * (1 / a) + float(acc) rounded ONCE
     out = float(oq - z_out) * s_out
 """
 import torch
@@ -84,15 +87,28 @@ def bias_of(mu_b, sigma_b, eps_b):
     return mu_b.float() + sigma_b.float() * eps_b.float()
 
 
+def out_scales(s_in, s_add, s_out):
+    """-> (a, m) of the output stage as 0-dim fp32 tensors: a = f32(s_in) * f32(s_add) and m = a / f32(s_out), both fp32 operations."""
+    a = f32(s_in) * f32(s_add)
+    return a, a / f32(s_out)
+
+
+def fma32(x, y, z):
+    """fmaf(x, y, z) on fp32 tensors, in double: the product of two fp32 values is exact there, and its sum with z is rounded to 53 bits
+    before the one rounding to fp32 -- which differs from a true fmaf only where that 53-bit value falls exactly on the midpoint of two
+    fp32 values and the exact sum does not (some 2^-29 of all operands; torch has no fp32 fma on the CPU to take instead)."""
+    return (x.double() * y.double() + z.double()).to(torch.float32)
+
+
 def requant(acc, b, pairs):
     """int32 acc [N, Co, ...] and fp32 b [Co] (or None) -> the u8 output image."""
     (s_in, _), (s_out, z_out), s_add = pairs[3], pairs[4], pairs[2][0]
     dev = acc.device
-    m = f32(float(s_in) * float(s_add) / float(s_out)).to(dev)
-    t = acc.to(torch.float32) * m
+    a, m = out_scales(s_in, s_add, s_out)
+    t = acc.to(torch.float32)
     if b is not None:
-        t = t + (b.to(dev) * rcp32(s_out).to(dev)).view((1, -1) + (1,) * (acc.dim() - 2))
-    return torch.clamp(torch.round(t) + z_out, 0, 255).to(torch.uint8)
+        t = fma32(b.to(dev).view((1, -1) + (1,) * (acc.dim() - 2)), (torch.tensor(1.0) / a).to(dev), t)
+    return torch.clamp(torch.round(t * m.to(dev)) + z_out, 0, 255).to(torch.uint8)
 
 
 def dequant(oq, pairs):
