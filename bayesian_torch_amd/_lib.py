@@ -80,6 +80,12 @@ class bt_q8_params(C.Structure):
         + [(n, _vp) for n in ("mu_packed", "sigma_packed", "mu_b", "sigma_b")]
 
 
+class bt_minmax_seg(C.Structure):
+    _fields_ = [("x", _vp), ("n", C.c_int64), ("dst", _vp)]
+
+
+MINMAX_MAX_SEGS = 4    # BT_MINMAX_MAX_SEGS
+
 _lib = None
 _lock = threading.Lock()
 
@@ -136,6 +142,8 @@ _PROTOS = {
     "bt_q8_pack": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "bt_q8_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
     "bt_q8_linear_fwd": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_q8_observe_w": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_minmax_update": (C.c_int, [C.c_int32, C.POINTER(bt_minmax_seg), _vp, _vp]),
 }
 EXPORTS = tuple(_PROTOS)
 

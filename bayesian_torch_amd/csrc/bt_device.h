@@ -66,6 +66,22 @@ __device__ __forceinline__ void philox_normal4(const RngKey& k, uint32_t sample,
   box_muller(r[2], r[3], z[2], z[3]);
 }
 
+// The index rule of a weight tensor's eps stream (include/bt_hip.h): the stream is tap-major over rows of inner4 = inner rounded up to
+// four channels, so Philox block q holds the draws of channels c0 .. c0 + 3 of ONE (row r, tap t); channel c0 + j of natural element
+// (r * inner + c0 + j) * taps + t exists while c0 + j < inner. One definition, in both directions: bt_rng_normal_fill walks the blocks,
+// the observer sweep (bt_q8_observe.hip) walks the natural order.
+__device__ __forceinline__ void eps_block_coords(long long q, long long inner4, long long taps, long long& r, long long& t, long long& c0) {
+  const long long e = q * 4;
+  const long long rt = e / inner4;
+  c0 = e % inner4;
+  t = rt % taps;
+  r = rt / taps;
+}
+// The other way round: natural element (row r, channel c, tap t) is number e & 3 of block e >> 2.
+__device__ __forceinline__ long long eps_stream_index(long long r, long long c, long long t, long long inner4, long long taps) {
+  return (r * taps + t) * inner4 + c;
+}
+
 // Flipout signs: activation-sized streams, consumed once per im2col tap, so a full Philox per
 // element would cost more than the contraction it decorates. The per-(seed, call, layer, tensor,
 // sample) key is derived once per block with Philox; each element then takes one round of a

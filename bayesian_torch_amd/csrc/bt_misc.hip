@@ -47,9 +47,8 @@ __global__ __launch_bounds__(256) void rng_normal_fill_kernel(RngKey k, const ui
   for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
     float z[4];
     philox_normal4(k, sample0 + s, (uint32_t)q, z);
-    const long long e = q * 4;
-    const long long c0 = e % inner4, rt = e / inner4;
-    const long long t = rt % taps, r = rt / taps;
+    long long r, t, c0;
+    eps_block_coords(q, inner4, taps, r, t, c0);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (c0 + j < inner) out[(long long)s * n + (r * inner + c0 + j) * taps + t] = z[j];

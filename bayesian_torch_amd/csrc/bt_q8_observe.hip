@@ -1,0 +1,282 @@
+// Calibration of the INT8 layers (layers/_quantized.py): the seven MinMaxObservers of the reference's post-training flow
+// (layers/variational_layers/conv_variational.py:331-337, :387-397; the same in linear_variational.py) as two sweeps that keep their
+// statistics on the device. The reference materialises sigma, eps, sigma * eps and mu + sigma * eps as weight-sized tensors on the CPU
+// and hands seven tensors to seven observers; here
+//   * bt_q8_observe_w reads (mu, rho) once per sample, regenerates the sample's draws from the call's RNG coordinates (or reads the
+//     supplied ones) and merges the ranges of q = sigma * coef, m = mu * coef, eps, t = q * eps and w = m + t -- the five qint8 stubs
+//     in the reference's order -- into stats[10]; nothing weight-sized is written;
+//   * bt_minmax_update merges the ranges of up to four fp32 tensors (a layer's input and output) into (min, max) pairs.
+// Reduction: per thread, wavefront shuffles, one LDS step per workgroup, then at most ONE vector atomic per statistic and workgroup on
+// the value's bit pattern (none when a plain load shows that the value would not widen the statistic). The bits of a non-negative float order like a signed integer's and those of a negative float in reverse like
+// an unsigned integer's, so a float maximum is a signed-integer atomic max for v >= 0 and an unsigned-integer atomic min for v < 0
+// (the minimum: the mirror image); -0 is made +0 first and non-finite values never reach the atomics (they are counted instead).
+// Minimum and maximum have no order: the result does not depend on how the workgroups are scheduled. A pair starts at (+inf, -inf)
+// and a call can only widen it.
+#include "bt_api_internal.h"
+
+namespace bt {
+
+constexpr int kObsThreads = 256;
+constexpr int kObsStats = 5;   // sigma, mu, eps, mul, add
+constexpr int kObsGrid = 2048;   // workgroups of a launch, at most (256 CUs x 8)
+
+__device__ __forceinline__ bool obs_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+struct Range {
+  float lo, hi;
+  __device__ __forceinline__ void take(float v, unsigned& bad) {
+    if (obs_finite(v)) {
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+    } else {
+      ++bad;
+    }
+  }
+};
+
+__device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
+  v = __fadd_rn(v, 0.0f);   // -0 -> +0
+  if (v >= 0.0f)
+    __hip_atomic_fetch_min(reinterpret_cast<int*>(addr), __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    __hip_atomic_fetch_max(reinterpret_cast<unsigned*>(addr), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
+  v = __fadd_rn(v, 0.0f);
+  if (v >= 0.0f)
+    __hip_atomic_fetch_max(reinterpret_cast<int*>(addr), __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    __hip_atomic_fetch_min(reinterpret_cast<unsigned*>(addr), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The workgroup's ranges r[0 .. K) and its count of non-finite values -> dst[k] (a (min, max) pair each) and *nonfinite.
+// lds: 4 * (2 * K + 1) words. Every thread of the workgroup calls it.
+template <int K>
+__device__ __forceinline__ void obs_merge(Range (&r)[K], unsigned bad, float* const (&dst)[K], unsigned* nonfinite, float* lds) {
+  constexpr int W = 2 * K + 1;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      r[k].lo = fminf(r[k].lo, __shfl_xor(r[k].lo, o, 64));
+      r[k].hi = fmaxf(r[k].hi, __shfl_xor(r[k].hi, o, 64));
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) lds[wv * W + 2 * k] = r[k].lo, lds[wv * W + 2 * k + 1] = r[k].hi;
+    lds[wv * W + 2 * K] = __uint_as_float(bad);
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 2 * K) {
+    const bool is_max = t & 1;
+    float v = lds[t];
+#pragma unroll
+    for (int w = 1; w < kObsThreads / 64; ++w) v = is_max ? fmaxf(v, lds[w * W + t]) : fminf(v, lds[w * W + t]);
+    // (still +-inf: the workgroup met no finite value.) A statistic only ever widens, so a value that does not widen what a plain
+    // load sees -- however stale -- cannot widen the current one: most workgroups issue no atomic at all, and the ones that do are
+    // not queued behind thousands of others on the same ten words.
+    if (obs_finite(v)) {
+      float* const p = dst[t >> 1] + (is_max ? 1 : 0);
+      const float cur = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (is_max ? v > cur : v < cur) {
+        if (is_max)
+          atomic_max_f32(p, v);
+        else
+          atomic_min_f32(p, v);
+      }
+    }
+  } else if (t == 2 * K) {
+    unsigned b = 0;
+#pragma unroll
+    for (int w = 0; w < kObsThreads / 64; ++w) b += __float_as_uint(lds[w * W + 2 * K]);
+    if (b) __hip_atomic_fetch_add(nonfinite, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// One weight: each product and the sum ONE fp32 rounding, as quantize() (mu * coef, sigma * coef) and the float forward
+// (sigma * eps, mu + sigma * eps) form them.
+__device__ __forceinline__ void obs_weight(float mu, float rho, float c, float eps, Range (&r)[kObsStats], unsigned& bad) {
+  const float q = __fmul_rn(softplus(rho), c);
+  const float m = __fmul_rn(mu, c);
+  const float t = __fmul_rn(q, eps);
+  const float w = __fadd_rn(m, t);
+  r[0].take(q, bad), r[1].take(m, bad), r[2].take(eps, bad), r[3].take(t, bad), r[4].take(w, bad);
+}
+
+struct ObsWArgs {
+  const float* mu;
+  const float* rho;
+  const float* coef;   // [rows] or null (1)
+  const float* eps;    // [S][n] or null: the tensor 0 stream of `key`
+  float* stats;        // [5][2]
+  unsigned* nonfinite;
+  const uint32_t* call_base;
+  RngKey key;
+  uint32_t sample0;
+  long long rows, inner, taps, n;
+};
+
+__device__ __forceinline__ void obs_init(Range (&r)[kObsStats]) {
+#pragma unroll
+  for (int k = 0; k < kObsStats; ++k) r[k].lo = INFINITY, r[k].hi = -INFINITY;
+}
+
+__device__ __forceinline__ void obs_finish(const ObsWArgs& a, Range (&r)[kObsStats], unsigned bad, float* lds) {
+  float* const dst[kObsStats] = {a.stats, a.stats + 2, a.stats + 4, a.stats + 6, a.stats + 8};
+  obs_merge<kObsStats>(r, bad, dst, a.nonfinite, lds);
+}
+
+// A thread per four consecutive elements of the weight's natural order, of sample blockIdx.y: 16-byte loads where mu, rho (and this
+// sample's supplied eps) are all 16-byte aligned, element by element for the last n & 3 elements and where they are not. kRng: the
+// element's draw is regenerated instead -- number e & 3 of Philox block e >> 2 of the tensor 0 stream, e = eps_stream_index(row,
+// channel, tap), the rule bt_rng_normal_fill materialises; consecutive taps of one channel lie in different blocks (the stream is
+// tap-major), so a 3 x 3 kernel runs one Philox block per element and a Linear layer one per four. The loads stay coalesced either way.
+template <bool kRng>
+__global__ __launch_bounds__(kObsThreads) void q8_observe_w_kernel(ObsWArgs a) {
+  __shared__ float lds[4 * (2 * kObsStats + 1)];
+  const float* const eps = kRng ? nullptr : a.eps + (long long)blockIdx.y * a.n;
+  RngKey k = a.key;
+  if (kRng && a.call_base) k.call += *a.call_base;
+  const uint32_t sample = a.sample0 + blockIdx.y;
+  const long long per_row = a.inner * a.taps, inner4 = (a.inner + 3) & ~3ll;
+  const int taps = (int)a.taps, inner = (int)a.inner;
+  const bool quads = ((((uintptr_t)a.mu) | ((uintptr_t)a.rho) | ((uintptr_t)eps)) & 15u) == 0;
+  const long long n4 = (a.n + 3) >> 2;
+  Range r[kObsStats];
+  unsigned bad = 0;
+  obs_init(r);
+  for (long long g = (long long)blockIdx.x * kObsThreads + threadIdx.x; g < n4; g += (long long)gridDim.x * kObsThreads) {
+    const long long i0 = g * 4;
+    const int cnt = a.n - i0 < 4 ? (int)(a.n - i0) : 4;
+    float m[4] = {0.f, 0.f, 0.f, 0.f}, rr[4] = {0.f, 0.f, 0.f, 0.f}, e[4] = {0.f, 0.f, 0.f, 0.f};
+    if (quads && cnt == 4) {
+      const float4 m4 = *reinterpret_cast<const float4*>(a.mu + i0);
+      const float4 r4 = *reinterpret_cast<const float4*>(a.rho + i0);
+      m[0] = m4.x, m[1] = m4.y, m[2] = m4.z, m[3] = m4.w;
+      rr[0] = r4.x, rr[1] = r4.y, rr[2] = r4.z, rr[3] = r4.w;
+      if (!kRng) {
+        const float4 e4 = *reinterpret_cast<const float4*>(eps + i0);
+        e[0] = e4.x, e[1] = e4.y, e[2] = e4.z, e[3] = e4.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) {
+          m[j] = a.mu[i0 + j], rr[j] = a.rho[i0 + j];
+          if (!kRng) e[j] = eps[i0 + j];
+        }
+    }
+    long long row = i0 / per_row;                       // (per_row < 2^31: the rest is 32-bit)
+    const int rem = (int)(i0 - row * per_row);
+    int c = rem / taps, t = rem - c * taps;
+    long long blk = -1;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) {
+        if (kRng) {
+          const long long el = eps_stream_index(row, c, t, inner4, taps);
+          if ((el >> 2) != blk) {
+            blk = el >> 2;
+            philox_normal4(k, sample, (uint32_t)blk, z);
+          }
+          const int w = (int)(el & 3);
+          e[j] = w == 0 ? z[0] : w == 1 ? z[1] : w == 2 ? z[2] : z[3];
+        }
+        obs_weight(m[j], rr[j], a.coef ? a.coef[row] : 1.0f, e[j], r, bad);
+        if (++t == taps) {
+          t = 0;
+          if (++c == inner) c = 0, ++row;
+        }
+      }
+  }
+  obs_finish(a, r, bad, lds);
+}
+
+struct MinMaxArgs {
+  const float* x[BT_MINMAX_MAX_SEGS];
+  long long n[BT_MINMAX_MAX_SEGS];
+  float* dst[BT_MINMAX_MAX_SEGS];
+  unsigned* nonfinite;
+};
+
+// Segment blockIdx.y: the elements before the first 16-byte boundary one by one, whole quads as 16-byte loads, the rest one by one.
+__global__ __launch_bounds__(kObsThreads) void minmax_update_kernel(MinMaxArgs a) {
+  __shared__ float lds[4 * 3];
+  const int sg = blockIdx.y;
+  const float* const x = a.x[sg];
+  const long long n = a.n[sg];
+  long long head = (long long)(((16u - (unsigned)(((uintptr_t)x) & 15u)) & 15u) >> 2);
+  if (head > n) head = n;
+  const long long nquad = (n - head) >> 2;
+  const long long tail0 = head + 4 * nquad;
+  Range r[1];
+  r[0].lo = INFINITY, r[0].hi = -INFINITY;
+  unsigned bad = 0;
+  const long long tid = (long long)blockIdx.x * kObsThreads + threadIdx.x, stride = (long long)gridDim.x * kObsThreads;
+  const float4* const x4 = reinterpret_cast<const float4*>(x + head);
+  for (long long g = tid; g < nquad; g += stride) {
+    const float4 v = x4[g];
+    r[0].take(v.x, bad), r[0].take(v.y, bad), r[0].take(v.z, bad), r[0].take(v.w, bad);
+  }
+  if (tid < head) r[0].take(x[tid], bad);                       // head < 4
+  if (tid < n - tail0) r[0].take(x[tail0 + tid], bad);          // n - tail0 < 4
+  float* const dst[1] = {a.dst[sg]};
+  obs_merge<1>(r, bad, dst, a.nonfinite, lds);
+}
+
+static const char* const kMinMaxNames[BT_MINMAX_MAX_SEGS] = {"minmax_update<1 segs>", "minmax_update<2 segs>", "minmax_update<3 segs>", "minmax_update<4 segs>"};
+
+}  // namespace bt
+
+extern "C" int bt_q8_observe_w(const float* mu, const float* rho, const float* coef, int64_t rows, int64_t inner, int64_t taps, int32_t S, const float* eps,
+                               const bt_rng* rng, float* stats, uint32_t* nonfinite, bt_stream_t stream) {
+  using namespace bt;
+  if (!mu || !rho || !stats || !nonfinite) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: null mu / rho / stats / nonfinite");
+  if (S < 1 || rows < 1 || inner < 1 || taps < 1) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: S < 1 or an empty weight tensor (n < 1)");
+  if (!eps == !rng) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: exactly one draw source, eps or rng");
+  if ((((uintptr_t)mu) | ((uintptr_t)rho) | ((uintptr_t)coef) | ((uintptr_t)eps) | ((uintptr_t)stats) | ((uintptr_t)nonfinite)) & 3u)
+    return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: a pointer that is not 4-byte aligned");
+  if (S > 65535 || rows >= (1ll << 31) || inner >= (1ll << 31) || taps >= (1ll << 31)) return set_error(BT_ERR_UNSUPPORTED, "bt_q8_observe_w: S > 65535 or tensor too large");
+  const long long nq = (long long)rows * taps * (((long long)inner + 3) >> 2);
+  if ((long long)inner * taps >= (1ll << 31) || (long long)rows * inner >= (1ll << 40) / taps || nq > (1ll << 32)) return set_error(BT_ERR_UNSUPPORTED, "bt_q8_observe_w: weight tensor too large for the draw stream");
+  ObsWArgs a = {};
+  a.mu = mu, a.rho = rho, a.coef = coef, a.eps = eps, a.stats = stats, a.nonfinite = nonfinite;
+  a.rows = rows, a.inner = inner, a.taps = taps, a.n = (long long)rows * inner * taps;
+  if (rng) a.call_base = rng->call_base_dev, a.key = make_key(*rng, 0), a.sample0 = rng->sample0;
+  // about kObsGrid workgroups over all samples (a few per CU), each walking its share of the quads: every workgroup ends in a merge
+  long long gx = (((a.n + 3) >> 2) + kObsThreads - 1) / kObsThreads;
+  const long long cap = (kObsGrid + S - 1) / S;
+  if (gx > cap) gx = cap;
+  const dim3 grid((unsigned)gx, (unsigned)S);
+  if (rng) return launch_kernel(q8_observe_w_kernel<true>, "q8_observe_w<eps on chip>", "bt_q8_observe_w", grid, dim3(kObsThreads), 0, 0, (hipStream_t)stream, a);
+  return launch_kernel(q8_observe_w_kernel<false>, "q8_observe_w<eps injected>", "bt_q8_observe_w", grid, dim3(kObsThreads), 0, 0, (hipStream_t)stream, a);
+}
+
+extern "C" int bt_minmax_update(int32_t n_segs, const bt_minmax_seg* segs, uint32_t* nonfinite, bt_stream_t stream) {
+  using namespace bt;
+  if (n_segs < 1 || n_segs > BT_MINMAX_MAX_SEGS) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: 1 to 4 segments");
+  if (!segs || !nonfinite || (((uintptr_t)nonfinite) & 3u)) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: null segs / nonfinite");
+  MinMaxArgs a = {};
+  long long most = 0;
+  for (int i = 0; i < BT_MINMAX_MAX_SEGS; ++i) {
+    const bt_minmax_seg& s = segs[i < n_segs ? i : 0];   // (the unused slots repeat segment 0; no workgroup reads them)
+    if (i < n_segs) {
+      if (!s.x || !s.dst || s.n < 1) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: a segment with a null pointer or n < 1");
+      if ((((uintptr_t)s.x) | ((uintptr_t)s.dst)) & 3u) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: a pointer that is not 4-byte aligned");
+      if (s.n >= (1ll << 40)) return set_error(BT_ERR_UNSUPPORTED, "bt_minmax_update: segment too large");
+      if (s.n > most) most = s.n;
+    }
+    a.x[i] = s.x, a.n[i] = s.n, a.dst[i] = s.dst;
+  }
+  a.nonfinite = nonfinite;
+  long long gx = (most + 4 * kObsThreads - 1) / (4 * kObsThreads);   // a thread takes at least one quad
+  if (gx > kObsGrid) gx = kObsGrid;
+  return launch_kernel(minmax_update_kernel, kMinMaxNames[n_segs - 1], "bt_minmax_update", dim3((unsigned)gx, (unsigned)n_segs), dim3(kObsThreads), 0, 0,
+                       (hipStream_t)stream, a);
+}

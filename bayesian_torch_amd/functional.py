@@ -722,3 +722,70 @@ def q8_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, 
         else:
             _lib.check(_lib.lib().bt_q8_conv2d_fwd(C.byref(geom), S, *tail_args))
     return out, out_q
+
+
+# ---------------------------------------------------------------------------- calibration of the INT8 layers (csrc/bt_q8_observe.hip)
+CALIB_ROWS = ("sigma", "mu", "eps", "mul", "add", "in", "out")      # the rows of a layer's ``calib_minmax`` [7, 2]: (min, max) pairs
+
+
+def calib_buffers(device=None):
+    """-> (calib_minmax fp32 [7, 2] of (+inf, -inf) pairs, calib_nonfinite int32 [1] of 0): empty statistics."""
+    mm = torch.empty((len(CALIB_ROWS), 2), dtype=torch.float32, device=device)
+    mm[:, 0], mm[:, 1] = float("inf"), float("-inf")
+    return mm, torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def _calib_dev(t, what, dtype):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} is on {t.device}: the observer kernels run on a HIP (MI355X) device only")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise TypeError(f"{what} must be a contiguous {dtype} tensor")
+    return t
+
+
+def _no_capture(dev, what):
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what}: calibration inside a graph capture is not supported; run the calibration batches eagerly")
+
+
+def q8_observe_w(mu, rho, stats, nonfinite, *, S=1, coef=None, eps=None, seed=0, call=0, layer_id=0, sample0=0, call_base=None):
+    """The weight-side observers (bt_q8_observe_w): merge the ranges of sigma * coef, mu * coef, eps, their product and the sampled
+    weight over S samples into ``stats`` (fp32, >= 10 elements: rows 0..4 of a ``calib_minmax``), counting non-finite values into
+    ``nonfinite`` (int32 [1]). mu, rho: [Co, Ci, ...]; eps: [S, *mu.shape] supplied, or None for the on-chip tensor 0 stream of the
+    given coordinates; coef: [Co] or None. Nothing is returned and nothing is read back."""
+    mu, rho = _lib.dev_f32(mu, "mu"), _lib.dev_f32(rho, "rho")
+    coef, eps = _lib.dev_f32(coef, "coef"), _lib.dev_f32(eps, "eps")
+    _calib_dev(stats, "stats", torch.float32), _calib_dev(nonfinite, "nonfinite", torch.int32)
+    _no_capture(mu.device, "q8_observe_w")
+    if mu.shape != rho.shape or mu.dim() < 2 or stats.numel() < 10:
+        raise RuntimeError("q8_observe_w: mu and rho must be two tensors of one shape [Co, Ci, ...] and stats must hold 10 values")
+    rows, inner = mu.shape[0], mu.shape[1]
+    taps = math.prod(mu.shape[2:])
+    if eps is not None and eps.numel() != S * mu.numel():
+        raise RuntimeError(f"q8_observe_w: eps holds {eps.numel()} elements, S={S} samples of {mu.numel()} weights need {S * mu.numel()}")
+    if coef is not None and coef.numel() != rows:
+        raise RuntimeError(f"q8_observe_w: coef must hold {rows} values")
+    R = _rng(seed, call, layer_id, sample0, call_base)
+    with _lib.on(mu.device):
+        _lib.check(_lib.lib().bt_q8_observe_w(mu.data_ptr(), rho.data_ptr(), _lib.ptr(coef), rows, inner, taps, S, _lib.ptr(eps), None if eps is not None else C.byref(R),
+                                              stats.data_ptr(), nonfinite.data_ptr(), _lib.stream_ptr(mu.device)))
+
+
+def minmax_update(segments, nonfinite):
+    """The activation-side observers (bt_minmax_update): ``segments`` is a list of up to four (x, dst) -- x an fp32 device tensor,
+    dst a 2-element fp32 view ((min, max), e.g. one row of a ``calib_minmax``) its range is merged into -- in ONE launch."""
+    if not 1 <= len(segments) <= _lib.MINMAX_MAX_SEGS:
+        raise RuntimeError(f"minmax_update: 1 to {_lib.MINMAX_MAX_SEGS} segments")
+    _calib_dev(nonfinite, "nonfinite", torch.int32)
+    keep = []
+    for x, dst in segments:
+        x = _lib.dev_f32(x, "x")
+        _calib_dev(dst, "dst", torch.float32)
+        if dst.numel() != 2 or x.numel() == 0 or x.device != nonfinite.device or dst.device != nonfinite.device:
+            raise RuntimeError("minmax_update: x must be a non-empty tensor and dst a (min, max) pair, all on the counter's device")
+        keep.append((x, dst))
+    dev = nonfinite.device
+    _no_capture(dev, "minmax_update")
+    arr = (_lib.bt_minmax_seg * len(keep))(*[_lib.bt_minmax_seg(x.data_ptr(), x.numel(), dst.data_ptr()) for x, dst in keep])
+    with _lib.on(dev):
+        _lib.check(_lib.lib().bt_minmax_update(len(keep), arr, nonfinite.data_ptr(), _lib.stream_ptr(dev)))

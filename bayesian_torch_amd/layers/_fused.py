@@ -30,6 +30,19 @@ BT_FUSED_KL = bool(_os.environ.get("BT_FUSED_KL"))         # A/B knob: inference
 MAX_TAPS = 128     # kernel positions (kh * kw of the Conv2d launch) the fused kernels and bt_pack_sync support (kMaxTaps)
 
 
+class _BnOutputObserver:
+    """Forward hook of the BatchNorm a calibrating layer will be folded with: the layer's ``out`` statistic is the range of the
+    BatchNorm's output. An object, not a closure: a deep copy of the model observes into the COPY's layer."""
+
+    def __init__(self, layer):
+        self.layer = layer
+
+    def __call__(self, module, args, output):
+        layer = self.layer
+        if layer.quant_prepare and not torch.is_grad_enabled():
+            F.minmax_update([(output, layer.calib_minmax[6])], layer.calib_nonfinite)
+
+
 class FusedBayesLayer(BaseVariationalLayer_):
     _kind = "linear"     # or "conv"
     _flip = False
@@ -106,6 +119,53 @@ class FusedBayesLayer(BaseVariationalLayer_):
 
     def prepare(self):
         raise NotImplementedError("post-training quantisation (QuantStub observers) is outside the MI355X hot path")
+
+    # ------------------------------------------------------------------ calibration (LinearReparameterization / Conv2dReparameterization)
+    def _calib_prepare(self, bn=None):
+        """What ``prepare()`` of the two convertible classes does (reference conv_variational.py:331-337: seven QuantStub observers):
+        empty statistics in two persistent buffers, ``calib_minmax`` [7, 2] -- (min, max) of sigma, mu, eps, mul, add, in, out -- and
+        ``calib_nonfinite`` [1], filled on the device by every no-grad forward from now on (csrc/bt_q8_observe.hip). ``bn``: the
+        BatchNorm2d that ``bnn_to_qbnn(fuse_conv_bn=True)`` will fold into this layer: the weight rows are then those of
+        mu * coef and sigma * coef, and ``out`` is observed at the BatchNorm's output through a forward hook."""
+        name = type(self).__name__
+        if getattr(self, "groups", 1) != 1:
+            raise NotImplementedError(f"{name}.prepare(): groups={self.groups} has no INT8 counterpart here (groups must be 1)")
+        if self.post_scale is not None or self.post_shift is not None or self.post_relu or self.post_pool:
+            raise RuntimeError(f"{name}.prepare(): the layer carries a folded output stage (fuse.py); calibrate the unfolded model")
+        if bn is not None and bn.training:
+            raise RuntimeError(f"{name}.prepare(): the BatchNorm to fold is in training mode; call model.eval() first")
+        self._calib_release()
+        mm, bad = F.calib_buffers(self._w("mu").device)
+        self.register_buffer("calib_minmax", mm)
+        self.register_buffer("calib_nonfinite", bad)
+        coef = None
+        if bn is not None:
+            from ._quantized import _sqrt
+            coef = (bn.weight.detach() / _sqrt(bn.running_var + bn.eps)).to(torch.float32).contiguous()      # quantize()'s bn_coef
+            self._calib_hook = bn.register_forward_hook(_BnOutputObserver(self))
+        self.register_buffer("calib_coef", coef, persistent=False)
+        self._calib_fused = bn is not None
+        self.quant_prepare = True
+
+    def _calib_release(self):
+        """Take the BatchNorm's observer hook out again (``convert()``; a second ``prepare()``)."""
+        hook = self.__dict__.pop("_calib_hook", None)
+        if hook is not None:
+            hook.remove()
+
+    def _calib_observe(self, x, out, mu_t, rho_t, S, coords, draw):
+        """The two observer launches of a calibrating forward: the weight side with the call's own draws (the supplied tensor, or the
+        forward's RNG coordinates), then the input and -- unless the folded BatchNorm's hook observes it -- the output."""
+        if self.post_scale is not None or self.post_shift is not None or self.post_relu or self.post_pool:
+            raise RuntimeError(f"{type(self).__name__}: folded an output stage (fuse.py) after prepare(); calibrate the unfolded model")
+        mm, bad = self.calib_minmax, self.calib_nonfinite
+        F.q8_observe_w(mu_t, rho_t, mm, bad, S=S, coef=self.calib_coef, eps=draw.get("eps_w"), seed=coords.seed, call=coords.call, layer_id=coords.layer_id,
+                       sample0=coords.sample0, call_base=coords.call_base)
+        kernels = [_lib.lib().bt_last_kernel_name().decode()]
+        segs = [(x, mm[5])] + ([] if self._calib_fused else [(out, mm[6])])
+        F.minmax_update(segs, bad)
+        kernels.append(_lib.lib().bt_last_kernel_name().decode())
+        self._last.update(observed=True, observer_kernel=kernels[0], observer_kernels=tuple(kernels))
 
     def _w(self, what):
         return getattr(self, f"{what}_{self._wname}")
@@ -303,6 +363,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self._w("mu").requires_grad or self._w("rho").requires_grad
                                                   or (self.mu_bias is not None and self.mu_bias.requires_grad))
         fwd_kl = want_kl      # the forward kernel sweeps the KL term itself
+        if self.quant_prepare and needs_grad:
+            raise RuntimeError(f"{type(self).__name__}: prepare() was called -- calibration forwards run under torch.no_grad(); convert the model before training on")
         if needs_grad:
             # training path: same fused forward kernel, gradients through the autograd bridge (autograd.py)
             if self.post_scale is not None or residual is not None or self.post_relu or self.post_pool:
@@ -345,6 +407,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
         self._last = dict(draw=draw or None, rng=coords, S=S, kernel=_lib.lib().bt_last_kernel_name().decode(), launch=_lib.last_launch_info(),
                           shared_x=shared, residual=residual is not None, fused_kl=bool(not needs_grad and fwd_kl),
                           x_shape=(B,) + tuple(x.shape[1:]), out_shape=(B,) + conv_shape)
+        if self.quant_prepare:
+            self._calib_observe(x, out, mu_t, rho_t, S, coords, draw)
         if lead is not None:
             out = out.reshape(lead + (self.out_features,))
         if one_d:

@@ -15,8 +15,9 @@ does not quantise the bias either). ROCm tensors have no quantised dtype: ``get_
 Deviations from the reference: the conv layer returns the DEQUANTISED fp32 output where the reference returns a quint8 tensor (the
 Linear layer dequantises there too); ``_last["out_q"]`` holds the u8 image when ``want_q`` is set. ``enable_int8_compute=False`` (the
 reference's deprecated dequantise-and-run-fp32 branch) raises NotImplementedError -- with the reference's precedence: a layer that has a
-``quant_dict`` takes the calibrated int8 branch whatever ``enable_int8_compute`` says, there and here -- and so does ``prepare()``: a ``quant_dict`` is
-supplied by the caller as a list of five ``{'scale', 'zero_point'}`` entries (eps, mul, add, in, out). The layers are not
+``quant_dict`` takes the calibrated int8 branch whatever ``enable_int8_compute`` says, there and here -- and so does ``prepare()`` of a
+quantised layer: calibration happens on the FLOAT layer (``quantization.prepare`` / ``convert``), and the
+``quant_dict`` -- a list of five ``{'scale', 'zero_point'}`` entries (eps, mul, add, in, out) -- comes from there or from the caller. The layers are not
 ``FusedBayesLayer``s: ``fuse.py`` leaves them alone, and their KL is 0 as in the reference.
 """
 import torch

@@ -35,6 +35,12 @@ class Conv2dReparameterization(FusedBayesLayer):
     def forward(self, input, return_kl=True, residual=None):
         return self._forward(input, return_kl, residual)
 
+    def prepare(self, bn=None):
+        """Start calibrating for ``bnn_to_qbnn``: see ``FusedBayesLayer._calib_prepare`` (subclasses keep raising)."""
+        if type(self) is not Conv2dReparameterization:
+            return super().prepare()
+        self._calib_prepare(bn)
+
 
 class Conv1dReparameterization(FusedBayesLayer):
     """Drop-in for reference ``conv_variational.py:68-232`` -- a 1 x k kernel over a 1 x L image on the same fused kernel."""

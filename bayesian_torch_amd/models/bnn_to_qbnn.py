@@ -7,6 +7,8 @@ the int8 images and the fp32 bias and becomes ``Identity``) -- and, as in the re
 rule names is left float; that is said in a ``UserWarning`` naming the layer, since the model then mixes float and int8 layers. Converted are ``LinearReparameterization`` and ``Conv2dReparameterization`` (groups 1); any other Bayesian layer raises
 NotImplementedError naming its class (Flipout, Conv1d / Conv3d, ConvTranspose, LSTM, groups > 1). An unfused BatchNorm is left as it
 is (the reference swaps in ``torch.nn.quantized.BatchNorm2d``, a CPU-only module; activations between layers stay fp32 here).
+A float layer that was calibrated (``quantization.prepare``, then forwards) yields a layer with the ``quant_dict`` its statistics give
+(reference :105-111, :132-138); an unprepared one converts to the default branch.
 """
 import warnings
 
@@ -26,7 +28,36 @@ def _quantized_class(d):
     return getattr(bayesian_layers, "Quantized" + name)
 
 
-def _finish(qbnn_layer, d):
+def _calibrated_dict(d, name):
+    """The ``quant_dict`` of a layer that was calibrated (``prepare()`` + forwards): [eps, mul, add, in, out] as {'scale', 'zero_point'} --
+    the reference's ``quant_dict[2:] + quint`` selection (models/bnn_to_qbnn.py:105-111) -- from the statistics the observer kernels
+    left on the device. ONE host read: the seven (min, max) pairs and whether any non-finite value was met."""
+    import torch
+    from bayesian_torch_amd.functional import CALIB_ROWS
+    from bayesian_torch_amd.quantization.quantize import observer_qparams
+    who = f"{type(d).__name__} '{name}'" if name else type(d).__name__
+    host = torch.cat([d.calib_minmax.detach().reshape(-1).to(torch.float32), (d.calib_nonfinite.detach().reshape(-1) != 0).to(torch.float32)]).cpu()
+    mm, bad = host[:-1].reshape(len(CALIB_ROWS), 2), bool(host[-1])
+    if bad:
+        raise RuntimeError(f"bnn_to_qbnn: {who} met non-finite values while calibrating (calib_nonfinite != 0): its ranges cannot be trusted")
+    out = []
+    for row in range(2, len(CALIB_ROWS)):
+        if not bool(torch.isfinite(mm[row]).all()):
+            raise RuntimeError(f"bnn_to_qbnn: {who} was prepared but its '{CALIB_ROWS[row]}' statistics are still empty: run the calibration batches "
+                               "(under torch.no_grad()) between prepare() and convert()")
+        scale, zp = observer_qparams(mm[row, 0], mm[row, 1], torch.qint8 if row < 5 else torch.quint8)
+        out.append({"scale": float(scale), "zero_point": int(zp)})
+    return out
+
+
+def _finish(qbnn_layer, d, fused=False, name=None):
+    if d.quant_prepare:
+        if bool(getattr(d, "_calib_fused", False)) != bool(fused):
+            how = lambda f: "fuse_conv_bn=True" if f else "fuse_conv_bn=False"
+            raise RuntimeError(f"bnn_to_qbnn: {type(d).__name__}{' ' + repr(name) if name else ''} was prepared with {how(d._calib_fused)} and is being converted "
+                               f"with {how(fused)}: its statistics describe a different layer")
+        qbnn_layer.quant_dict = _calibrated_dict(d, name)
+        d._calib_release()
     qbnn_layer.__dict__["_float"] = d          # (not a submodule: quantize() takes it out again)
     qbnn_layer.quantize()
     qbnn_layer._layer_id = d._layer_id          # the converted layer keeps the float layer's draw stream
@@ -35,8 +66,8 @@ def _finish(qbnn_layer, d):
     return qbnn_layer
 
 
-def qbnn_linear_layer(d):
-    return _finish(_quantized_class(d)(in_features=d.in_features, out_features=d.out_features), d)
+def qbnn_linear_layer(d, name=None):
+    return _finish(_quantized_class(d)(in_features=d.in_features, out_features=d.out_features), d, name=name)
 
 
 def _conv_shell(d):
@@ -44,51 +75,81 @@ def _conv_shell(d):
                                padding=d.padding, dilation=d.dilation, groups=d.groups)
 
 
-def qbnn_conv_layer(d):
-    return _finish(_conv_shell(d), d)
+def qbnn_conv_layer(d, name=None):
+    return _finish(_conv_shell(d), d, name=name)
 
 
-def batch_norm_folding(conv, bn):
+def batch_norm_folding(conv, bn, name=None):
     qbnn_layer = _conv_shell(conv)
     qbnn_layer.bn_weight, qbnn_layer.bn_bias = bn.weight, bn.bias
     qbnn_layer.bn_running_mean, qbnn_layer.bn_running_var, qbnn_layer.bn_eps = bn.running_mean, bn.running_var, bn.eps
-    return _finish(qbnn_layer, conv)
+    return _finish(qbnn_layer, conv, fused=True, name=name)
 
 
-def _walk(m, fuse_conv_bn):
+def conv_bn_pairs(m):
+    """The (conv, BatchNorm) pairs the folding rules name among the children of ``m`` -- ``conv1/bn1 ... conv3/bn3`` and a two-element
+    ``downsample`` Sequential, a BatchNorm that is already ``Identity`` excepted -- as (holder module, conv key, bn key). The one
+    statement of the rules: the converter folds these pairs and ``quantization.enable_prepare(fuse_conv_bn=True)`` calibrates them."""
+    out = []
+    for i in (1, 2, 3):
+        c, b = f"conv{i}", f"bn{i}"
+        if c in m._modules and b in m._modules and "Identity" not in m._modules[b].__class__.__name__:
+            out.append((m, c, b))
+    ds = m._modules.get("downsample")
+    if ds is not None and ds.__class__.__name__ == "Sequential" and len(ds) == 2 and "Identity" not in ds[1].__class__.__name__:
+        out.append((ds, "0", "1"))
+    return out
+
+
+class _Convert:
+    """What the walk does to a model that is being converted."""
+
+    def refuse(self, child):
+        _quantized_class(child)          # raises: the Bayesian LSTM (a module of two Linear layers) has no INT8 counterpart
+
+    def conv(self, m, name):
+        setattr(m, name, qbnn_conv_layer(m._modules[name], name))
+
+    def linear(self, m, name):
+        setattr(m, name, qbnn_linear_layer(m._modules[name], name))
+
+    def pair(self, holder, c, b):
+        setattr(holder, c, batch_norm_folding(holder._modules[c], holder._modules[b], c))
+        setattr(holder, b, Identity())
+
+    def left(self, m, name):
+        left = m._modules[name]
+        if hasattr(left, "_layer_id") and hasattr(left, "kl_loss") and not left.__class__.__name__.startswith("Quantized"):
+            _quantized_class(left)       # raises for a Bayesian layer that has no INT8 counterpart
+            warnings.warn(f"bnn_to_qbnn(fuse_conv_bn=True): {left.__class__.__name__} '{name}' is named by no conv/bn folding rule and stays "
+                          "float, as in the reference; the converted model mixes float and int8 layers", UserWarning, stacklevel=4)
+
+
+def _walk(m, fuse_conv_bn, act):
+    """The reference's module walk (models/bnn_to_qbnn.py:198-237); ``act`` says what happens at each site (conversion: ``_Convert``;
+    calibration: quantization/quantize.py's)."""
     for name in list(m._modules):
         child = m._modules[name]
         cname = child.__class__.__name__
         if "LSTM" in cname:
-            _quantized_class(child)          # raises: the Bayesian LSTM (a module of two Linear layers) has no INT8 counterpart
+            act.refuse(child)
         elif child._modules:
             if "Conv" in cname:
-                setattr(m, name, qbnn_conv_layer(child))
+                act.conv(m, name)
             elif "Linear" in cname:
-                setattr(m, name, qbnn_linear_layer(child))
+                act.linear(m, name)
             else:
-                _walk(child, fuse_conv_bn)
+                _walk(child, fuse_conv_bn, act)
         elif "Linear" in cname:
-            setattr(m, name, qbnn_linear_layer(child))
+            act.linear(m, name)
         elif fuse_conv_bn:
-            for i in (1, 2, 3):
-                c, b = f"conv{i}", f"bn{i}"
-                if c in m._modules and b in m._modules and "Identity" not in m._modules[b].__class__.__name__:
-                    setattr(m, c, batch_norm_folding(m._modules[c], m._modules[b]))
-                    setattr(m, b, Identity())
-            ds = m._modules.get("downsample")
-            if ds is not None and ds.__class__.__name__ == "Sequential" and len(ds) == 2 and "Identity" not in ds[1].__class__.__name__:
-                ds[0] = batch_norm_folding(ds[0], ds[1])
-                ds[1] = Identity()
-            left = m._modules[name]
-            if hasattr(left, "_layer_id") and hasattr(left, "kl_loss") and not left.__class__.__name__.startswith("Quantized"):
-                _quantized_class(left)       # raises for a Bayesian layer that has no INT8 counterpart
-                warnings.warn(f"bnn_to_qbnn(fuse_conv_bn=True): {left.__class__.__name__} '{name}' is named by no conv/bn folding rule and stays "
-                              "float, as in the reference; the converted model mixes float and int8 layers", UserWarning, stacklevel=3)
+            for holder, c, b in conv_bn_pairs(m):
+                act.pair(holder, c, b)
+            act.left(m, name)
         elif "Conv" in cname:
-            setattr(m, name, qbnn_conv_layer(child))
+            act.conv(m, name)
 
 
 def bnn_to_qbnn(m, fuse_conv_bn=False):
-    _walk(m, fuse_conv_bn)
+    _walk(m, fuse_conv_bn, _Convert())
     return

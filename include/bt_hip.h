@@ -548,6 +548,33 @@ int bt_q8_conv2d_fwd(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t
 int bt_q8_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, const float *x, int64_t x_sample_stride, const bt_q8_params *p,
                      const float *eps_w, const float *eps_b, const bt_rng *rng, float *out, uint8_t *out_q, bt_stream_t stream);
 
+/* Calibration of the INT8 layers: the seven MinMaxObservers of the reference's prepare() / calibrate / convert() flow
+ * (conv_variational.py:331-337, :387-397), with the statistics kept on the device. A statistic is a (min, max) pair of fp32 values
+ * that starts at (+inf, -inf); both calls MERGE into it (a call can only widen a pair), skip non-finite values and count them into
+ * *nonfinite (uint32, device memory), write nothing else, allocate nothing and never synchronise with the host. The merge is one
+ * integer vector atomic per statistic and workgroup on the value's bit pattern: the result does not depend on scheduling.
+ *
+ * bt_q8_observe_w, the weight side: mu, rho fp32 [rows][inner][taps] (the weight's natural order, n = rows * inner * taps elements, any
+ * n, 4-byte alignment only), S samples of draws -- eps fp32 [S][n] in the same order, or eps NULL and rng: tensor 0's stream under
+ * bt_rng_normal_fill's index rule, sample rng->sample0 + s --, coef fp32 [rows] or NULL (1): a per-output-channel factor, the folded
+ * BatchNorm's weight / sqrt(running_var + eps). With sigma = log1p(exp(rho)) (the kernels' softplus) and every operation ONE fp32
+ * rounding:  m = mu * coef,  q = sigma * coef,  t = q * eps,  w = m + t.  stats: fp32 [5][2], the ranges of q, m, eps, t, w -- the
+ * reference's five qint8 stubs in its order (sigma, mu, eps, mul, add).
+ * BT_ERR_BAD_ARG before any launch: a null mu / rho / stats / nonfinite, S < 1, rows / inner / taps < 1, both eps and rng or neither, a
+ * pointer that is not 4-byte aligned. BT_ERR_UNSUPPORTED, nothing launched: S > 65535, n >= 2^40, inner * taps >= 2^31, rows * taps * ceil(inner / 4) > 2^32. */
+int bt_q8_observe_w(const float *mu, const float *rho, const float *coef, int64_t rows, int64_t inner, int64_t taps, int32_t S,
+                    const float *eps, const bt_rng *rng, float *stats, uint32_t *nonfinite, bt_stream_t stream);
+/* The activation side: the ranges of up to BT_MINMAX_MAX_SEGS fp32 tensors (x, n elements, 4-byte alignment only), each merged into its
+ * own pair dst[2], in one launch. BT_ERR_BAD_ARG before any launch: n_segs outside 1..4, a null segs / nonfinite / x / dst, n < 1, a
+ * pointer that is not 4-byte aligned. */
+#define BT_MINMAX_MAX_SEGS 4
+typedef struct bt_minmax_seg {
+  const float *x;
+  int64_t n;
+  float *dst; /* (min, max) */
+} bt_minmax_seg;
+int bt_minmax_update(int32_t n_segs, const bt_minmax_seg *segs, uint32_t *nonfinite, bt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

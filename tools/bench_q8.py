@@ -14,7 +14,13 @@ synchronise at each end of a window), ``--repeats`` windows each; a rate is imag
 model the median, min and max rate over the windows, then the kernel every Bayesian layer of the int8 and the float model ran, and each
 int8 layer's own time (HIP events around its launch, median of ``--n``) beside the float layer's.
 
-    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10]
+``--calibrate N``: a third copy is calibrated first -- ``quantization.prepare(fuse_conv_bn=True)``, N calls of ``mc_forward`` on fresh
+random batches (every layer observes all S samples' draws, its input and its output on the device), ``quantization.convert`` -- and
+reported as ``int8_calibrated`` beside the default-branch ``int8``; per layer the prepared float layer's time (forward + the observer
+launches in the layer's own forward; the folded BatchNorm's output is observed behind it, outside these events) beside the float
+layer's, and the layer's calibrated ``quant_dict``. Calibration is not on the inference path: it runs N times per model, ever.
+
+    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10] [--calibrate N]
 """
 import argparse
 import copy
@@ -80,6 +86,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=10)
+    ap.add_argument("--calibrate", type=int, default=0, metavar="N", help="also calibrate a copy on N batches and report it beside the default-branch model")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_q8 needs a GPU: a CPU run measures nothing")
@@ -101,6 +108,23 @@ def main():
     models = {"float": net, "float_fused": fused, "int8": q}
     B, S = args.B, args.S
     x = torch.randn(B, 3, 32, 32, device="cuda")
+    if args.calibrate > 0:
+        from bayesian_torch_amd import quantization
+        cal = quantization.prepare(copy.deepcopy(net), fuse_conv_bn=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.calibrate):
+            mc.mc_forward(cal, torch.randn(B, 3, 32, 32, device="cuda"), S, with_kl=False)
+        torch.cuda.synchronize()
+        print(json.dumps(dict(what="calibration", batches=args.calibrate, B=B, S=S, seconds=round(time.perf_counter() - t0, 3))), flush=True)
+        for (nm, kf, uf), (_, _, up) in zip(layer_times(net, x, S, args.n), layer_times(cal, x, S, args.n)):
+            m = dict(cal.named_modules())[nm]
+            print(json.dumps(dict(what="observer", layer=nm, float_us=uf, prepared_us=up, observer_us=round(up - uf, 1), observer_kernels=m._last.get("observer_kernels"))), flush=True)
+        quantization.convert(cal, fuse_conv_bn=True)
+        for nm, m in cal.named_modules():
+            if getattr(m, "quant_dict", None) is not None:
+                print(json.dumps(dict(what="quant_dict", layer=nm, pairs=[(round(d["scale"], 6), d["zero_point"]) for d in m.quant_dict])), flush=True)
+        models["int8_calibrated"] = cal
     run = {k: (lambda m=m: mc.mc_forward(m, x, S, with_kl=False)) for k, m in models.items()}
     with torch.no_grad():
         for k in models:
@@ -116,6 +140,8 @@ def main():
                                   windows=len(r), window_s=args.window)), flush=True)
         print(json.dumps(dict(what="ratio", int8_over_float=round(statistics.median(rates["int8"]) / statistics.median(rates["float"]), 3),
                               int8_over_float_fused=round(statistics.median(rates["int8"]) / statistics.median(rates["float_fused"]), 3))), flush=True)
+        if "int8_calibrated" in rates:
+            print(json.dumps(dict(what="ratio", int8_calibrated_over_int8=round(statistics.median(rates["int8_calibrated"]) / statistics.median(rates["int8"]), 3))), flush=True)
         tq, tf = layer_times(q, x, S, args.n), layer_times(net, x, S, args.n)
         for (nm, kq, uq), (nf, kf, uf) in zip(tq, tf):
             print(json.dumps(dict(what="layer", layer=nm, int8_us=uq, float_us=uf, int8_kernel=kq, float_kernel=kf)), flush=True)
