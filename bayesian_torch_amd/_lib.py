@@ -80,6 +80,11 @@ class bt_q8_params(C.Structure):
         + [(n, _vp) for n in ("mu_packed", "sigma_packed", "mu_b", "sigma_b")]
 
 
+class bt_q8_flip_params(C.Structure):
+    _fields_ = [(n, bt_q8_pair) for n in ("eps", "delta", "inp", "mean", "sign_in", "sign_out", "xp", "pert", "pert_signed", "out")] \
+        + [("s_mu", C.c_double), ("s_sigma", C.c_double)] + [(n, _vp) for n in ("mu_packed", "sigma_packed", "mu_b", "sigma_b")]
+
+
 class bt_minmax_seg(C.Structure):
     _fields_ = [("x", _vp), ("n", C.c_int64), ("dst", _vp)]
 
@@ -142,6 +147,9 @@ _PROTOS = {
     "bt_q8_pack": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "bt_q8_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
     "bt_q8_linear_fwd": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_q8_flip_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, C.POINTER(bt_q8_flip_params), _vp, _vp, _vp, _vp, C.POINTER(bt_rng), _vp, _vp,
+                                       _vp]),
+    "bt_q8_flip_linear_fwd": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_q8_flip_params), _vp, _vp, _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
     "bt_q8_observe_w": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
     "bt_minmax_update": (C.c_int, [C.c_int32, C.POINTER(bt_minmax_seg), _vp, _vp]),
 }

@@ -17,17 +17,9 @@
 // Operand layout in LDS: [unit][row or pixel][16 bytes]; lane l of a wave reads the 16 bytes of row l & 31 in unit 2 * chunk + (l >> 5)
 // for A and B alike -- the contraction only needs A and B to agree on which k a (lane half, byte) pair means, and they are written
 // by the same rule. C/D: column (pixel) l & 31, row (channel) (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).
-#include "bt_api_internal.h"
+#include "bt_q8_common.h"
 
 namespace bt {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-constexpr int kQ8Threads = 256;
-constexpr int kQ8TM = 64;    // output channels per workgroup
-constexpr int kQ8TN = 128;   // output pixels per workgroup
-constexpr int kQ8SU = 4;     // units (16 K positions each) per stage
 
 struct Q8Args {
   const float* x;
@@ -55,8 +47,6 @@ struct Q8Args {
   int z_in, z_out;
 };
 
-__device__ __forceinline__ int clamp_i8(float v) { return (int)fminf(fmaxf(v, -128.f), 127.f); }
-
 // e -> p -> w of one weight (include/bt_hip.h): one fp32 rounding per operation.
 __device__ __forceinline__ int q8_weight(int qm, int qs, float eps, const Q8Args& a) {
   const int e = clamp_i8(rintf(__fmul_rn(eps, a.inv_eps)));
@@ -64,15 +54,6 @@ __device__ __forceinline__ int q8_weight(int qm, int qs, float eps, const Q8Args
   const float t = __fadd_rn(__fmul_rn((float)p, a.s_mul), __fmul_rn((float)qm, a.s_mu));
   return clamp_i8(rintf(__fmul_rn(t, a.inv_add)));
 }
-
-// Walked unit v -> (tap t, 16-channel block cb): the v / CB-th live tap when taps are pruned, else the v / CB-th tap.
-__device__ __forceinline__ void q8_unit(const Q8Args& a, int v, int& t, int& cb) {
-  const int tv = v / a.CB;
-  cb = v - tv * a.CB;
-  t = a.pruned ? (int)((a.live_taps >> (4 * tv)) & 15u) : tv;
-}
-
-__device__ __forceinline__ int sext8(int word, int j) { return (int)(int8_t)((unsigned)word >> (8 * j)); }
 
 __global__ __launch_bounds__(kQ8Threads) void q8_fwd_kernel(Q8Args a) {
   __shared__ v4i lds_a[kQ8SU * kQ8TM];   // 4 KiB
@@ -313,15 +294,8 @@ __global__ __launch_bounds__(256) void q8_pack_kernel(const int8_t* __restrict__
 
 static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const float* x, long long x_sample_stride, const bt_q8_params* p, const float* eps_w,
                       const float* eps_b, const bt_rng* rng, float* out, uint8_t* out_q, hipStream_t stream) {
-  char buf[256];
-  auto fail = [&](int code, const char* what) {
-    snprintf(buf, sizeof(buf), "%s: %s", who, what);
-    return set_error(code, buf);
-  };
-  if (!x || !p || !out || S <= 0 || x_sample_stride < 0) return fail(BT_ERR_BAD_ARG, "null x / p / out, S <= 0 or a negative sample stride");
-  if (!p->mu_packed || !p->sigma_packed) return fail(BT_ERR_BAD_ARG, "the int8 packs are missing (bt_q8_pack)");
-  if ((((uintptr_t)p->mu_packed) | ((uintptr_t)p->sigma_packed)) & 15u) return fail(BT_ERR_BAD_ARG, "the int8 packs must be 16-byte aligned");
-  if (const char* ge = geom_error(g)) return fail(BT_ERR_BAD_ARG, ge);
+  const Q8Fail fail = {who};
+  if (int rc = q8_check_operands(fail, x, p, out, S, x_sample_stride, p ? p->mu_packed : nullptr, p ? p->sigma_packed : nullptr, g)) return rc;
   if (!eps_w && !rng) return fail(BT_ERR_BAD_ARG, "neither eps_w nor rng");
   if (eps_w && !eps_b && p->mu_b && p->sigma_b) return fail(BT_ERR_BAD_ARG, "eps_w without eps_b for a bias that has a sigma");
   const bt_q8_pair* pairs[5] = {&p->eps, &p->mul, &p->add, &p->in, &p->out};
@@ -332,14 +306,9 @@ static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const flo
     return fail(BT_ERR_BAD_ARG, "an in / out zero point outside 0..255");
   if (g.groups != 1) return fail(BT_ERR_UNSUPPORTED, "groups != 1");
   if (p->eps.zero_point || p->mul.zero_point || p->add.zero_point) return fail(BT_ERR_UNSUPPORTED, "a nonzero eps / mul / add zero point");
-  const long long taps = (long long)g.kh * g.kw, K = taps * g.Ci;
-  if (K * 32640ll >= (1ll << 31)) return fail(BT_ERR_UNSUPPORTED, "K * 32640 >= 2^31: the int32 accumulator could overflow");
-  const long long Ho = conv_out_h(g), Wo = conv_out_w(g);
-  if (Ho <= 0 || Wo <= 0) return fail(BT_ERR_BAD_ARG, "convolution output would be empty");
-  const long long npix = (long long)g.B * Ho * Wo;
-  if (S > 65535 || npix >= (1ll << 31) || (long long)g.Ci * g.H * g.W * g.B >= (1ll << 40)) return fail(BT_ERR_UNSUPPORTED, "S > 65535 or tensor too large");
-  const long long Ci16 = ((long long)g.Ci + 15) & ~15ll;
-  if ((long long)g.Co * taps * (((long long)g.Ci + 3) >> 2) > (1ll << 32)) return fail(BT_ERR_UNSUPPORTED, "weight tensor too large for the draw stream");
+  long long Ho, Wo, npix;
+  if (int rc = q8_check_sizes(fail, g, S, Ho, Wo, npix)) return rc;
+  const long long taps = (long long)g.kh * g.kw, Ci16 = ((long long)g.Ci + 15) & ~15ll;
 
   Q8Args a = {};
   a.x = x, a.x_sample_stride = x_sample_stride, a.qmu = p->mu_packed, a.qsg = p->sigma_packed, a.eps_w = eps_w;
@@ -350,29 +319,10 @@ static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const flo
   a.call_base = R.call_base_dev, a.kw = make_key(R, 0), a.kb = make_key(R, 1), a.sample0 = R.sample0;
   a.B = g.B, a.Ci = g.Ci, a.H = g.H, a.W = g.W, a.Co = g.Co, a.KH = g.kh, a.KW = g.kw, a.sh = g.sh, a.sw = g.sw, a.ph = g.ph, a.pw = g.pw, a.dh = g.dh, a.dw = g.dw;
   a.Ho = (int)Ho, a.Wo = (int)Wo, a.CB = (int)(Ci16 / 16), a.taps = (int)taps, a.U = (int)(taps * (Ci16 / 16)), a.npix = npix;
-  // Taps that read padding for EVERY output pixel: with z_in == 128 a padding position is the MFMA's zero and no correction term
-  // reads the row sum, so such a tap contributes nothing and is not walked (a 3 x 3 kernel on a 1 x 1 map keeps its centre tap).
+  // With z_in == 128 a padding position is the MFMA's zero and no correction term reads the row sum: taps that read padding for every
+  // output pixel are not walked (q8_live_taps).
   a.VU = a.U;
-  if (p->in.zero_point == 128 && taps <= 16) {
-    uint64_t live = 0;
-    int n_live = 0;
-    for (int ky = 0; ky < g.kh; ++ky) {
-      bool row = false;
-      for (long long oh = 0; oh < Ho && !row; ++oh) {
-        const long long ih = oh * g.sh - g.ph + (long long)ky * g.dh;
-        row = ih >= 0 && ih < g.H;
-      }
-      for (int kx = 0; kx < g.kw; ++kx) {
-        bool col = false;
-        for (long long ow = 0; ow < Wo && !col; ++ow) {
-          const long long iw = ow * g.sw - g.pw + (long long)kx * g.dw;
-          col = iw >= 0 && iw < g.W;
-        }
-        if (row && col) live |= (uint64_t)(ky * g.kw + kx) << (4 * n_live++);
-      }
-    }
-    if (n_live < taps && n_live > 0) a.pruned = 1, a.live_taps = live, a.VU = n_live * a.CB;
-  }
+  if (p->in.zero_point == 128 && q8_live_taps(g, Ho, Wo, a.CB, a.live_taps, a.VU)) a.pruned = 1;
   const float s_eps = (float)p->eps.scale, s_add = (float)p->add.scale, s_in = (float)p->in.scale, s_out = (float)p->out.scale;
   a.inv_eps = 1.0f / s_eps;
   a.m_mul = (float)(p->s_sigma * p->eps.scale / p->mul.scale);

@@ -1,6 +1,8 @@
-"""INT8 post-training-quantised Reparameterization layers -- ``QuantizedLinearReparameterization`` and
+"""INT8 post-training-quantised Bayesian layers. Reparameterization -- ``QuantizedLinearReparameterization`` and
 ``QuantizedConv2dReparameterization`` of the reference (layers/variational_layers/quantize_linear_variational.py:44-224,
-quantize_conv_variational.py:303-552) on the fused int8 MFMA forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd, csrc/bt_q8.hip).
+quantize_conv_variational.py:303-552) on the fused int8 MFMA forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd, csrc/bt_q8.hip) -- and, at
+the end of this file, Flipout: ``QuantizedLinearFlipout`` and ``QuantizedConv2dFlipout`` on the two-contraction forward
+(bt_q8_flip_conv2d_fwd / bt_q8_flip_linear_fwd, csrc/bt_q8_flip.hip; ``_QuantizedFlipoutLayer`` says what differs).
 
 The reference's forward is a chain of ``torch.ops.quantized.*`` calls, which exist on the CPU only. Here the chain -- quantise eps,
 quantised mul and add (the sampled int8 weight), quantise x, the int8 contraction, requantise -- is ONE launch for all S Monte-Carlo
@@ -174,29 +176,40 @@ class _QuantizedLayer(BaseVariationalLayer_):
         s_mu, s_sigma, packs = self._frozen()
         pairs = self._pairs(s_mu, s_sigma, normal_scale, default_scale, default_zero_point)
         S, shared, coords = self._call_coords(ctx, x.shape[0])
-        mu_b, sigma_b = self.quantized_mu_bias, self.quantized_sigma_bias
-        inj = self._take_injected()
-        eps_w = eps_b = None
-        if inj is not None:
-            eps_w = inj["eps_w"]
-            eps_b = inj.get("eps_b")
-            if eps_w.shape[0] != S:
-                raise RuntimeError(f"inject_draw holds {eps_w.shape[0]} samples, this call computes {S}")
-        elif rng.get_mode() == "torch":          # eps_w then eps_b per sample: the reference's draw order
-            eps_w = torch.empty((S,) + self._wshape, device=x.device)
-            eps_b = torch.empty((S, self._wshape[0]), device=x.device) if (mu_b is not None and sigma_b is not None) else None
-            for s in range(S):
-                eps_w[s].normal_()
-                if eps_b is not None:
-                    eps_b[s].normal_()
-        out, out_q = F.q8_forward(x, packs, self._wshape, s_mu, s_sigma, pairs, mu_b, sigma_b, conv=conv, S=S, shared_x=shared, eps_w=eps_w, eps_b=eps_b,
-                                  seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
-                                  want_q=self.want_q)
-        self._last = dict(draw=None if eps_w is None else dict(eps_w=eps_w, eps_b=eps_b), rng=coords, S=S, shared_x=shared, pairs=pairs, out_q=out_q,
-                          kernel=_lib.lib().bt_last_kernel_name().decode())
+        draw = self._supplied_draw(self._take_injected(), S, x, shared)
+        out, out_q = self._launch(x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw)
+        B = x.shape[0] // (1 if shared else S)
+        self._last = dict(draw=draw, rng=coords, S=S, shared_x=shared, pairs=pairs, out_q=out_q, x_shape=(B,) + tuple(x.shape[1:]),
+                          out_shape=(B,) + tuple(out.shape[1:]), kernel=_lib.lib().bt_last_kernel_name().decode())
         if lead is not None:
             out = out.reshape(lead + (self._wshape[0],))
         return (out, 0) if return_kl else out
+
+    def _has_sampled_bias(self):
+        return self.quantized_mu_bias is not None and self.quantized_sigma_bias is not None
+
+    def _supplied_draw(self, inj, S, x, shared):
+        """The draw this call reads instead of the on-chip streams -- the injected one, or in rng mode "torch" eps_w then eps_b per sample,
+        the reference's draw order -- as dict(eps_w, eps_b), or None."""
+        if inj is not None:
+            eps_w, eps_b = inj["eps_w"], inj.get("eps_b")
+            if eps_w.shape[0] != S:
+                raise RuntimeError(f"inject_draw holds {eps_w.shape[0]} samples, this call computes {S}")
+            return dict(eps_w=eps_w, eps_b=eps_b)
+        if rng.get_mode() != "torch":
+            return None
+        eps_w = torch.empty((S,) + self._wshape, device=x.device)
+        eps_b = torch.empty((S, self._wshape[0]), device=x.device) if self._has_sampled_bias() else None
+        for s in range(S):
+            eps_w[s].normal_()
+            if eps_b is not None:
+                eps_b[s].normal_()
+        return dict(eps_w=eps_w, eps_b=eps_b)
+
+    def _launch(self, x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw):
+        return F.q8_forward(x, packs, self._wshape, s_mu, s_sigma, pairs, self.quantized_mu_bias, self.quantized_sigma_bias, conv=conv, S=S, shared_x=shared,
+                            seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base, want_q=self.want_q,
+                            **(draw or {}))
 
     def materialize_last_draw(self):
         """The draw the last forward used: ``eps_w`` [S, *weight shape] and ``eps_b`` [S, Co] (None without a sampled bias) -- the
@@ -213,13 +226,16 @@ class _QuantizedLayer(BaseVariationalLayer_):
         dev = self.quantized_mu_weight.device
         eps_w = F.rng_fill_normal(seed, call, lid, sample0, 0, st["S"], self._wshape, dev)
         eps_b = None
-        if self.quantized_mu_bias is not None and self.quantized_sigma_bias is not None:
+        if self._has_sampled_bias():
             eps_b = F.rng_fill_normal(seed, call, lid, sample0, 1, st["S"], (self._wshape[0],), dev)
-        return dict(eps_w=eps_w, eps_b=eps_b)
+        return self._with_signs(dict(eps_w=eps_w, eps_b=eps_b), st, dev)
+
+    def _with_signs(self, d, st, dev):
+        return d
 
 
-class QuantizedLinearReparameterization(_QuantizedLayer):
-    """Drop-in for reference ``quantize_linear_variational.py:44-224``. Build it with ``bnn_to_qbnn``."""
+class _LinearShell:
+    """Construction and conversion of a quantised Linear layer, Reparameterization or Flipout (the float twins name their parameters alike)."""
 
     def __init__(self, in_features, out_features):
         super().__init__()
@@ -227,20 +243,24 @@ class QuantizedLinearReparameterization(_QuantizedLayer):
         self._init_common((out_features, in_features), True)
 
     def quantize(self, src=None):
-        """Take over the parameters of ``src`` (a LinearReparameterization; default: the layer ``bnn_to_qbnn`` attached): int8 images of
+        """Take over the parameters of ``src`` (the float Linear layer; default: the layer ``bnn_to_qbnn`` attached): int8 images of
         mu and log1p(exp(rho)), fp32 bias."""
         src = self._source(src)
         has_b = src.mu_bias is not None
         self.bias = has_b
         self._store(src.mu_weight, _softplus(src.rho_weight.detach()), src.mu_bias if has_b else None, _softplus(src.rho_bias.detach()) if has_b else None)
 
+
+class QuantizedLinearReparameterization(_LinearShell, _QuantizedLayer):
+    """Drop-in for reference ``quantize_linear_variational.py:44-224``. Build it with ``bnn_to_qbnn``."""
+
     def forward(self, input, enable_int8_compute=True, normal_scale=6 / 255, default_scale=0.2, default_zero_point=128, return_kl=True):
         return self._q8_forward(input, enable_int8_compute, normal_scale, default_scale, default_zero_point, return_kl)
 
 
-class QuantizedConv2dReparameterization(_QuantizedLayer):
-    """Drop-in for reference ``quantize_conv_variational.py:303-552``; returns the dequantised fp32 output (the reference: a quint8
-    tensor). ``bn_*``: set by ``batch_norm_folding`` before ``quantize()`` folds the BatchNorm into the int8 images and the bias."""
+class _Conv2dShell:
+    """Construction and conversion of a quantised Conv2d layer, Reparameterization or Flipout. ``bn_*``: set by ``batch_norm_folding``
+    before ``quantize()`` folds the BatchNorm into the int8 images and the bias."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=False):
         super().__init__()
@@ -261,7 +281,7 @@ class QuantizedConv2dReparameterization(_QuantizedLayer):
         return dict(stride=two(self.stride), padding=two(self.padding), dilation=two(self.dilation), groups=1)
 
     def quantize(self, src=None):
-        """Take over the parameters of ``src`` (a Conv2dReparameterization; default: the layer ``bnn_to_qbnn`` attached), folding the
+        """Take over the parameters of ``src`` (the float Conv2d layer; default: the layer ``bnn_to_qbnn`` attached), folding the
         BatchNorm given in ``bn_*`` if there is one: the expressions of quantize_conv_variational.py:405-435 in their order, with one
         difference -- the square root of ``running_var + eps`` is the IEEE (correctly rounded) fp32 value (``_sqrt``), where the
         reference takes whatever the host's fp32 ``torch.sqrt`` gives."""
@@ -285,8 +305,93 @@ class QuantizedConv2dReparameterization(_QuantizedLayer):
         self._store(mu, sigma, mu_b, sigma_b)
         self.bn_weight = self.bn_bias = self.bn_running_mean = self.bn_running_var = self.bn_eps = None
 
+
+class QuantizedConv2dReparameterization(_Conv2dShell, _QuantizedLayer):
+    """Drop-in for reference ``quantize_conv_variational.py:303-552``; returns the dequantised fp32 output (the reference: a quint8
+    tensor)."""
+
     def forward(self, input, enable_int8_compute=True, normal_scale=6 / 255, default_scale=0.1, default_zero_point=128, return_kl=True):
         return self._q8_forward(input, enable_int8_compute, normal_scale, default_scale, default_zero_point, return_kl)
 
 
-__all__ = ["QuantizedLinearReparameterization", "QuantizedConv2dReparameterization"]
+class _QuantizedFlipoutLayer(_QuantizedLayer):
+    """What the two INT8 Flipout layers add to ``_QuantizedLayer``: ten (scale, zero point) pairs, a draw of four tensors, and the
+    two-contraction forward (bt_q8_flip_conv2d_fwd / bt_q8_flip_linear_fwd, csrc/bt_q8_flip.hip).
+
+    One chain for the default and the calibrated branch (the reference's two branches differ, and both are broken: section 4.6h):
+    quantise x; o1 = qconv(x, q_mu, mu_b); quantise the two +-1 sign tensors; delta = quantized.mul(q_sigma, quantize(eps));
+    x' = quantized.mul(x, sign_in); p = qconv(x', delta, sigma_b * eps_b); out = quantized.add(o1, quantized.mul(p, sign_out)). The
+    signs are fair coins, as the float Flipout layers define them.
+
+    ``quant_dict``: a list of TEN ``{'scale', 'zero_point'}`` entries in the reference's order -- eps, delta, in, mean, sign_in, sign_out,
+    xp, pert, pert_signed, out -- supplied by the caller: Flipout layers are not calibrated here (``prepare()`` raises). ``inject_draw``:
+    dict(eps_w [S, *weight shape], eps_b [S, Co] or None, sign_in fp32 [S, B, *x.shape[1:]], sign_out fp32 [S, B, Co, ...]); in a sign
+    tensor a negative value means -1 and anything else +1. rng mode "torch" draws eps_w, eps_b, sign_in, sign_out per sample."""
+
+    def prepare(self):
+        raise NotImplementedError("Flipout layers are not calibrated here (the two partial outputs are never materialised by the float kernels): supply "
+                                  f"quant_dict, a list of ten {{'scale', 'zero_point'}} entries ({', '.join(F.Q8_FLIP_PAIRS)})")
+
+    def _pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
+        """The ten (scale, zero point) pairs of this call, in ``functional.Q8_FLIP_PAIRS``' order."""
+        if self.quant_dict is not None:
+            if len(self.quant_dict) != 10:
+                raise ValueError(f"quant_dict must hold ten {{'scale', 'zero_point'}} entries: {', '.join(F.Q8_FLIP_PAIRS)}")
+            return [(float(d["scale"]), int(d["zero_point"])) for d in self.quant_dict]
+        dflt = (float(default_scale), int(default_zero_point))
+        return [(float(normal_scale), 0), (s_sigma * float(normal_scale), 0)] + [dflt] * 8
+
+    def _out_tail(self, x):
+        conv = self._conv()
+        if conv is None:
+            return (self._wshape[0],)
+        return (self._wshape[0],) + F.conv_out_hw(x.shape[2], x.shape[3], self._wshape[2], self._wshape[3], *conv["stride"], *conv["padding"], *conv["dilation"])
+
+    def _supplied_draw(self, inj, S, x, shared):
+        if inj is not None:
+            d = dict(eps_w=inj["eps_w"], eps_b=inj.get("eps_b"), sign_in=inj["sign_in"], sign_out=inj["sign_out"])
+            if d["eps_w"].shape[0] != S:
+                raise RuntimeError(f"inject_draw holds {d['eps_w'].shape[0]} samples, this call computes {S}")
+            return d
+        if rng.get_mode() != "torch":
+            return None
+        dev, B = x.device, x.shape[0] // (1 if shared else S)
+        d = dict(eps_w=torch.empty((S,) + self._wshape, device=dev), eps_b=torch.empty((S, self._wshape[0]), device=dev) if self._has_sampled_bias() else None,
+                 sign_in=torch.empty((S, B) + tuple(x.shape[1:]), device=dev), sign_out=torch.empty((S, B) + self._out_tail(x), device=dev))
+        for s in range(S):
+            d["eps_w"][s].normal_()
+            if d["eps_b"] is not None:
+                d["eps_b"][s].normal_()
+            d["sign_in"][s].uniform_(-1, 1).sign_()
+            d["sign_out"][s].uniform_(-1, 1).sign_()
+        return d
+
+    def _launch(self, x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw):
+        return F.q8_flip_forward(x, packs, self._wshape, s_mu, s_sigma, pairs, self.quantized_mu_bias, self.quantized_sigma_bias, conv=conv, S=S, shared_x=shared,
+                                 seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
+                                 want_q=self.want_q, **(draw or {}))
+
+    def _with_signs(self, d, st, dev):
+        """materialize_last_draw after an on-chip draw: the two sign streams (bt_rng_sign_fill, tensors 2 and 3) beside eps_w and eps_b."""
+        seed, _, call, lid, sample0 = st["rng"]
+        d["sign_in"] = F.rng_fill_sign(seed, call, lid, sample0, 2, st["S"], st["x_shape"], dev)
+        d["sign_out"] = F.rng_fill_sign(seed, call, lid, sample0, 3, st["S"], st["out_shape"], dev)
+        return d
+
+
+class QuantizedLinearFlipout(_LinearShell, _QuantizedFlipoutLayer):
+    """Drop-in for reference ``quantized_linear_flipout.py:44-261``. Build it with ``bnn_to_qbnn(flipout=True)``."""
+
+    def forward(self, x, normal_scale=6 / 255, default_scale=0.1, default_zero_point=128, return_kl=True):
+        return self._q8_forward(x, True, normal_scale, default_scale, default_zero_point, return_kl)
+
+
+class QuantizedConv2dFlipout(_Conv2dShell, _QuantizedFlipoutLayer):
+    """Drop-in for reference ``quantized_conv_flipout.py:257-514``; returns the dequantised fp32 output. BatchNorm folding as on
+    ``QuantizedConv2dReparameterization`` (reference :350-386)."""
+
+    def forward(self, x, normal_scale=6 / 255, default_scale=0.1, default_zero_point=128, return_kl=True):
+        return self._q8_forward(x, True, normal_scale, default_scale, default_zero_point, return_kl)
+
+
+__all__ = ["QuantizedLinearReparameterization", "QuantizedConv2dReparameterization"]      # (the Flipout pair: exported by layers/flipout_layers)

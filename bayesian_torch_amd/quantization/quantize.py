@@ -107,10 +107,11 @@ def prepare(model, fuse_conv_bn=False):
     return model
 
 
-def convert(model, fuse_conv_bn=False):
-    """``bnn_to_qbnn(model, fuse_conv_bn)``: every calibrated layer becomes an INT8 layer with the ``quant_dict`` its statistics give
-    (one host read per layer); ``fuse_conv_bn`` must be what ``prepare`` was given. -> the model."""
-    _Q.bnn_to_qbnn(model, fuse_conv_bn=fuse_conv_bn)
+def convert(model, fuse_conv_bn=False, flipout=False):
+    """``bnn_to_qbnn(model, fuse_conv_bn, flipout)``: every calibrated layer becomes an INT8 layer with the ``quant_dict`` its statistics
+    give (one host read per layer); ``fuse_conv_bn`` must be what ``prepare`` was given. ``flipout=True`` converts the Flipout layers too
+    (they are not calibrated: default pairs, or a ``quant_dict`` of the caller's). -> the model."""
+    _Q.bnn_to_qbnn(model, fuse_conv_bn=fuse_conv_bn, flipout=flipout)
     return model
 
 

@@ -548,6 +548,48 @@ int bt_q8_conv2d_fwd(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t
 int bt_q8_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, const float *x, int64_t x_sample_stride, const bt_q8_params *p,
                      const float *eps_w, const float *eps_b, const bt_rng *rng, float *out, uint8_t *out_q, bt_stream_t stream);
 
+/* INT8 post-training-quantised Flipout layers (layers/flipout_layers/quantized_conv_flipout.py:257-514, quantized_linear_flipout.py
+ * :119-261): both contractions of the Flipout estimator and the whole operator chain between them in ONE launch, bit for bit what the
+ * chain of torch's CPU quantised operators gives. Ten (scale, zero point) pairs, in the order of the reference's ten-entry quant_dict:
+ * eps, delta, in, mean, sign_in, sign_out, xp, pert, pert_signed, out. Conventions as above (one fp32 rounding per operation, rne);
+ * requant is the output stage above (fbgemm's, ONE fma); sign_in / sign_out are +1 or -1:
+ *   e    = clamp(rne(eps * (1 / s_eps)), -128, 127)
+ *   d    = clamp(rne(float(q_sigma * e) * float(s_sigma * s_eps / s_delta)), -128, 127)        qint8 x qint8: the quotient in double
+ *   xq   = clamp(rne(x * (1 / s_in)) + z_in, 0, 255)
+ *   acc1 = sum_k (xq - z_in) * q_mu;   o1 = requant(acc1, mu_b; a = float(s_in) * float(s_mu)) -> (s_mean, z_mean)
+ *   qsi  = clamp(rne(sign_in * (1 / s_si)) + z_si, 0, 255),   qso likewise from sign_out
+ *   x'   = umul(xq, qsi -> xp)
+ *   acc2 = sum_k (x' - z_xp) * d;      p  = requant(acc2, sigma_b * eps_b; a = float(s_xp) * float(s_delta)) -> (s_pert, z_pert)
+ *   p'   = umul(p, qso -> pert_signed)
+ *   oq   = uadd(o1, p' -> out),        out = float(oq - z_out) * s_out
+ *   umul(a, b -> o) = clamp(rne(float((a - z_a) * (b - z_b)) * M) + z_o, 0, 255),  M = float(s_a) * float(s_b) * (1 / float(s_o)), fp32, left to right
+ *   uadd(a, b -> o) = clamp(rne((fmaf(float(a), s_a, -(float(z_a) * s_a)) + fmaf(float(b), s_b, -(float(z_b) * s_b))) * (1 / s_o)) + z_o, 0, 255)
+ * Padding contributes a real zero to both contractions. mu_b NULL: no bias on either path (sigma_b is then ignored); sigma_b NULL: the
+ * perturbation path carries none (a bias that came from BatchNorm folding). */
+typedef struct bt_q8_flip_params {
+  bt_q8_pair eps, delta, in, mean, sign_in, sign_out, xp, pert, pert_signed, out;
+  double s_mu, s_sigma;                   /* the scales of the two int8 parameter images */
+  const int8_t *mu_packed, *sigma_packed; /* bt_q8_pack's */
+  const float *mu_b, *sigma_b;            /* fp32 [Co] */
+} bt_q8_flip_params;
+/* The forward. x, x_sample_stride, out, out_q: as bt_q8_conv2d_fwd. A supplied draw is whole or absent: eps_w fp32 [S][Co][Ci][taps],
+ * eps_b [S][Co] (needed when there is a sigma_b), sign_in fp32 [S][B][Ci][H][W] and sign_out fp32 [S][B][Co][Ho][Wo] -- a NEGATIVE value
+ * means -1, anything else (+0, -0 and NaN included) +1 -- or all four NULL and rng: eps as above, the signs hash_sign of tensor 2's
+ * (sign_in) and tensor 3's (sign_out) stream at the element's offset in ONE sample's tensor, sample rng->sample0 + s -- so a launch fed
+ * bt_rng_normal_fill's and bt_rng_sign_fill's output gives the same bytes, and samples that share one x still get their own signs.
+ * BT_ERR_BAD_ARG before any launch: a null x / p / out / pack, a pack that is not 16-byte aligned, neither eps_w nor rng, eps_w without
+ * both sign tensors or a sign tensor without eps_w, eps_w without eps_b when the bias has a sigma, a scale <= 0, a zero point outside
+ * 0..255 (all but eps and delta), a product of scales that underflows fp32, an empty output. BT_ERR_UNSUPPORTED, nothing launched:
+ * groups != 1, a nonzero eps or delta zero point, Ci * taps * 32640 >= 2^31, 2^32 or more elements in one sample's x or output, and the
+ * size limits of bt_q8_conv2d_fwd. */
+int bt_q8_flip_conv2d_fwd(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t x_sample_stride, const bt_q8_flip_params *p,
+                          const float *eps_w, const float *eps_b, const float *sign_in, const float *sign_out, const bt_rng *rng,
+                          float *out, uint8_t *out_q, bt_stream_t stream);
+/* Linear as the 1 x 1 map: x [B][In], out [S][B][Out], eps_w [S][Out][In], sign_in [S][B][In], sign_out [S][B][Out]. */
+int bt_q8_flip_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, const float *x, int64_t x_sample_stride,
+                          const bt_q8_flip_params *p, const float *eps_w, const float *eps_b, const float *sign_in,
+                          const float *sign_out, const bt_rng *rng, float *out, uint8_t *out_q, bt_stream_t stream);
+
 /* Calibration of the INT8 layers: the seven MinMaxObservers of the reference's prepare() / calibrate / convert() flow
  * (conv_variational.py:331-337, :387-397), with the statistics kept on the device. A statistic is a (min, max) pair of fp32 values
  * that starts at (+inf, -inf); both calls MERGE into it (a call can only widen a pair), skip non-finite values and count them into

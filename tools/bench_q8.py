@@ -20,7 +20,12 @@ reported as ``int8_calibrated`` beside the default-branch ``int8``; per layer th
 launches in the layer's own forward; the folded BatchNorm's output is observed behind it, outside these events) beside the float
 layer's, and the layer's calibrated ``quant_dict``. Calibration is not on the inference path: it runs N times per model, ever.
 
-    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10] [--calibrate N]
+``--flipout``: the Flipout ResNet18 (bench.py's cfg4: the same network via dnn_to_bnn(type="Flipout"), same seeded parameters) joins the
+alternation as ``float_flipout``, and its copy converted by bnn_to_qbnn(fuse_conv_bn=True, flipout=True) as ``int8_flipout``: every conv
+and the Linear on the two-contraction int8 forward (bt_q8_flip_conv2d_fwd / bt_q8_flip_linear_fwd, default pairs). Per layer: the
+int8 Flipout layer's time beside the float Flipout layer's and the INT8 Reparameterization layer's -- DESIGN.md 4.6h.
+
+    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10] [--calibrate N] [--flipout]
 """
 import argparse
 import copy
@@ -87,6 +92,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--calibrate", type=int, default=0, metavar="N", help="also calibrate a copy on N batches and report it beside the default-branch model")
+    ap.add_argument("--flipout", action="store_true", help="also run the Flipout ResNet18, float and converted to the INT8 Flipout layers")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_q8 needs a GPU: a CPU run measures nothing")
@@ -106,6 +112,16 @@ def main():
     bnn_to_qbnn(q, fuse_conv_bn=True)
     fused = H.fuse_inference(copy.deepcopy(net))
     models = {"float": net, "float_fused": fused, "int8": q}
+    if args.flipout:
+        torch.manual_seed(0)
+        fnet = H.resnet18(10, 64)
+        dnn_to_bnn(fnet, dict(PRIOR, type="Flipout"))
+        with torch.no_grad():
+            H.fill_bayes_params(fnet, 1)
+        fnet = fnet.cuda().eval()
+        fq = copy.deepcopy(fnet)
+        bnn_to_qbnn(fq, fuse_conv_bn=True, flipout=True)
+        models["float_flipout"], models["int8_flipout"] = fnet, fq
     B, S = args.B, args.S
     x = torch.randn(B, 3, 32, 32, device="cuda")
     if args.calibrate > 0:
@@ -142,6 +158,13 @@ def main():
                               int8_over_float_fused=round(statistics.median(rates["int8"]) / statistics.median(rates["float_fused"]), 3))), flush=True)
         if "int8_calibrated" in rates:
             print(json.dumps(dict(what="ratio", int8_calibrated_over_int8=round(statistics.median(rates["int8_calibrated"]) / statistics.median(rates["int8"]), 3))), flush=True)
+        if args.flipout:
+            med = lambda k: statistics.median(rates[k])
+            print(json.dumps(dict(what="ratio", int8_flipout_over_float_flipout=round(med("int8_flipout") / med("float_flipout"), 3),
+                                  int8_flipout_over_int8=round(med("int8_flipout") / med("int8"), 3))), flush=True)
+            for (nm, kq, uq), (_, kf, uf), (_, _, ur) in zip(layer_times(fq, x, S, args.n), layer_times(fnet, x, S, args.n), layer_times(q, x, S, args.n)):
+                print(json.dumps(dict(what="layer_flipout", layer=nm, int8_flipout_us=uq, float_flipout_us=uf, int8_reparam_us=ur, int8_flipout_kernel=kq,
+                                      float_flipout_kernel=kf)), flush=True)
         tq, tf = layer_times(q, x, S, args.n), layer_times(net, x, S, args.n)
         for (nm, kq, uq), (nf, kf, uf) in zip(tq, tf):
             print(json.dumps(dict(what="layer", layer=nm, int8_us=uq, float_us=uf, int8_kernel=kq, float_kernel=kf)), flush=True)
