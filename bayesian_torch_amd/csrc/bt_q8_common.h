@@ -1,6 +1,24 @@
-// What the two INT8 forwards (bt_q8.hip: Reparameterization, bt_q8_flip.hip: Flipout) share: the tile geometry, the byte helpers, the
-// walk over (live) taps, and the host's argument and geometry checks. One definition of each, so the two kernels walk K alike and the
-// two entry points refuse alike.
+// The INT8 forwards (bt_q8.hip: Reparameterization, bt_q8_flip.hip: Flipout) are one walk with different arithmetic. This header
+// holds the walk -- q8_walk_kernel<Chain> -- with its argument core, its byte helpers and the host's checks and plan for that core; a
+// translation unit adds a chain (the arithmetic), the chain's own arguments and the entry points.
+//
+// The walk. A workgroup (256 threads, 4 waves as 2 x 2) owns a tile of 64 output channels x 128 output pixels of one sample and walks K
+// in stages of four units; a unit is the 16 (padded) input channels of one tap, 16 bytes of either operand. A chain runs kC
+// contractions over the same K (1: Reparameterization, 2: Flipout's mean and perturbation), so everything below exists kC times:
+//   * producers, weight side: thread (row, unit) reads its 16 bytes of q_mu and q_sigma from the [Co][taps][Ci16] packs, takes the
+//     unit's 16 draws (Philox blocks of the tensor 0 stream, or the injected fp32 eps), has the chain turn every four of them into one
+//     packed word per contraction and writes the 16 int8 weights to LDS in the MFMA's operand layout; it also sums them (the
+//     zero-point correction needs sum_k w over ALL K positions);
+//   * producers, x side: thread (pixel, two units) fetches the fp32 NCHW values, quantises them to xq, has the chain turn xq into one
+//     byte per contraction (padding: the chain's pad byte, z - 128, so that the correction (128 - z) * sum_k w makes padding a real
+//     zero) and writes them to LDS likewise;
+//   * consumers: every wave runs 2 K-chunks x 2 pixel blocks x kC contractions of 32x32x32 MFMAs on its 32 x 64 quarter.
+// The global operands of a stage are fetched one stage ahead into registers; where padding is the MFMA's zero in every B tile the taps
+// that read padding for every output pixel are not walked (DESIGN.md section 4.6f has the measurements). The output stage runs per
+// element in registers: the chain makes the u8 level of the kC corrected accumulators and bias terms, the walk stores it.
+// Operand layout in LDS: [unit][row or pixel][16 bytes]; lane l of a wave reads the 16 bytes of row l & 31 in unit 2 * chunk + (l >> 5)
+// for A and B alike -- the contraction only needs A and B to agree on which k a (lane half, byte) pair means, and they are written
+// by the same rule. C/D: column (pixel) l & 31, row (channel) (reg & 3) + 8 * (reg >> 2) + 4 * (l >> 5).
 #pragma once
 #include "bt_api_internal.h"
 
@@ -14,17 +32,312 @@ constexpr int kQ8TM = 64;    // output channels per workgroup
 constexpr int kQ8TN = 128;   // output pixels per workgroup
 constexpr int kQ8SU = 4;     // units (16 K positions each) per stage
 
+// What the walk reads; a chain's argument block derives from it.
+struct Q8Core {
+  const float* x;
+  long long x_sample_stride;
+  const int8_t* qmu;
+  const int8_t* qsg;
+  const float* eps_w;
+  const float* eps_b;
+  const float* mu_b;
+  const float* sigma_b;
+  float* out;
+  uint8_t* out_q;
+  const uint32_t* call_base;
+  RngKey kw, kb;
+  uint32_t sample0;
+  int B, Ci, H, W, Co, KH, KW, sh, sw, ph, pw, dh, dw, Ho, Wo;
+  int CB;     // 16-channel blocks per tap (Ci16 / 16)
+  int U;      // units: taps * CB
+  int taps;
+  int VU;     // units walked: live taps * CB (== U unless taps are pruned)
+  int pruned;           // some tap reads padding for every output pixel and padding is the MFMA's zero: such a tap contributes 0 and is skipped
+  uint64_t live_taps;   // pruned: the live taps in ascending order, four bits each (taps <= 16)
+  long long npix;       // B * Ho * Wo
+  float inv_eps, inv_in, s_out;
+  int z_in, z_out;
+};
+
 __device__ __forceinline__ int clamp_i8(float v) { return (int)fminf(fmaxf(v, -128.f), 127.f); }
 
 __device__ __forceinline__ int sext8(int word, int j) { return (int)(int8_t)((unsigned)word >> (8 * j)); }
 
-// Walked unit v -> (tap t, 16-channel block cb): the v / CB-th live tap when taps are pruned, else the v / CB-th tap. A: a kernel's
-// argument block with CB, pruned and live_taps.
-template <class A>
-__device__ __forceinline__ void q8_unit(const A& a, int v, int& t, int& cb) {
+// clamp(rne(t) + z, 0, 255): the last stage of every quint8 quantisation, as a float.
+__device__ __forceinline__ float q8_level(float t, int z) { return fminf(fmaxf(__fadd_rn(rintf(t), (float)z), 0.f), 255.f); }
+
+// quantize_per_tensor of one activation: clamp(rne(v * (1 / s)) + z, 0, 255).
+__device__ __forceinline__ int q8_quant_x(float v, float inv_s, int z) { return (int)q8_level(__fmul_rn(v, inv_s), z); }
+
+// clamp(rne(float(prod) * m) + z, 0, 255): quantized.mul of two quint8 values whose zero-point-free product is prod.
+__device__ __forceinline__ int q8_umul(int prod, float m, int z) { return (int)q8_level(__fmul_rn((float)prod, m), z); }
+
+// Walked unit v -> (tap t, 16-channel block cb): the v / CB-th live tap when taps are pruned, else the v / CB-th tap.
+__device__ __forceinline__ void q8_unit(const Q8Core& a, int v, int& t, int& cb) {
   const int tv = v / a.CB;
   cb = v - tv * a.CB;
   t = a.pruned ? (int)((a.live_taps >> (4 * tv)) & 15u) : tv;
+}
+
+// Walked unit v as the x side sees it, for the output pixel whose window starts at (ih0, iw0): the unit's first channel c0, whether
+// its tap lies inside the image, and the offset of (c0, tap) in that image (meaningful only where inside). plane: H * W, which the
+// caller holds once (formed here, from a.H and a.W, it costs q8_walk_kernel<Q8Reparam> two registers and with them its third wave).
+struct Q8Tap {
+  int c0;
+  bool inside;
+  long long off;
+};
+__device__ __forceinline__ Q8Tap q8_tap(const Q8Core& a, int v, int ih0, int iw0, long long plane) {
+  int t, cb;
+  q8_unit(a, v, t, cb);
+  const int ky = t / a.KW, kx = t - ky * a.KW;
+  const int ih = ih0 + ky * a.dh, iw = iw0 + kx * a.dw;
+  Q8Tap r;
+  r.c0 = cb * 16;
+  r.inside = ih >= 0 && ih < a.H && iw >= 0 && iw < a.W;
+  r.off = (long long)r.c0 * plane + (long long)ih * a.W + iw;
+  return r;
+}
+
+// A Chain has
+//   kC                                   contractions;
+//   Args                                 : Q8Core, the kernel's argument block;
+//   Chain(a, s, sample, call_base)       per-workgroup set-up (call_base: what *a.call_base adds to a key's call, 0 without one);
+//   bias(mu, has_sigma, sigma, eps, b)   mu_b, sigma_b, eps_b of a channel -> kC bias terms;
+//   weights(qm, qs, eps, w, sum)         one packed q_mu word, one packed q_sigma word, their four draws -> kC packed weight words,
+//                                        whose bytes it adds to the kC row sums;
+//   pads(p)                              the kC bytes of a padding position;
+//   activation(xq, off, b)               a quantised x and its offset in one sample's x -> kC bytes;
+//   corrections(zc)                      what multiplies the kC row sums;
+//   output(acc, b, off)                  kC corrected accumulators, bias terms, the offset in one sample's output -> the u8 level.
+template <class Chain>
+__global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Args a) {
+  constexpr int kC = Chain::kC;
+  __shared__ v4i lds_a[kC][kQ8SU * kQ8TM];   // 4 KiB each
+  __shared__ v4i lds_b[kC][kQ8SU * kQ8TN];   // 8 KiB each
+  __shared__ int row_sum[kC][kQ8TM];
+  __shared__ float bias_term[kC][kQ8TM];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int s = blockIdx.z;
+  const int co0 = blockIdx.y * kQ8TM;
+  const long long n0 = (long long)blockIdx.x * kQ8TN;
+  const uint32_t call_base = a.call_base ? *a.call_base : 0u;
+  RngKey kw = a.kw, kb = a.kb;
+  kw.call += call_base, kb.call += call_base;
+  const uint32_t sample = a.sample0 + (uint32_t)s;
+  const Chain chain(a, s, sample, call_base);
+
+  // the bias terms of this sample's channels (0 without a bias): the output stage takes them into the accumulators' scales
+  if (tid < kQ8TM) {
+    const int co = co0 + tid;
+    float bt[kC];
+#pragma unroll
+    for (int c = 0; c < kC; ++c) bt[c] = 0.f;
+    if (a.mu_b && co < a.Co) {
+      const float mu = a.mu_b[co];
+      float sg = 0.f, eb = 0.f;
+      if (a.sigma_b) {
+        if (a.eps_b) {
+          eb = a.eps_b[(long long)s * a.Co + co];
+        } else {
+          float z[4];
+          philox_normal4(kb, sample, (uint32_t)(co >> 2), z);
+          eb = z[co & 3];
+        }
+        sg = a.sigma_b[co];
+      }
+      chain.bias(mu, a.sigma_b != nullptr, sg, eb, bt);
+    }
+#pragma unroll
+    for (int c = 0; c < kC; ++c) bias_term[c][tid] = bt[c];
+  }
+
+  // weight side: this thread's (row, unit of the stage)
+  const int a_row = tid >> 2, a_ul = tid & 3;
+  const int a_co = co0 + a_row;
+  const bool a_live = a_co < a.Co;
+  const long long inner4 = ((long long)a.Ci + 3) & ~3ll;
+  int wsum[kC];
+#pragma unroll
+  for (int c = 0; c < kC; ++c) wsum[c] = 0;
+
+  // x side: this thread's pixel and its two units of the stage
+  const int b_pl = tid & (kQ8TN - 1), b_u2 = (tid >> 7) * 2;
+  const long long b_n = n0 + b_pl;
+  const bool b_live = b_n < a.npix;
+  int ih0 = 0, iw0 = 0;
+  long long xoff0 = 0;   // the offset of this pixel's image in one sample's x
+  if (b_live) {
+    const long long hw = (long long)a.Ho * a.Wo;
+    const long long bi = b_n / hw;
+    const int r = (int)(b_n - bi * hw);
+    const int oh = r / a.Wo, ow = r - oh * a.Wo;
+    ih0 = oh * a.sh - a.ph;
+    iw0 = ow * a.sw - a.pw;
+    xoff0 = bi * (long long)a.Ci * a.H * a.W;
+  }
+  const float* xb = a.x + (long long)s * a.x_sample_stride + xoff0;
+  const long long plane = (long long)a.H * a.W;
+  int pad[kC];
+  chain.pads(pad);
+
+  v16i acc[kC][2];
+#pragma unroll
+  for (int c = 0; c < kC; ++c)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[c][0][i] = 0, acc[c][1][i] = 0;
+  const int wm = wv & 1, wn = wv >> 1;
+
+  // The global operands of a stage are fetched one stage ahead, into registers: this thread's 16 bytes of either pack and its 2 x 16
+  // fp32 values of x (0 where nothing is read). The loads are issued behind the barrier that publishes the current stage and are in
+  // flight under its MFMAs and the next stage's Philox rounds.
+  v4i pqm = {0, 0, 0, 0}, pqs = {0, 0, 0, 0};
+  float px[2][16];
+  auto prefetch = [&](int u0) {
+    const int va = u0 + a_ul;
+    if (a_live && va < a.VU) {
+      int t, cb;
+      q8_unit(a, va, t, cb);
+      const long long off = ((long long)a_co * a.U + t * a.CB + cb) * 16;
+      pqm = *reinterpret_cast<const v4i*>(a.qmu + off);
+      pqs = *reinterpret_cast<const v4i*>(a.qsg + off);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int v = u0 + b_u2 + k;
+      Q8Tap tp = {0, false, 0};
+      const float* xp = xb;
+      if (b_live && v < a.VU) {
+        tp = q8_tap(a, v, ih0, iw0, plane);
+        if (tp.inside) xp = xb + tp.off;
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) px[k][j] = (tp.inside && tp.c0 + j < a.Ci) ? xp[(long long)j * plane] : 0.f;
+    }
+  };
+  prefetch(0);
+
+  for (int u0 = 0; u0 < a.VU; u0 += kQ8SU) {
+    // ---- weight producer
+    {
+      const int v = u0 + a_ul;
+      v4i wq[kC];
+#pragma unroll
+      for (int c = 0; c < kC; ++c) wq[c] = v4i{0, 0, 0, 0};
+      if (a_live && v < a.VU) {
+        int t, cb;
+        q8_unit(a, v, t, cb);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c = cb * 16 + 4 * q;
+          float eps[4] = {0.f, 0.f, 0.f, 0.f};
+          if (c < a.Ci) {
+            if (a.eps_w) {
+              const float* ep = a.eps_w + (((long long)s * a.Co + a_co) * a.Ci + c) * a.taps + t;
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                if (c + j < a.Ci) eps[j] = ep[(long long)j * a.taps];
+            } else {
+              philox_normal4(kw, sample, (uint32_t)(eps_stream_index(a_co, c, t, inner4, a.taps) >> 2), eps);
+            }
+          }
+          int w[kC];
+          chain.weights(pqm[q], pqs[q], eps, w, wsum);
+#pragma unroll
+          for (int cc = 0; cc < kC; ++cc) wq[cc][q] = w[cc];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < kC; ++c) lds_a[c][a_ul * kQ8TM + a_row] = wq[c];
+    }
+    // ---- x producer
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int ul = b_u2 + k, v = u0 + ul;
+      v4i xq[kC];
+#pragma unroll
+      for (int c = 0; c < kC; ++c) xq[c] = v4i{0, 0, 0, 0};
+      if (b_live && v < a.VU) {
+        const Q8Tap tp = q8_tap(a, v, ih0, iw0, plane);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          int word[kC];
+#pragma unroll
+          for (int c = 0; c < kC; ++c) word[c] = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            int byte[kC];
+#pragma unroll
+            for (int c = 0; c < kC; ++c) byte[c] = pad[c];
+            if (tp.c0 + 4 * q + j >= a.Ci) {
+#pragma unroll
+              for (int c = 0; c < kC; ++c) byte[c] = 0;
+            } else if (tp.inside) {
+              chain.activation(q8_quant_x(px[k][4 * q + j], a.inv_in, a.z_in), xoff0 + tp.off + (long long)(4 * q + j) * plane, byte);
+            }
+#pragma unroll
+            for (int c = 0; c < kC; ++c) word[c] |= byte[c] << (8 * j);
+          }
+#pragma unroll
+          for (int c = 0; c < kC; ++c) xq[c][q] = word[c];
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < kC; ++c) lds_b[c][ul * kQ8TN + b_pl] = xq[c];
+    }
+    __syncthreads();
+    if (u0 + kQ8SU < a.VU) prefetch(u0 + kQ8SU);
+    // ---- consumers
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+      const int ul = 2 * ch + (lane >> 5);
+      const int ar = ul * kQ8TM + 32 * wm + (lane & 31), br = ul * kQ8TN + 64 * wn + (lane & 31);
+#pragma unroll
+      for (int c = 0; c < kC; ++c) {
+        const v4i av = lds_a[c][ar];
+        acc[c][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, lds_b[c][br], acc[c][0], 0, 0, 0);
+        acc[c][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, lds_b[c][br + 32], acc[c][1], 0, 0, 0);
+      }
+    }
+    __syncthreads();   // the stage has been consumed
+  }
+
+  // sum_k w of a row: its four producer threads are four adjacent lanes
+#pragma unroll
+  for (int c = 0; c < kC; ++c) {
+    wsum[c] += __shfl_xor(wsum[c], 1, 64);
+    wsum[c] += __shfl_xor(wsum[c], 2, 64);
+    if (a_ul == 0) row_sum[c][a_row] = wsum[c];
+  }
+  __syncthreads();
+
+  const long long hw = (long long)a.Ho * a.Wo;
+  int zc[kC];
+  chain.corrections(zc);
+  float* const out_s = a.out + (long long)s * a.npix * a.Co;   // this sample's [B][Co][Ho][Wo]
+  uint8_t* const outq_s = a.out_q ? a.out_q + (long long)s * a.npix * a.Co : nullptr;
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+    const long long n = n0 + 64 * wn + 32 * blk + (lane & 31);
+    if (n >= a.npix) continue;
+    const long long bi = n / hw;
+    const long long obase = bi * a.Co * hw + (n - bi * hw);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 32 * wm + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+      const int co = co0 + row;
+      if (co >= a.Co) continue;
+      const long long oi = obase + (long long)co * hw;
+      int av[kC];
+      float bt[kC];
+#pragma unroll
+      for (int c = 0; c < kC; ++c) av[c] = acc[c][blk][i] + zc[c] * row_sum[c][row], bt[c] = bias_term[c][row];
+      const float oq = chain.output(av, bt, oi);
+      out_s[oi] = __fmul_rn(__fsub_rn(oq, (float)a.z_out), a.s_out);
+      if (outq_s) outq_s[oi] = (uint8_t)oq;
+    }
+  }
 }
 
 // Taps that read padding for EVERY output pixel: where a padding position is the MFMA's zero and no correction term reads the row
@@ -55,8 +368,8 @@ inline bool q8_live_taps(const bt_conv2d_geom& g, long long Ho, long long Wo, in
   return true;
 }
 
-// The refusals the INT8 forwards have in common, in two steps between which an entry point checks its own draws and (scale, zero
-// point) pairs. Each returns BT_OK or the recorded error.
+// The refusals the INT8 forwards have in common, in steps between which an entry point checks its own draws, its (scale, zero point)
+// pairs and its multipliers. Each returns BT_OK or the recorded error.
 struct Q8Fail {
   const char* who;
   int operator()(int code, const char* what) const {
@@ -84,6 +397,40 @@ inline int q8_check_sizes(const Q8Fail& fail, const bt_conv2d_geom& g, int S, lo
   npix = (long long)g.B * Ho * Wo;
   if (S > 65535 || npix >= (1ll << 31) || (long long)g.Ci * g.H * g.W * g.B >= (1ll << 40)) return fail(BT_ERR_UNSUPPORTED, "S > 65535 or tensor too large");
   if ((long long)g.Co * taps * (((long long)g.Ci + 3) >> 2) > (1ll << 32)) return fail(BT_ERR_UNSUPPORTED, "weight tensor too large for the draw stream");
+  return BT_OK;
+}
+
+// What an entry point hands the plan besides the geometry: the operands both chains have. P: bt_q8_params or bt_q8_flip_params.
+struct Q8Operands {
+  const float* x;
+  long long x_sample_stride;
+  const float* eps_w;
+  const float* eps_b;
+  const bt_rng* rng;
+  float* out;
+  uint8_t* out_q;
+};
+
+// The last step: fills the walk's core from checked operands and sizes, and sets the grid. `zero_pad`: a padding position is the
+// MFMA's zero in every B tile (all the activations' zero points are 128), so taps that read padding only are not walked (q8_live_taps).
+template <class P>
+inline int q8_plan(const Q8Fail& fail, const bt_conv2d_geom& g, int S, long long Ho, long long Wo, long long npix, const Q8Operands& o, const P& p, bool zero_pad,
+                   Q8Core& a, dim3& grid) {
+  a.x = o.x, a.x_sample_stride = o.x_sample_stride, a.qmu = p.mu_packed, a.qsg = p.sigma_packed, a.eps_w = o.eps_w;
+  a.eps_b = o.eps_b;   // (a supplied bias draw beside on-chip weight draws is read)
+  a.mu_b = p.mu_b, a.sigma_b = p.mu_b ? p.sigma_b : nullptr, a.out = o.out, a.out_q = o.out_q;
+  bt_rng none = {};
+  const bt_rng& R = o.rng ? *o.rng : none;
+  a.call_base = R.call_base_dev, a.kw = make_key(R, 0), a.kb = make_key(R, 1), a.sample0 = R.sample0;
+  a.B = g.B, a.Ci = g.Ci, a.H = g.H, a.W = g.W, a.Co = g.Co, a.KH = g.kh, a.KW = g.kw, a.sh = g.sh, a.sw = g.sw, a.ph = g.ph, a.pw = g.pw, a.dh = g.dh, a.dw = g.dw;
+  const long long taps = (long long)g.kh * g.kw, CB = (((long long)g.Ci + 15) & ~15ll) / 16;
+  a.Ho = (int)Ho, a.Wo = (int)Wo, a.CB = (int)CB, a.taps = (int)taps, a.U = (int)(taps * CB), a.npix = npix;
+  a.VU = a.U;
+  if (zero_pad && q8_live_taps(g, Ho, Wo, a.CB, a.live_taps, a.VU)) a.pruned = 1;
+  a.inv_eps = 1.0f / (float)p.eps.scale, a.inv_in = 1.0f / (float)p.in.scale, a.s_out = (float)p.out.scale;
+  a.z_in = p.in.zero_point, a.z_out = p.out.zero_point;
+  grid = dim3((unsigned)((npix + kQ8TN - 1) / kQ8TN), (unsigned)((g.Co + kQ8TM - 1) / kQ8TM), (unsigned)S);
+  if (grid.y > 65535u) return fail(BT_ERR_UNSUPPORTED, "more than 65535 * 64 output channels");
   return BT_OK;
 }
 

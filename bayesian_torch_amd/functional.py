@@ -691,12 +691,10 @@ def q8_pack(q_mu, q_sigma):
     return mp, sp
 
 
-def q8_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, *, conv=None, S=1, shared_x=True, eps_w=None, eps_b=None,
-               seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False):
-    """The INT8 fused forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd; the arithmetic is include/bt_hip.h's). x: fp32 [B, Ci, H, W]
-    (conv: dict(stride, padding, dilation, groups)) or [B, In] (conv None); packs: q8_pack's; wshape: the weight's natural shape;
-    pairs: five (scale, zero point) -- eps, mul, add, in, out; eps_w [S, *wshape] and eps_b [S, Co] supplied, or None for the on-chip
-    streams. -> (out fp32 [S * B, Co, ...], the u8 image or None)."""
+def _q8_launch(who, x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, rng, want_q, params, draws=None):
+    """What the two INT8 forwards share: the operands, the draw sizes, the geometry, the outputs and the linear / conv2d call of
+    ``bt_<who>_*_fwd``. params(mu_packed, sigma_packed, mu_b, sigma_b) -> the entry's params struct; draws(B, x_elems, tail) -> the
+    pointers the entry takes between eps_b and rng (checked against the geometry there)."""
     x = _lib.dev_f32(x, "input")
     mu_b, sigma_b = _lib.dev_f32(mu_b, "mu_b"), _lib.dev_f32(sigma_b, "sigma_b")
     eps_w, eps_b = _lib.dev_f32(eps_w, "eps_w"), _lib.dev_f32(eps_b, "eps_b")
@@ -704,24 +702,35 @@ def q8_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, 
     wshape = tuple(int(v) for v in wshape)
     n = math.prod(wshape)
     if eps_w is not None and eps_w.numel() != S * n:
-        raise RuntimeError(f"q8_forward: eps_w holds {eps_w.numel()} elements, S={S} samples of {n} weights need {S * n}")
+        raise RuntimeError(f"{who}_forward: eps_w holds {eps_w.numel()} elements, S={S} samples of {n} weights need {S * n}")
     if eps_b is not None and eps_b.numel() != S * wshape[0]:
-        raise RuntimeError(f"q8_forward: eps_b must be [S={S}, {wshape[0]}]")
+        raise RuntimeError(f"{who}_forward: eps_b must be [S={S}, {wshape[0]}]")
     dev = x.device
     B, geom, x_elems, tail = _geometry(x, _Shape(wshape), conv, S, shared_x)
+    more = draws(B, x_elems, tail) if draws else ()
     out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev)
     out_q = torch.empty((S * B,) + tail, dtype=torch.uint8, device=dev) if want_q else None
-    pr = [_lib.bt_q8_pair(float(s), int(z), 0) for s, z in pairs]
-    P = _lib.bt_q8_params(pr[0], pr[1], pr[2], pr[3], pr[4], float(s_mu), float(s_sigma), mp.data_ptr(), sp.data_ptr(), _lib.ptr(mu_b), _lib.ptr(sigma_b))
-    Rg = _rng(seed, call, layer_id, sample0, call_base)
-    tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), _lib.ptr(eps_w), _lib.ptr(eps_b), C.byref(Rg), out.data_ptr(), _lib.ptr(out_q),
+    P = params(mp.data_ptr(), sp.data_ptr(), _lib.ptr(mu_b), _lib.ptr(sigma_b))
+    Rg = _rng(*rng)
+    tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), _lib.ptr(eps_w), _lib.ptr(eps_b), *more, C.byref(Rg), out.data_ptr(), _lib.ptr(out_q),
                  _lib.stream_ptr(dev))
     with _lib.on(dev):
         if conv is None:
-            _lib.check(_lib.lib().bt_q8_linear_fwd(B, wshape[1], wshape[0], S, *tail_args))
+            _lib.check(getattr(_lib.lib(), f"bt_{who}_linear_fwd")(B, wshape[1], wshape[0], S, *tail_args))
         else:
-            _lib.check(_lib.lib().bt_q8_conv2d_fwd(C.byref(geom), S, *tail_args))
+            _lib.check(getattr(_lib.lib(), f"bt_{who}_conv2d_fwd")(C.byref(geom), S, *tail_args))
     return out, out_q
+
+
+def q8_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, *, conv=None, S=1, shared_x=True, eps_w=None, eps_b=None,
+               seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False):
+    """The INT8 fused forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd; the arithmetic is include/bt_hip.h's). x: fp32 [B, Ci, H, W]
+    (conv: dict(stride, padding, dilation, groups)) or [B, In] (conv None); packs: q8_pack's; wshape: the weight's natural shape;
+    pairs: five (scale, zero point) -- eps, mul, add, in, out; eps_w [S, *wshape] and eps_b [S, Co] supplied, or None for the on-chip
+    streams. -> (out fp32 [S * B, Co, ...], the u8 image or None)."""
+    pr = [_lib.bt_q8_pair(float(s), int(z), 0) for s, z in pairs]
+    return _q8_launch("q8", x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, (seed, call, layer_id, sample0, call_base), want_q,
+                      lambda *ptrs: _lib.bt_q8_params(pr[0], pr[1], pr[2], pr[3], pr[4], float(s_mu), float(s_sigma), *ptrs))
 
 
 Q8_FLIP_PAIRS = ("eps", "delta", "in", "mean", "sign_in", "sign_out", "xp", "pert", "pert_signed", "out")      # the order of a ten-entry quant_dict
@@ -734,39 +743,21 @@ def q8_flip_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=N
     point) in the order ``Q8_FLIP_PAIRS``, and a supplied draw is whole or absent: eps_w [S, *wshape], eps_b [S, Co] (when there is a
     sigma_b), sign_in fp32 [S, B, *x.shape[1:]] and sign_out fp32 [S, B, Co, ...] (a negative value means -1, anything else +1), or
     all None for the on-chip streams (tensors 0 to 3). -> (out fp32 [S * B, Co, ...], the u8 image or None)."""
-    x = _lib.dev_f32(x, "input")
-    mu_b, sigma_b = _lib.dev_f32(mu_b, "mu_b"), _lib.dev_f32(sigma_b, "sigma_b")
-    eps_w, eps_b = _lib.dev_f32(eps_w, "eps_w"), _lib.dev_f32(eps_b, "eps_b")
     sign_in, sign_out = _lib.dev_f32(sign_in, "sign_in"), _lib.dev_f32(sign_out, "sign_out")
-    mp, sp = _dev_i8(packs[0], "mu_packed"), _dev_i8(packs[1], "sigma_packed")
-    wshape = tuple(int(v) for v in wshape)
-    n = math.prod(wshape)
     if len(pairs) != len(Q8_FLIP_PAIRS):
         raise ValueError(f"q8_flip_forward: pairs must hold ten (scale, zero point): {', '.join(Q8_FLIP_PAIRS)}")
-    if eps_w is not None and eps_w.numel() != S * n:
-        raise RuntimeError(f"q8_flip_forward: eps_w holds {eps_w.numel()} elements, S={S} samples of {n} weights need {S * n}")
-    if eps_b is not None and eps_b.numel() != S * wshape[0]:
-        raise RuntimeError(f"q8_flip_forward: eps_b must be [S={S}, {wshape[0]}]")
-    dev = x.device
-    B, geom, x_elems, tail = _geometry(x, _Shape(wshape), conv, S, shared_x)
-    n_out = B * math.prod(tail)
-    if sign_in is not None and sign_in.numel() != S * x_elems:
-        raise RuntimeError(f"q8_flip_forward: sign_in holds {sign_in.numel()} elements, S={S} samples of x need {S * x_elems}")
-    if sign_out is not None and sign_out.numel() != S * n_out:
-        raise RuntimeError(f"q8_flip_forward: sign_out holds {sign_out.numel()} elements, S={S} samples of the output need {S * n_out}")
-    out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev)
-    out_q = torch.empty((S * B,) + tail, dtype=torch.uint8, device=dev) if want_q else None
+
+    def signs(B, x_elems, tail):
+        n_out = B * math.prod(tail)
+        if sign_in is not None and sign_in.numel() != S * x_elems:
+            raise RuntimeError(f"q8_flip_forward: sign_in holds {sign_in.numel()} elements, S={S} samples of x need {S * x_elems}")
+        if sign_out is not None and sign_out.numel() != S * n_out:
+            raise RuntimeError(f"q8_flip_forward: sign_out holds {sign_out.numel()} elements, S={S} samples of the output need {S * n_out}")
+        return _lib.ptr(sign_in), _lib.ptr(sign_out)
+
     pr = [_lib.bt_q8_pair(float(s), int(z), 0) for s, z in pairs]
-    P = _lib.bt_q8_flip_params(*pr, float(s_mu), float(s_sigma), mp.data_ptr(), sp.data_ptr(), _lib.ptr(mu_b), _lib.ptr(sigma_b))
-    Rg = _rng(seed, call, layer_id, sample0, call_base)
-    tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), _lib.ptr(eps_w), _lib.ptr(eps_b), _lib.ptr(sign_in), _lib.ptr(sign_out), C.byref(Rg),
-                 out.data_ptr(), _lib.ptr(out_q), _lib.stream_ptr(dev))
-    with _lib.on(dev):
-        if conv is None:
-            _lib.check(_lib.lib().bt_q8_flip_linear_fwd(B, wshape[1], wshape[0], S, *tail_args))
-        else:
-            _lib.check(_lib.lib().bt_q8_flip_conv2d_fwd(C.byref(geom), S, *tail_args))
-    return out, out_q
+    return _q8_launch("q8_flip", x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, (seed, call, layer_id, sample0, call_base), want_q,
+                      lambda *ptrs: _lib.bt_q8_flip_params(*pr, float(s_mu), float(s_sigma), *ptrs), signs)
 
 
 # ---------------------------------------------------------------------------- calibration of the INT8 layers (csrc/bt_q8_observe.hip)

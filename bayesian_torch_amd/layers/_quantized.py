@@ -206,10 +206,12 @@ class _QuantizedLayer(BaseVariationalLayer_):
                 eps_b[s].normal_()
         return dict(eps_w=eps_w, eps_b=eps_b)
 
+    _forward_fn = staticmethod(F.q8_forward)      # the functional forward of the estimator: what _launch calls
+
     def _launch(self, x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw):
-        return F.q8_forward(x, packs, self._wshape, s_mu, s_sigma, pairs, self.quantized_mu_bias, self.quantized_sigma_bias, conv=conv, S=S, shared_x=shared,
-                            seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base, want_q=self.want_q,
-                            **(draw or {}))
+        return self._forward_fn(x, packs, self._wshape, s_mu, s_sigma, pairs, self.quantized_mu_bias, self.quantized_sigma_bias, conv=conv, S=S, shared_x=shared,
+                                seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
+                                want_q=self.want_q, **(draw or {}))
 
     def materialize_last_draw(self):
         """The draw the last forward used: ``eps_w`` [S, *weight shape] and ``eps_b`` [S, Co] (None without a sampled bias) -- the
@@ -328,6 +330,8 @@ class _QuantizedFlipoutLayer(_QuantizedLayer):
     dict(eps_w [S, *weight shape], eps_b [S, Co] or None, sign_in fp32 [S, B, *x.shape[1:]], sign_out fp32 [S, B, Co, ...]); in a sign
     tensor a negative value means -1 and anything else +1. rng mode "torch" draws eps_w, eps_b, sign_in, sign_out per sample."""
 
+    _forward_fn = staticmethod(F.q8_flip_forward)
+
     def prepare(self):
         raise NotImplementedError("Flipout layers are not calibrated here (the two partial outputs are never materialised by the float kernels): supply "
                                   f"quant_dict, a list of ten {{'scale', 'zero_point'}} entries ({', '.join(F.Q8_FLIP_PAIRS)})")
@@ -365,11 +369,6 @@ class _QuantizedFlipoutLayer(_QuantizedLayer):
             d["sign_in"][s].uniform_(-1, 1).sign_()
             d["sign_out"][s].uniform_(-1, 1).sign_()
         return d
-
-    def _launch(self, x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw):
-        return F.q8_flip_forward(x, packs, self._wshape, s_mu, s_sigma, pairs, self.quantized_mu_bias, self.quantized_sigma_bias, conv=conv, S=S, shared_x=shared,
-                                 seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
-                                 want_q=self.want_q, **(draw or {}))
 
     def _with_signs(self, d, st, dev):
         """materialize_last_draw after an on-chip draw: the two sign streams (bt_rng_sign_fill, tensors 2 and 3) beside eps_w and eps_b."""

@@ -6,6 +6,7 @@ import zlib
 
 import torch
 
+import _q8_edges as E
 import _q8_flip_model as FM
 
 S_MU, S_SIGMA = 0.003, 0.0009                                  # the scales of the random int8 images
@@ -18,6 +19,23 @@ GEOMS = {
     "conv_c20x6k3p1_1x1": ((6, 20, 3, 3), (5, 20, 1, 1), C3(1, 1, 1)),         # eight of nine taps read padding only
     "linear_70x10_b3": ((10, 70), (3, 70), None),
 }
+
+
+def _edge_geom(name):
+    (KH, KW, H, W, *_), Ci, Co, B, _ = E.GEOMS[name]
+    return (Co, Ci, KH, KW), (B, Ci, H, W), E.geom_conv(name)
+
+
+# The walk's hard geometries, which the Reparameterization kernel sees in tests/test_gpu_q8_edges.py (tests/_q8_edges.py, F): both
+# chains run on one walk (csrc/bt_q8_common.h), so both are held to them.
+EDGE_GEOMS = ("k3x5_2x7_uneven", "k4x4_2x1_s2p3", "k5x5_2x2_p2", "k2x8_3x2_p1x7", "k3x3_1x5")
+GEOMS.update({name: _edge_geom(name) for name in EDGE_GEOMS})
+
+
+def pruned(c):
+    """Whether the kernel prunes the taps of case c: both activations' zero points 128, at most 16 taps, a tap that reads padding only."""
+    wshape, xshape, conv = GEOMS[c["name"]]
+    return conv is not None and c["pairs"][FM.XP][1] == 128 and E.walked_taps(conv, wshape, xshape, c["pairs"][FM.IN][1])[1]
 
 
 def pairs_of(kind, K):
@@ -96,3 +114,17 @@ LAYER_CASES = [
     ("linear_70x10_b3", "default", "none", 8.0),
     ("linear_70x10_b3", "clamps", "mu_only", 1.5),
 ]
+
+# (name, kind, bias, x_std) on the edge geometries, supplied draws, S = 1: pruned taps and, with the 'dict' pairs, padding corrected
+# through both row sums; 25 taps (no pruning) with the default pairs: padding a true zero in both contractions; a pixel tile that
+# crosses images, so that both sign offsets cross an image boundary inside one workgroup. x_std 1.5 spreads x over +-15 levels of the
+# default in-scale 0.1 (and +-30 of the dict's 0.05): neither activation saturates, and K >= 160 spreads o1 and p over tens of levels.
+EDGE_CASES = [
+    ("k3x5_2x7_uneven", "default", "full", 1.5),
+    ("k3x5_2x7_uneven", "dict", "full", 1.5),
+    ("k5x5_2x2_p2", "default", "full", 1.5),
+    ("k2x8_3x2_p1x7", "dict", "full", 1.5),
+]
+# (name, kind, bias, x_std) run with S = 2: on-chip draws on 16 taps of which eight are walked; guard bands around the results and signs
+ON_CHIP_EDGE = ("k4x4_2x1_s2p3", "default", "full", 1.5)
+GUARD_EDGE = ("k3x3_1x5", "default", "full", 1.5)

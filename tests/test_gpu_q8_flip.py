@@ -70,6 +70,62 @@ def test_sign_tensor_convention():
     _same(out, out_q, want_q, want, "scaled sign tensors")
 
 
+# ---------------------------------------------------------------------------- 1b. the walk's edge geometries (tests/_q8_edges.py, F)
+@pytest.mark.parametrize("name,kind,bias,x_std", FC.EDGE_CASES)
+def test_edge_geometry_supplied_draw_equals_model(name, kind, bias, x_std):
+    """k3x5_2x7_uneven: two channel tiles, two pixel tiles, every stride / padding / dilation pair uneven -- with the default pairs (taps
+    pruned) and the 'dict' pairs (nothing pruned, padding corrected through both row sums); k5x5_2x2_p2: 25 taps, so no pruning at zero
+    points 128: padding is a true zero in both contractions; k2x8_3x2_p1x7: a pixel tile crosses images, and with it both sign offsets
+    (test_q8_flip_model_host.py shows the cases are what they are for)."""
+    c = FC.case(name, kind, bias, 1, x_std)
+    want_q, want, _ = FC.model(c)
+    assert len(torch.unique(want_q)) > 16       # the case is not saturated away
+    out, out_q = _launch(c)
+    _same(out, out_q, want_q, want, f"{name} {kind} bias={bias}")
+
+
+def test_pruned_16_tap_geometry_on_chip_draws_equal_the_filled_streams():
+    """k4x4_2x1_s2p3, zero points 128: eight of 16 taps are walked, and the draw of a walked unit is indexed by its TAP, not by its
+    position in the walk -- the launch equals one fed the filled streams (tensors 0 to 3), and the model on them."""
+    from bayesian_torch_amd import _lib
+    from bayesian_torch_amd import functional as F
+    name, kind, bias, x_std = FC.ON_CHIP_EDGE
+    c = dict(FC.case(name, kind, bias, 2, x_std))
+    assert FC.pruned(c)
+    coords = dict(seed=0x5EED0F00D, call=6, layer_id=3, sample0=2)
+    out, out_q = _launch(c, draws=False, **coords)
+    assert _lib.lib().bt_last_kernel_name().decode() == "q8_flip_fwd<i8 32x32x32,64x128,draws on chip>"
+    fill = lambda fn, tensor, shape: fn(coords["seed"], coords["call"], coords["layer_id"], coords["sample0"], tensor, 2, tuple(shape), DEV)
+    c["eps_w"], c["eps_b"] = fill(F.rng_fill_normal, 0, c["wshape"]), fill(F.rng_fill_normal, 1, (c["wshape"][0],))
+    c["sign_in"], c["sign_out"] = fill(F.rng_fill_sign, 2, c["x"].shape[1:]), fill(F.rng_fill_sign, 3, (c["x"].shape[1],) + tuple(out.shape[1:]))
+    out2, out_q2 = _launch(c)
+    torch.cuda.synchronize()
+    assert torch.equal(out_q, out_q2) and torch.equal(out, out2)
+    c = {k: v.cpu() if k in ("eps_w", "eps_b", "sign_in", "sign_out") else v for k, v in c.items()}
+    want_q, want, _ = FC.model(c)
+    assert len(torch.unique(want_q)) > 16
+    _same(out, out_q, want_q, want, f"{name} on chip, S=2")
+    per = out_q.shape[0] // 2
+    assert not torch.equal(out_q[:per], out_q[per:])      # the samples differ
+
+
+def test_guard_bands_on_a_pruned_geometry():
+    """k3x3_1x5, S = 2, three live taps (VU = 6: no multiple of the stage): nothing is written outside out and out_q, every element of
+    out is written, and sign_in and sign_out lie between NaN bands at an odd offset; the packs stay 16-byte aligned."""
+    import _guard as G
+    name, kind, bias, x_std = FC.GUARD_EDGE
+    c = dict(FC.case(name, kind, bias, 2, x_std))
+    want_q, want, _ = FC.model(c)
+    assert FC.pruned(c) and len(torch.unique(want_q)) > 16
+    c["sign_in"], c["sign_out"] = G.place(c["sign_in"].to(DEV), 1), G.place(c["sign_out"].to(DEV), 3)
+    with G.guarded_allocations(lambda shape, dtype: 0 if dtype == torch.int8 else 1) as log:      # (the packs must be 16-byte aligned)
+        out, out_q = _launch(c)
+    torch.cuda.synchronize()
+    assert {g.view.dtype for g in log} == {torch.int8, torch.float32, torch.uint8}      # the packs, out, out_q
+    G.check_all(log)
+    _same(out, out_q, want_q, want, f"{name} between guard bands, S=2")
+
+
 # ---------------------------------------------------------------------------- 2. the layers: on-chip draws, materialize_last_draw
 def _layer_of(c):
     """A quantised Flipout layer holding a case's images, scales, bias tensors and pairs (a checkpoint load), on the device."""

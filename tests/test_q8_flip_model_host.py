@@ -3,9 +3,12 @@ quantized.mul and quantized.add of quint8 tensors over ALL 65 536 pairs of u8 va
 quantisation of the sign tensors at tie and saturating scales, and the whole chain against the literal operator chain
 (quantize_per_tensor, quantized conv2d / linear, quantized.mul, quantized.add) on the layer cases the GPU test runs. The two readings
 torch does not take (tests/_q8_flip_model.py) are shown to give other bytes. No kernels are launched."""
+import math
+
 import pytest
 import torch
 
+import _q8_edges as E
 import _q8_flip_cases as FC
 import _q8_flip_model as FM
 import _q8_model as M
@@ -20,7 +23,7 @@ def _case_sets():
     """... and every set a layer case runs an operator at: (in, sign_in -> xp) and (pert, sign_out -> pert_signed) for mul, (mean,
     pert_signed -> out) for add."""
     mul, add = set(), set()
-    for name, kind, bias, x_std in FC.LAYER_CASES:
+    for name, kind, bias, x_std in FC.LAYER_CASES + FC.EDGE_CASES:
         p = FC.case(name, kind, bias, 1, x_std)["pairs"]
         mul.add(p[FM.IN] + p[FM.SIGN_IN] + p[FM.XP])
         mul.add(p[FM.PERT] + p[FM.SIGN_OUT] + p[FM.PERT_SIGNED])
@@ -137,7 +140,7 @@ def _torch_chain(c, s):
     return out.int_repr(), dict(o1=o1.int_repr(), xp=xp.int_repr(), p=p.int_repr(), ps=ps.int_repr())
 
 
-@pytest.mark.parametrize("name,kind,bias,x_std", FC.LAYER_CASES)
+@pytest.mark.parametrize("name,kind,bias,x_std", FC.LAYER_CASES + FC.EDGE_CASES + [FC.ON_CHIP_EDGE, FC.GUARD_EDGE])
 def test_whole_chain_equals_the_operator_chain(name, kind, bias, x_std):
     """fbgemm: oneDNN's dilated quantised conv corrupts the heap in torch 2.10, and its requantisation ties are its own
     (tests/test_q8_model_host.py)."""
@@ -173,6 +176,36 @@ def test_cases_reach_what_they_are_for():
     c = FC.case("conv_c37x70k3p1_9x7", "dict", "full", 1, 1.5)
     oq, _, mid = FC.model(c)
     assert len(torch.unique(oq)) > 64 and len(torch.unique(mid[0]["p"])) > 64 and len(torch.unique(mid[0]["d"])) > 64
+
+
+def test_edge_cases_reach_what_they_are_for():
+    """The edge-geometry cases (FC.EDGE_CASES, FC.ON_CHIP_EDGE, FC.GUARD_EDGE): the model's u8 output has more than 16 distinct values
+    (the bar of test_gpu_q8_edges.py's uneven-geometry test), the 'dict' cases' intermediates o1, p and p' are not constant, and each
+    geometry is walked the way its case is for: pruned or not, a pixel tile that crosses images, two channel and two pixel tiles."""
+    want_pruned = {("k3x5_2x7_uneven", "default"): True, ("k3x5_2x7_uneven", "dict"): False, ("k5x5_2x2_p2", "default"): False,
+                   ("k2x8_3x2_p1x7", "dict"): False, ("k4x4_2x1_s2p3", "default"): True, ("k3x3_1x5", "default"): True}
+    specs = [(c, 1) for c in FC.EDGE_CASES] + [(FC.ON_CHIP_EDGE, 2), (FC.GUARD_EDGE, 2)]
+    assert {(s[0], s[1]) for s, _ in specs} == set(want_pruned) and {s[0] for s, _ in specs} == set(FC.EDGE_GEOMS)
+    for (name, kind, bias, x_std), S in specs:
+        c = FC.case(name, kind, bias, S, x_std)
+        oq, _, mid = FC.model(c)
+        levels = {k: len(torch.unique(torch.cat([m[k] for m in mid]))) for k in ("o1", "p", "ps")}
+        print(f"{name} {kind} S={S}: {oq.numel()} outputs, {len(torch.unique(oq))} levels; o1 / p / p' levels {levels}; pruned: {FC.pruned(c)}")
+        assert len(torch.unique(oq)) > 16, (name, kind)
+        assert FC.pruned(c) is want_pruned[(name, kind)], (name, kind)
+        if kind == "dict":
+            assert all(p[1] != 128 for p in c["pairs"][2:]) and min(levels.values()) > 1, (name, levels)
+        else:
+            assert all(p[1] == 128 for p in c["pairs"][2:]), name
+        if S == 2:
+            assert not torch.equal(*oq.chunk(2, 0)), name
+    wshape, xshape, conv = FC.GEOMS["k3x5_2x7_uneven"]
+    assert wshape[0] > 64 and xshape[0] * math.prod(E.conv_out(conv, wshape, xshape)) > 128            # two channel tiles, two pixel tiles
+    assert all(a != b for a, b in (wshape[2:], conv["stride"], conv["padding"], conv["dilation"]))
+    wshape, xshape, conv = FC.GEOMS["k2x8_3x2_p1x7"]
+    per = math.prod(E.conv_out(conv, wshape, xshape))
+    assert per < 128 < xshape[0] * per and 128 % per                                                   # pixel 128 lies inside an image
+    assert math.prod(FC.GEOMS["k4x4_2x1_s2p3"][0][2:]) == 16 and math.prod(FC.GEOMS["k5x5_2x2_p2"][0][2:]) == 25
 
 
 def test_the_rejected_forms_change_the_layer_cases():
