@@ -152,6 +152,9 @@ _PROTOS = {
     "bt_q8_flip_linear_fwd": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_q8_flip_params), _vp, _vp, _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
     "bt_q8_observe_w": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
     "bt_minmax_update": (C.c_int, [C.c_int32, C.POINTER(bt_minmax_seg), _vp, _vp]),
+    "bt_q8_flip_observe_conv2d": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, C.POINTER(bt_params), C.POINTER(bt_draws)] + [_vp] * 8),
+    "bt_q8_flip_observe_linear": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_params), C.POINTER(bt_draws)] + [_vp] * 8),
+    "bt_q8_flip_observe_x": (C.c_int, [C.c_int64, C.c_int32, _vp, C.c_int64, _vp, C.POINTER(bt_rng)] + [_vp] * 5),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -16,6 +16,11 @@ EnvKnob g_force_generic{"BT_FORCE_GENERIC", [](const char* e) { return e ? 1 : 0
 static unsigned long long* g_dbg = nullptr;
 static thread_local long long g_launch_info[16] = {};
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// tile geometry of the launch just made (bt_last_launch_info)
+static void record_plan(const FwdArgs& r, int fused_kl) {
+  const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, fused_kl, 0};
+  for (int i = 0; i < 16; ++i) g_launch_info[i] = v[i];
+}
 
 // One forward call as the C ABI hands it over. u: the input dilation and explicit padding of bt_*_conv2d_updil_fwd (g holds the REAL
 // input dims), or null. w: the depth window of bt_*_conv2d_dwin_fwd (g describes the launch over the VIRTUAL, unfolded operand), or null.
@@ -216,9 +221,7 @@ static int run(const Call& c, bt_stream_t stream) {
   c.fill_args(kl_after, a);
   int rc = c.dispatch(a, r, (hipStream_t)stream);
   if (rc != BT_OK) return rc;
-  // tile geometry of the launch just made (bt_last_launch_info)
-  const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, r.do_kl, 0};
-  for (int i = 0; i < 16; ++i) g_launch_info[i] = v[i];
+  record_plan(r, r.do_kl);
   if (kl_after) {
     const bt_params* p = c.p;
     const float* mu[2] = {p->mu_w, p->mu_b};
@@ -324,9 +327,59 @@ extern "C" int bt_lowrank_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const f
   a.lowrank = 1, a.lr_R = R, a.lr_L = R > 0 ? L : mean, a.lr_z = (eps_w && R > 0) ? z : nullptr, a.lr_mean_stride = mean_stride, a.lr_sd = sqrtf(d);
   const int rc = launch_lowrank(a, r, (hipStream_t)stream);
   if (rc != BT_OK) return rc;
-  const long long v[16] = {r.total_blocks, r.m_tiles, r.n_tiles, r.S, r.t_NI, r.t_R, r.t_Wt, r.pixel_major, r.row_taps, r.kl_slices, r.G, r.n_bt, r.n_rt, r.n_ct, 0, 0};
-  for (int i = 0; i < 16; ++i) g_launch_info[i] = v[i];
+  record_plan(r, 0);
   return BT_OK;
+}
+
+// The observing two-contraction launch of a calibrating Flipout layer (include/bt_hip.h; bt_fused_flipout_obs.hip): the float Flipout
+// call's checks of operands, draws, geometry and 32-bit offsets, then the general kernel's OBS form.
+namespace bt {
+int launch_flipout_obs(bool linear, const FwdArgs& a, FwdArgs& ran, hipStream_t stream);   // bt_fused_flipout_obs.hip
+
+static int observe_flip(const char* who, bool linear, const bt_conv2d_geom& g, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p, const bt_draws* d,
+                        const float* coef, const float* shift, float* mean_mm, float* pert_mm, float* pert_signed_mm, float* sign_out_mm, uint32_t* nonfinite,
+                        bt_stream_t stream) {
+  char msg[256];
+  auto fail = [&](int code, const char* what) {
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return set_error(code, msg);
+  };
+  if (!mean_mm || !pert_mm || !pert_signed_mm || !sign_out_mm || !nonfinite) return fail(BT_ERR_BAD_ARG, "null statistics / nonfinite");
+  uintptr_t bits = (uintptr_t)x | (uintptr_t)coef | (uintptr_t)shift | (uintptr_t)mean_mm | (uintptr_t)pert_mm | (uintptr_t)pert_signed_mm | (uintptr_t)sign_out_mm | (uintptr_t)nonfinite;
+  if (p) bits |= (uintptr_t)p->mu_w | (uintptr_t)p->rho_w | (uintptr_t)p->mu_b | (uintptr_t)p->rho_b;
+  if (d) bits |= (uintptr_t)d->eps_w | (uintptr_t)d->eps_b | (uintptr_t)d->sign_in | (uintptr_t)d->sign_out;
+  if (bits & 3u) return fail(BT_ERR_BAD_ARG, "a pointer that is not 4-byte aligned");
+  if (d && d->rng.flags) return fail(BT_ERR_BAD_ARG, "supplied draws in the natural layouts only (bt_rng.flags must be 0)");
+  bt_params pp;
+  if (p) pp = *p, pp.mu_packed = pp.sigma_packed = nullptr, pp.prior_kind = BT_PRIOR_NORMAL;   // (the general kernel reads the natural layout)
+  bt_epilogue ep;
+  memset(&ep, 0, sizeof(ep));
+  ep.scale = coef, ep.shift = shift;
+  const Call c{true, linear, g, S, x, x_sample_stride, p ? &pp : nullptr, d, &ep, mean_mm, nullptr, nullptr, 0, who, nullptr, nullptr};
+  if (int rc = c.validate()) return rc;
+  if (g.groups != 1) return fail(BT_ERR_UNSUPPORTED, "groups must be 1 (the INT8 Flipout layers')");
+  if (S > 65535) return fail(BT_ERR_UNSUPPORTED, "S > 65535");
+  FwdArgs a, r;
+  c.fill_args(false, a);
+  a.out = nullptr, a.out_vec4 = 0;   // nothing is stored
+  a.obs_dst[0] = mean_mm, a.obs_dst[1] = pert_mm, a.obs_dst[2] = pert_signed_mm, a.obs_dst[3] = sign_out_mm, a.obs_nonfinite = nonfinite;
+  if (int rc = launch_flipout_obs(linear, a, r, (hipStream_t)stream)) return rc;
+  record_plan(r, 0);
+  return BT_OK;
+}
+}  // namespace bt
+
+extern "C" int bt_q8_flip_observe_conv2d(const bt_conv2d_geom* g, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p, const bt_draws* d,
+                                         const float* coef, const float* shift, float* mean_mm, float* pert_mm, float* pert_signed_mm, float* sign_out_mm,
+                                         uint32_t* nonfinite, bt_stream_t stream) {
+  if (!g) return bt::set_error(BT_ERR_BAD_ARG, "bt_q8_flip_observe_conv2d: null geometry");
+  return bt::observe_flip("bt_q8_flip_observe_conv2d", false, *g, S, x, x_sample_stride, p, d, coef, shift, mean_mm, pert_mm, pert_signed_mm, sign_out_mm, nonfinite, stream);
+}
+extern "C" int bt_q8_flip_observe_linear(int32_t B, int32_t In, int32_t Out, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p, const bt_draws* d,
+                                         const float* coef, const float* shift, float* mean_mm, float* pert_mm, float* pert_signed_mm, float* sign_out_mm,
+                                         uint32_t* nonfinite, bt_stream_t stream) {
+  return bt::observe_flip("bt_q8_flip_observe_linear", true, bt::linear_geom(B, In, Out), S, x, x_sample_stride, p, d, coef, shift, mean_mm, pert_mm, pert_signed_mm,
+                          sign_out_mm, nonfinite, stream);
 }
 
 extern "C" size_t bt_fused_scratch_bytes(const bt_conv2d_geom* g, int32_t S) {

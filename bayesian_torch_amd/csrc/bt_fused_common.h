@@ -71,21 +71,29 @@ struct FwdArgs {
   long long lr_mean_stride;
   float lr_sd;
   int lr_R;
+  // observing launch (bt_q8_flip_observe_conv2d / _linear, the general Flipout kernel's OBS form): nothing is stored through `out`; the
+  // ranges of mean, pert, pert_signed and sign_out (bt_hip.h) are merged into the four (min, max) pairs obs_dst[0..3] and the non-finite
+  // values counted into *obs_nonfinite. All null on every other launch.
+  float* obs_dst[4];
+  unsigned* obs_nonfinite;
 };
 
 // Plan-only digest of the argument block: every field in declaration order, without the two padding holes (behind sample0, at the end).
 // The depth-window fields behind inv_uw are folded in only when the launch is one, and the low-rank fields behind those likewise: every
-// other launch hashes the bytes it always did.
+// other launch hashes the bytes it always did. The observer fields behind those: only on an observing launch.
 inline uint64_t digest_arg(uint64_t h, const FwdArgs& a) {
   constexpr size_t hole = offsetof(FwdArgs, sample0) + sizeof(uint32_t), end = offsetof(FwdArgs, inv_uw) + sizeof(uint32_t);
   constexpr size_t end_dw = offsetof(FwdArgs, inv_do) + sizeof(uint32_t);
   constexpr size_t end_lr = offsetof(FwdArgs, lr_R) + sizeof(int);
-  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && offsetof(FwdArgs, dwin) == end && offsetof(FwdArgs, lowrank) == end_dw && sizeof(FwdArgs) == end_lr,
+  constexpr size_t end_obs = offsetof(FwdArgs, obs_nonfinite) + sizeof(unsigned*);
+  static_assert(offsetof(FwdArgs, call_base) == hole + 4 && offsetof(FwdArgs, dwin) == end && offsetof(FwdArgs, lowrank) == end_dw &&
+                    offsetof(FwdArgs, obs_dst) == end_lr && sizeof(FwdArgs) == end_obs,
                 "FwdArgs padding moved: name the holes here");
   h = fnv1a(h, &a, hole);
   h = fnv1a(h, &a.call_base, end - offsetof(FwdArgs, call_base));
   if (a.dwin) h = fnv1a(h, &a.dwin, end_dw - end);
-  return a.lowrank ? fnv1a(h, &a.lowrank, end_lr - end_dw) : h;
+  if (a.lowrank) h = fnv1a(h, &a.lowrank, end_lr - end_dw);
+  return a.obs_nonfinite ? fnv1a(h, &a.obs_dst, end_obs - end_lr) : h;
 }
 
 // The split-precision chains (bt_fused_split.hip, bt_fused_split_flip.hip), for every translation unit that calls them. Each works on

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "bt_fused_common.h"
+#include "bt_observe.h"
 
 namespace bt {
 
@@ -142,7 +143,13 @@ __device__ __forceinline__ double block_sum_all(double v, double* scratch) {  //
 // load of the element's R <= 4 values of L, z_s is taken once per workgroup and sample into registers (tensor 4 of the draw streams, or
 // read), eps is the stream the other forms draw. No softplus, no bias stage, no KL sweep. An instantiation unit of its own
 // (bt_fused_lowrank.hip), so that the other forms carry none of it.
-template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false, bool DWIN = false, bool LOWRANK = false>
+// OBS: the observing launch of a calibrating Flipout layer (FwdArgs::obs_dst: bt_q8_flip_observe_conv2d / _linear). Both contractions run
+// as in the forward; the output stage forms mean = (acc0 + bias0) * scale + shift, pert = (acc1 + bias1) * scale and pert_signed =
+// pert * s_out of every valid element -- one rounding per operation -- and keeps their ranges and s_out's instead of storing anything;
+// the workgroup's ranges are merged where the two role arms have rejoined (obs_merge: the producer waves bring empty ranges). Supplied
+// signs are read as obs_sign reads them (negative: -1, anything else +1). No residual, no ReLU, no KL, no 16-byte stores. An
+// instantiation unit of its own (bt_fused_flipout_obs.hip), so that the other forms carry none of it.
+template <int BN, int BM, int CWN, bool FLIP, bool LINEAR, bool TRANS, bool INJ, bool UPD = false, bool DWIN = false, bool LOWRANK = false, bool OBS = false>
 __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   unsigned long long* const dbg_ = kStamps ? a.dbg : nullptr;  // stage stamps: diagnostic build only (make STAMPS=1)
   constexpr int CWM = 4 / CWN;
@@ -156,6 +163,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   static_assert(!UPD || (!LINEAR && !INJ), "the input-dilated form: convolutions, on-chip draws");
   static_assert(!DWIN || (!LINEAR && !INJ && !UPD), "the depth-window form: convolutions, on-chip draws, not input-dilated");
   static_assert(!LOWRANK || (!FLIP && !LINEAR && !UPD && !DWIN), "the low-rank form: plain convolutions, Reparameterization");
+  static_assert(!OBS || (FLIP && !UPD && !DWIN && !LOWRANK), "the observing form: Flipout, plain convolutions and Linear");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];  // ONE LDS object
   int4* const taptab = reinterpret_cast<int4*>(smem + 2 * BUF_WORDS);
@@ -188,6 +196,16 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
   const RngKey key_w = weight_key(a);
   uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams (injected: the signs are read)
   if (FLIP && !INJ) sign_keys(a, key_w, sample, &skey_in, &skey_out);
+  [[maybe_unused]] auto read_sign = [](float v) -> float {  // a supplied sign as this form uses it
+    if constexpr (OBS) return obs_sign(v);
+    else return v;
+  };
+  [[maybe_unused]] Range obs_r[OBS ? 4 : 1];  // OBS: mean, pert, pert_signed, s_out of this thread's valid output elements
+  [[maybe_unused]] unsigned obs_bad = 0;
+  if constexpr (OBS) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) obs_r[k].lo = INFINITY, obs_r[k].hi = -INFINITY;
+  }
 
   // ---- active taps of this tile (wave 0: ballot compaction, ascending tap order) ---------------------------------
   if (wave == 0) {
@@ -651,7 +669,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
             const int idx = (4 * kq + j) * XS + rl;
             const float v = ((xok >> (4 * p + j)) & 1ull) ? xv[4 * p + j] : 0.f;
             Xt0[idx] = v;
-            if (FLIP) Xt1[idx] = __fmul_rn(v, INJ ? xs_[4 * p + j] : hash_sign(skey_in, xo[4 * p + j]));
+            if (FLIP) Xt1[idx] = __fmul_rn(v, INJ ? read_sign(xs_[4 * p + j]) : hash_sign(skey_in, xo[4 * p + j]));
           }
         }
       }
@@ -665,7 +683,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
           for (int c = 0; c < CCs; ++c) {
             const float v = ((xok >> (i * CCs + c)) & 1ull) ? xv[i * CCs + c] : 0.f;
             Xt0[c * PCH + pos] = v;
-            if (FLIP) Xt1[c * PCH + pos] = __fmul_rn(v, INJ ? xs_[i * CCs + c] : hash_sign(skey_in, xo[i * CCs + c]));
+            if (FLIP) Xt1[c * PCH + pos] = __fmul_rn(v, INJ ? read_sign(xs_[i * CCs + c]) : hash_sign(skey_in, xo[i * CCs + c]));
           }
         }
       }
@@ -677,7 +695,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
           const int idx = ((t << LCC) + xg + c * NG) * XS + xm;
           const float v = ((xok >> (t * CPT + c)) & 1ull) ? xv[t * CPT + c] : 0.f;
           Xt0[idx] = v;
-          if (FLIP) Xt1[idx] = __fmul_rn(v, INJ ? xs_[t * CPT + c] : hash_sign(skey_in, xo[t * CPT + c]));
+          if (FLIP) Xt1[idx] = __fmul_rn(v, INJ ? read_sign(xs_[t * CPT + c]) : hash_sign(skey_in, xo[t * CPT + c]));
         }
     } else {
       const int KC = na_s << LCC;
@@ -687,7 +705,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
         if (kc < KC) {
           const float v = ((xok >> q) & 1ull) ? xv[q] : 0.f;
           Xt0[kc * XS + xm] = v;
-          if (FLIP) Xt1[kc * XS + xm] = __fmul_rn(v, INJ ? xs_[q] : hash_sign(skey_in, xo[q]));
+          if (FLIP) Xt1[kc * XS + xm] = __fmul_rn(v, INJ ? read_sign(xs_[q]) : hash_sign(skey_in, xo[q]));
         }
       }
     }
@@ -837,7 +855,7 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
     const float* const sout_s = (FLIP && INJ) ? a.sign_out + (long long)s * a.out_elems : nullptr;
     const float* const res_s = a.ep_res ? a.ep_res + (long long)s * a.ep_res_stride : nullptr;
     const bool relu = a.ep_relu != 0;
-    if (TRANS && a.out_vec4) {
+    if (!OBS && TRANS && a.out_vec4) {
       // spatial NCHW output through the D[m][co] orientation: a lane owns ONE output channel (bias / scale / shift are lane
       // constants) and registers 4q..4q+3 are 4 consecutive output positions -> one 16-byte store (and residual load) per 4
       // values. The host guarantees Ho*Wo % 4 == 0 and 16-byte aligned tensors, so a quad never straddles an image.
@@ -920,7 +938,17 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
           }
           if constexpr (FLIP) {
   #pragma unroll
-            for (int r = 0; r < 16; ++r) so[r] = INJ ? sout_s[oi[r]] : hash_sign(skey_out, oi[r]);
+            for (int r = 0; r < 16; ++r) so[r] = INJ ? read_sign(sout_s[oi[r]]) : hash_sign(skey_out, oi[r]);
+          }
+          if constexpr (OBS) {  // ranges instead of stores: only the tile's valid elements (okv) ever reach one
+  #pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float mean = __fadd_rn(__fmul_rn(__fadd_rn(acc[0][i][j][r], bias0[col[r]]), osc[col[r]]), osh[col[r]]);
+              const float pert = __fmul_rn(__fadd_rn(acc[NW - 1][i][j][r], bias1[col[r]]), osc[col[r]]);
+              const float psig = __fmul_rn(pert, so[r]);
+              if (okv[r]) obs_r[0].take(mean, obs_bad), obs_r[1].take(pert, obs_bad), obs_r[2].take(psig, obs_bad), obs_r[3].take(so[r], obs_bad);
+            }
+            continue;
           }
   #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -934,6 +962,11 @@ __global__ __launch_bounds__(kThreads) void fused_fwd_kernel(const FwdArgs a) {
         }
       }
     }
+  }
+
+  if constexpr (OBS) {  // both arms have rejoined: every wave of the workgroup merges (behind the bias words, in the dead stage memory)
+    float* const dst[4] = {a.obs_dst[0], a.obs_dst[1], a.obs_dst[2], a.obs_dst[3]};
+    obs_merge<4, kThreads / 64>(obs_r, obs_bad, dst, a.obs_nonfinite, smem + 4 * BN);
   }
 
   if (dbg_ && blockIdx.x == 0 && tid == 0) dbg_[126] = __builtin_amdgcn_s_memtime();

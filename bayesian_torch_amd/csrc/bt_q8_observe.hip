@@ -6,97 +6,12 @@
 //     supplied ones) and merges the ranges of q = sigma * coef, m = mu * coef, eps, t = q * eps and w = m + t -- the five qint8 stubs
 //     in the reference's order -- into stats[10]; nothing weight-sized is written;
 //   * bt_minmax_update merges the ranges of up to four fp32 tensors (a layer's input and output) into (min, max) pairs.
-// Reduction: per thread, wavefront shuffles, one LDS step per workgroup, then at most ONE vector atomic per statistic and workgroup on
-// the value's bit pattern (none when a plain load shows that the value would not widen the statistic). The bits of a non-negative float order like a signed integer's and those of a negative float in reverse like
-// an unsigned integer's, so a float maximum is a signed-integer atomic max for v >= 0 and an unsigned-integer atomic min for v < 0
-// (the minimum: the mirror image); -0 is made +0 first and non-finite values never reach the atomics (they are counted instead).
-// Minimum and maximum have no order: the result does not depend on how the workgroups are scheduled. A pair starts at (+inf, -inf)
-// and a call can only widen it.
-#include "bt_api_internal.h"
+// The reduction, the (min, max) pair and the merge: bt_observe.h (the INT8 Flipout layers' observers share them).
+#include "bt_observe.h"
 
 namespace bt {
 
-constexpr int kObsThreads = 256;
 constexpr int kObsStats = 5;   // sigma, mu, eps, mul, add
-constexpr int kObsGrid = 2048;   // workgroups of a launch, at most (256 CUs x 8)
-
-__device__ __forceinline__ bool obs_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
-
-struct Range {
-  float lo, hi;
-  __device__ __forceinline__ void take(float v, unsigned& bad) {
-    if (obs_finite(v)) {
-      lo = fminf(lo, v);
-      hi = fmaxf(hi, v);
-    } else {
-      ++bad;
-    }
-  }
-};
-
-__device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
-  v = __fadd_rn(v, 0.0f);   // -0 -> +0
-  if (v >= 0.0f)
-    __hip_atomic_fetch_min(reinterpret_cast<int*>(addr), __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else
-    __hip_atomic_fetch_max(reinterpret_cast<unsigned*>(addr), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-  v = __fadd_rn(v, 0.0f);
-  if (v >= 0.0f)
-    __hip_atomic_fetch_max(reinterpret_cast<int*>(addr), __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else
-    __hip_atomic_fetch_min(reinterpret_cast<unsigned*>(addr), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The workgroup's ranges r[0 .. K) and its count of non-finite values -> dst[k] (a (min, max) pair each) and *nonfinite.
-// lds: 4 * (2 * K + 1) words. Every thread of the workgroup calls it.
-template <int K>
-__device__ __forceinline__ void obs_merge(Range (&r)[K], unsigned bad, float* const (&dst)[K], unsigned* nonfinite, float* lds) {
-  constexpr int W = 2 * K + 1;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      r[k].lo = fminf(r[k].lo, __shfl_xor(r[k].lo, o, 64));
-      r[k].hi = fmaxf(r[k].hi, __shfl_xor(r[k].hi, o, 64));
-    }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) lds[wv * W + 2 * k] = r[k].lo, lds[wv * W + 2 * k + 1] = r[k].hi;
-    lds[wv * W + 2 * K] = __uint_as_float(bad);
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < 2 * K) {
-    const bool is_max = t & 1;
-    float v = lds[t];
-#pragma unroll
-    for (int w = 1; w < kObsThreads / 64; ++w) v = is_max ? fmaxf(v, lds[w * W + t]) : fminf(v, lds[w * W + t]);
-    // (still +-inf: the workgroup met no finite value.) A statistic only ever widens, so a value that does not widen what a plain
-    // load sees -- however stale -- cannot widen the current one: most workgroups issue no atomic at all, and the ones that do are
-    // not queued behind thousands of others on the same ten words.
-    if (obs_finite(v)) {
-      float* const p = dst[t >> 1] + (is_max ? 1 : 0);
-      const float cur = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (is_max ? v > cur : v < cur) {
-        if (is_max)
-          atomic_max_f32(p, v);
-        else
-          atomic_min_f32(p, v);
-      }
-    }
-  } else if (t == 2 * K) {
-    unsigned b = 0;
-#pragma unroll
-    for (int w = 0; w < kObsThreads / 64; ++w) b += __float_as_uint(lds[w * W + 2 * K]);
-    if (b) __hip_atomic_fetch_add(nonfinite, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
 
 // One weight: each product and the sum ONE fp32 rounding, as quantize() (mu * coef, sigma * coef) and the float forward
 // (sigma * eps, mu + sigma * eps) form them.

@@ -762,11 +762,14 @@ def q8_flip_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=N
 
 # ---------------------------------------------------------------------------- calibration of the INT8 layers (csrc/bt_q8_observe.hip)
 CALIB_ROWS = ("sigma", "mu", "eps", "mul", "add", "in", "out")      # the rows of a layer's ``calib_minmax`` [7, 2]: (min, max) pairs
+# ... and of a Flipout layer's [13, 2]: bt_q8_observe_w's five rows ("add" is a quantity Flipout never forms: conversion ignores it), then
+# the reference's eight quint8 stubs. The ten a quant_dict takes (Q8_FLIP_PAIRS) are rows 2, 3 and 5..12.
+CALIB_FLIP_ROWS = ("sigma", "mu", "eps", "delta", "add", "in", "mean", "sign_in", "sign_out", "xp", "pert", "pert_signed", "out")
 
 
-def calib_buffers(device=None):
-    """-> (calib_minmax fp32 [7, 2] of (+inf, -inf) pairs, calib_nonfinite int32 [1] of 0): empty statistics."""
-    mm = torch.empty((len(CALIB_ROWS), 2), dtype=torch.float32, device=device)
+def calib_buffers(device=None, rows=len(CALIB_ROWS)):
+    """-> (calib_minmax fp32 [rows, 2] of (+inf, -inf) pairs, calib_nonfinite int32 [1] of 0): empty statistics."""
+    mm = torch.empty((rows, 2), dtype=torch.float32, device=device)
     mm[:, 0], mm[:, 1] = float("inf"), float("-inf")
     return mm, torch.zeros(1, dtype=torch.int32, device=device)
 
@@ -825,3 +828,62 @@ def minmax_update(segments, nonfinite):
     arr = (_lib.bt_minmax_seg * len(keep))(*[_lib.bt_minmax_seg(x.data_ptr(), x.numel(), dst.data_ptr()) for x, dst in keep])
     with _lib.on(dev):
         _lib.check(_lib.lib().bt_minmax_update(len(keep), arr, nonfinite.data_ptr(), _lib.stream_ptr(dev)))
+
+
+def _pair(t, what):
+    _calib_dev(t, what, torch.float32)
+    if t.numel() != 2:
+        raise RuntimeError(f"{what} must be a (min, max) pair")
+    return t.data_ptr()
+
+
+def q8_flip_observe_x(x, in_mm, sign_in_mm, xp_mm, nonfinite, *, S=1, shared_x=True, sign_in=None, seed=0, call=0, layer_id=0, sample0=0, call_base=None):
+    """The input-side observers of a calibrating Flipout layer (bt_q8_flip_observe_x): merge the ranges of x, sign_in and x * sign_in
+    over S samples into the three (min, max) pairs. x: one batch shared by the samples, or S stacked ones (``shared_x`` False);
+    sign_in: fp32 [S, one sample's x] supplied (negative: -1, anything else +1), or None for the on-chip tensor 2 stream."""
+    x, sign_in = _lib.dev_f32(x, "x"), _lib.dev_f32(sign_in, "sign_in")
+    _calib_dev(nonfinite, "nonfinite", torch.int32)
+    _no_capture(x.device, "q8_flip_observe_x")
+    per = 1 if shared_x else S
+    if x.numel() == 0 or x.numel() % per:
+        raise RuntimeError("q8_flip_observe_x: x must be non-empty and hold S stacked batches when it is not shared")
+    n = x.numel() // per
+    if sign_in is not None and sign_in.numel() != S * n:
+        raise RuntimeError(f"q8_flip_observe_x: sign_in holds {sign_in.numel()} elements, S={S} samples of x need {S * n}")
+    R = _rng(seed, call, layer_id, sample0, call_base)
+    with _lib.on(x.device):
+        _lib.check(_lib.lib().bt_q8_flip_observe_x(n, S, x.data_ptr(), 0 if shared_x else n, _lib.ptr(sign_in), None if sign_in is not None else C.byref(R),
+                                                   _pair(in_mm, "in_mm"), _pair(sign_in_mm, "sign_in_mm"), _pair(xp_mm, "xp_mm"), nonfinite.data_ptr(),
+                                                   _lib.stream_ptr(x.device)))
+
+
+def q8_flip_observe(x, mu_w, rho_w, mu_b, rho_b, mean_mm, pert_mm, pert_signed_mm, sign_out_mm, nonfinite, *, conv=None, S=1, shared_x=True, coef=None,
+                    shift=None, eps_w=None, eps_b=None, sign_in=None, sign_out=None, seed=0, call=0, layer_id=0, sample0=0, call_base=None):
+    """The observing two-contraction launch of a calibrating Flipout layer (bt_q8_flip_observe_conv2d / _linear; include/bt_hip.h):
+    ``_fused_forward``'s operands of a Flipout call -- the draws all supplied or all None -- and an optional per-channel coef / shift
+    (the BatchNorm to be folded). Merges the ranges of the mean output, the perturbation output, the perturbation output times sign_out
+    and sign_out, over every output element of all S samples, into the four (min, max) pairs. Nothing output-sized is written."""
+    x = _lib.dev_f32(x, "input")
+    dev = x.device
+    tens = dict(mu_w=mu_w, rho_w=rho_w, mu_b=mu_b, rho_b=rho_b, eps_w=eps_w, eps_b=eps_b, sign_in=sign_in, sign_out=sign_out, coef=coef, shift=shift)
+    for k, t in tens.items():
+        t = _lib.dev_f32(t, k)
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{k} on {t.device} but input on {dev}")
+        tens[k] = t
+    _calib_dev(nonfinite, "nonfinite", torch.int32)
+    _no_capture(dev, "q8_flip_observe")
+    B, geom, x_elems, tail = _geometry(x, mu_w, conv, S, shared_x)
+    n_so, Co = B * math.prod(tail), mu_w.shape[0]
+    for k, n in (("eps_w", S * mu_w.numel()), ("eps_b", S * Co), ("sign_in", S * x_elems), ("sign_out", S * n_so), ("coef", Co), ("shift", Co)):
+        if tens[k] is not None and tens[k].numel() != n:
+            raise RuntimeError(f"q8_flip_observe: {k} holds {tens[k].numel()} elements, this launch needs {n}")
+    P = _lib.bt_params(tens["mu_w"].data_ptr(), tens["rho_w"].data_ptr(), _lib.ptr(tens["mu_b"]), _lib.ptr(tens["rho_b"]), None, None, None, None, None, None,
+                       _lib.PRIOR_NORMAL, 0)
+    D = _lib.bt_draws(_lib.ptr(tens["eps_w"]), _lib.ptr(tens["eps_b"]), _lib.ptr(tens["sign_in"]), _lib.ptr(tens["sign_out"]),
+                      _rng(seed, call, layer_id, sample0, call_base))
+    tail_args = (S, x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), C.byref(D), _lib.ptr(tens["coef"]), _lib.ptr(tens["shift"]), _pair(mean_mm, "mean_mm"),
+                 _pair(pert_mm, "pert_mm"), _pair(pert_signed_mm, "pert_signed_mm"), _pair(sign_out_mm, "sign_out_mm"), nonfinite.data_ptr(), _lib.stream_ptr(dev))
+    L = _lib.lib()
+    with _lib.on(dev):
+        _lib.check(L.bt_q8_flip_observe_linear(B, geom.Ci, geom.Co, *tail_args) if conv is None else L.bt_q8_flip_observe_conv2d(C.byref(geom), *tail_args))

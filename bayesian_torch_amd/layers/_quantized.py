@@ -326,15 +326,17 @@ class _QuantizedFlipoutLayer(_QuantizedLayer):
     signs are fair coins, as the float Flipout layers define them.
 
     ``quant_dict``: a list of TEN ``{'scale', 'zero_point'}`` entries in the reference's order -- eps, delta, in, mean, sign_in, sign_out,
-    xp, pert, pert_signed, out -- supplied by the caller: Flipout layers are not calibrated here (``prepare()`` raises). ``inject_draw``:
+    xp, pert, pert_signed, out -- supplied by the caller, or built by ``convert`` from the statistics of a FLOAT Flipout layer that was
+    calibrated (``prepare(flipout=True)``, section 4.6i); ``prepare()`` of this converted layer raises. ``inject_draw``:
     dict(eps_w [S, *weight shape], eps_b [S, Co] or None, sign_in fp32 [S, B, *x.shape[1:]], sign_out fp32 [S, B, Co, ...]); in a sign
     tensor a negative value means -1 and anything else +1. rng mode "torch" draws eps_w, eps_b, sign_in, sign_out per sample."""
 
     _forward_fn = staticmethod(F.q8_flip_forward)
 
     def prepare(self):
-        raise NotImplementedError("Flipout layers are not calibrated here (the two partial outputs are never materialised by the float kernels): supply "
-                                  f"quant_dict, a list of ten {{'scale', 'zero_point'}} entries ({', '.join(F.Q8_FLIP_PAIRS)})")
+        raise NotImplementedError("calibration happens on the float Flipout layer (quantization.prepare(model, flipout=True), forwards, then "
+                                  "convert(model, flipout=True)), not on the converted one; or supply quant_dict, a list of ten "
+                                  f"{{'scale', 'zero_point'}} entries ({', '.join(F.Q8_FLIP_PAIRS)})")
 
     def _pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
         """The ten (scale, zero point) pairs of this call, in ``functional.Q8_FLIP_PAIRS``' order."""

@@ -5,7 +5,8 @@ Same module walk as the reference's, in place: a leaf whose class name contains 
 with it, ``conv1/bn1 ... conv3/bn3`` of a module and a two-element ``downsample`` Sequential are folded (the BatchNorm goes into
 the int8 images and the fp32 bias and becomes ``Identity``) -- and, as in the reference, a ``Conv2dReparameterization`` that no such
 rule names is left float; that is said in a ``UserWarning`` naming the layer, since the model then mixes float and int8 layers. Converted are ``LinearReparameterization`` and ``Conv2dReparameterization`` (groups 1) and, with ``flipout=True`` only, ``LinearFlipout`` and
-``Conv2dFlipout`` (groups 1; ``QuantizedLinearFlipout`` / ``QuantizedConv2dFlipout``, whose ten-entry ``quant_dict`` comes from the caller);
+``Conv2dFlipout`` (groups 1; ``QuantizedLinearFlipout`` / ``QuantizedConv2dFlipout``, whose ten-entry ``quant_dict`` comes from the caller
+or from calibration: ``quantization.prepare(model, flipout=True)``);
 any other Bayesian layer raises NotImplementedError naming its class (Flipout without the keyword, Conv1d / Conv3d, ConvTranspose, LSTM,
 groups > 1). An unfused BatchNorm is left as it
 is (the reference swaps in ``torch.nn.quantized.BatchNorm2d``, a CPU-only module; activations between layers stay fp32 here).
@@ -26,7 +27,7 @@ def _quantized_class(d, flipout=False):
     name = d.__class__.__name__
     if name in _CONVERTIBLE_FLIPOUT and not flipout:
         raise NotImplementedError(f"bnn_to_qbnn: {name} is converted on request only: pass flipout=True (its INT8 layer takes a ten-entry quant_dict "
-                                  "from the caller and cannot be calibrated here)")
+                                  "from the caller or from prepare(flipout=True))")
     if name not in _CONVERTIBLE + _CONVERTIBLE_FLIPOUT:
         raise NotImplementedError(f"bnn_to_qbnn: {name} has no INT8 counterpart here (converted: {', '.join(_CONVERTIBLE)}; with flipout=True: "
                                   f"{', '.join(_CONVERTIBLE_FLIPOUT)})")
@@ -38,21 +39,28 @@ def _quantized_class(d, flipout=False):
 def _calibrated_dict(d, name):
     """The ``quant_dict`` of a layer that was calibrated (``prepare()`` + forwards): [eps, mul, add, in, out] as {'scale', 'zero_point'} --
     the reference's ``quant_dict[2:] + quint`` selection (models/bnn_to_qbnn.py:105-111) -- from the statistics the observer kernels
-    left on the device. ONE host read: the seven (min, max) pairs and whether any non-finite value was met."""
+    left on the device; a Flipout layer's ten entries in ``functional.Q8_FLIP_PAIRS`` order. ONE host read: the seven (thirteen)
+    (min, max) pairs and whether any non-finite value was met."""
     import torch
-    from bayesian_torch_amd.functional import CALIB_ROWS
+    from bayesian_torch_amd.functional import CALIB_FLIP_ROWS, CALIB_ROWS, Q8_FLIP_PAIRS
     from bayesian_torch_amd.quantization.quantize import observer_qparams
+    flip = bool(getattr(d, "_flip", False))
+    if flip:      # ten of the thirteen rows, in the quant_dict's order: eps and delta symmetric qint8, the other eight affine quint8
+        CALIB_ROWS = CALIB_FLIP_ROWS
+        take = [(CALIB_FLIP_ROWS.index(n), torch.qint8 if n in ("eps", "delta") else torch.quint8) for n in Q8_FLIP_PAIRS]
+    else:
+        take = [(row, torch.qint8 if row < 5 else torch.quint8) for row in range(2, len(CALIB_ROWS))]
     who = f"{type(d).__name__} '{name}'" if name else type(d).__name__
     host = torch.cat([d.calib_minmax.detach().reshape(-1).to(torch.float32), (d.calib_nonfinite.detach().reshape(-1) != 0).to(torch.float32)]).cpu()
     mm, bad = host[:-1].reshape(len(CALIB_ROWS), 2), bool(host[-1])
     if bad:
         raise RuntimeError(f"bnn_to_qbnn: {who} met non-finite values while calibrating (calib_nonfinite != 0): its ranges cannot be trusted")
     out = []
-    for row in range(2, len(CALIB_ROWS)):
+    for row, dtype in take:
         if not bool(torch.isfinite(mm[row]).all()):
             raise RuntimeError(f"bnn_to_qbnn: {who} was prepared but its '{CALIB_ROWS[row]}' statistics are still empty: run the calibration batches "
                                "(under torch.no_grad()) between prepare() and convert()")
-        scale, zp = observer_qparams(mm[row, 0], mm[row, 1], torch.qint8 if row < 5 else torch.quint8)
+        scale, zp = observer_qparams(mm[row, 0], mm[row, 1], dtype)
         out.append({"scale": float(scale), "zero_point": int(zp)})
     return out
 

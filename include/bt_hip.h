@@ -617,6 +617,41 @@ typedef struct bt_minmax_seg {
 } bt_minmax_seg;
 int bt_minmax_update(int32_t n_segs, const bt_minmax_seg *segs, uint32_t *nonfinite, bt_stream_t stream);
 
+/* Calibration of the INT8 Flipout layers: the activation-side observers of the reference's twelve-observer flow
+ * (flipout_layers/conv_flipout.py:339-345, :419-434; linear_flipout.py:115-118, :178-191). The weight side (sigma, mu, eps, delta =
+ * sigma * eps) is bt_q8_observe_w's rows 0..3 and the output bt_minmax_update's; the two launches below take the rest. Statistics,
+ * merging, non-finite values, allocation and synchronisation: as above. Each statistic is its own (min, max) pair, fp32 [2].
+ *
+ * The observing two-contraction launch: bt_flipout_conv2d_fwd's / bt_flipout_linear_fwd's operands -- g, S, x, x_sample_stride, p (the
+ * priors and the packed parameters are not read) and d: all draws supplied in the natural layouts (eps_w, eps_b when biased, sign_in,
+ * sign_out; a NEGATIVE sign value means -1, anything else +1, and the +-1 that was used is what is observed) or none (eps from tensor
+ * 0's stream, the bias draw from tensor 1's, the signs hash_sign of tensor 2's and 3's, exactly as the forward draws them) -- and an
+ * optional per-output-channel coef[Co] / shift[Co], both or neither (absent: 1 and 0), the BatchNorm to be folded. For every output
+ * element of all S samples, with sigma = log1p(exp(rho)), conv the layer's contraction (fp32 MFMA accumulation) and every other
+ * operation ONE fp32 rounding:
+ *   mean        = (conv(x, mu) + mu_b) * coef + shift
+ *   pert        = (conv(x * sign_in, sigma * eps) + sigma_b * eps_b) * coef         (no bias: no bias terms)
+ *   pert_signed = pert * sign_out
+ * and the ranges of mean, pert, pert_signed and sign_out are merged into the four pairs. Nothing output-sized is written.
+ * BT_ERR_BAD_ARG before any launch: what the Flipout forward refuses in these operands (null x / p / d / mu_w / rho_w, S < 1, a bad
+ * geometry, some draws supplied and others not, coef without shift), a null pair or nonfinite, a pointer that is not 4-byte aligned,
+ * bt_rng.flags != 0. BT_ERR_UNSUPPORTED, nothing launched: groups != 1, S > 65535, and the sizes the fp32 general kernel refuses (a
+ * tensor of 2^30 elements or more, more than 128 taps). */
+int bt_q8_flip_observe_conv2d(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t x_sample_stride, const bt_params *p,
+                              const bt_draws *d, const float *coef, const float *shift, float *mean_mm, float *pert_mm,
+                              float *pert_signed_mm, float *sign_out_mm, uint32_t *nonfinite, bt_stream_t stream);
+int bt_q8_flip_observe_linear(int32_t B, int32_t In, int32_t Out, int32_t S, const float *x, int64_t x_sample_stride,
+                              const bt_params *p, const bt_draws *d, const float *coef, const float *shift, float *mean_mm,
+                              float *pert_mm, float *pert_signed_mm, float *sign_out_mm, uint32_t *nonfinite, bt_stream_t stream);
+/* The input-side sweep: x fp32, n elements per sample (sample s reads x + s * x_sample_stride; 0: one x for all samples, which still
+ * get their own signs), 4-byte alignment only. sign_in fp32 [S][n] (negative: -1, anything else +1), or NULL and rng: hash_sign of
+ * tensor 2's stream at the element's offset within ONE sample's tensor, sample rng->sample0 + s, as the forward indexes it. Merges the
+ * ranges of x, sign_in and x * sign_in (one fp32 rounding). BT_ERR_BAD_ARG before any launch: a null x / pair / nonfinite, S < 1,
+ * n < 1, a negative stride, both sign_in and rng or neither, a pointer that is not 4-byte aligned. BT_ERR_UNSUPPORTED, nothing
+ * launched: S > 65535, n >= 2^32. */
+int bt_q8_flip_observe_x(int64_t n, int32_t S, const float *x, int64_t x_sample_stride, const float *sign_in, const bt_rng *rng,
+                         float *in_mm, float *sign_in_mm, float *xp_mm, uint32_t *nonfinite, bt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

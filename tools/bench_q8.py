@@ -25,6 +25,11 @@ alternation as ``float_flipout``, and its copy converted by bnn_to_qbnn(fuse_con
 and the Linear on the two-contraction int8 forward (bt_q8_flip_conv2d_fwd / bt_q8_flip_linear_fwd, default pairs). Per layer: the
 int8 Flipout layer's time beside the float Flipout layer's and the INT8 Reparameterization layer's -- DESIGN.md 4.6h.
 
+``--flipout --calibrate N``: a copy of the Flipout model is calibrated as well -- ``quantization.prepare(fuse_conv_bn=True, flipout=True)``,
+N calls of ``mc_forward``, ``quantization.convert(fuse_conv_bn=True, flipout=True)`` -- and joins the alternation as
+``int8_flipout_calibrated`` beside the default-pair ``int8_flipout`` and ``float_flipout``; per layer the float Flipout layer's time, the
+prepared layer's (forward + the four observer launches) and their difference, the observers alone -- DESIGN.md 4.6i.
+
     python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10] [--calibrate N] [--flipout]
 """
 import argparse
@@ -141,6 +146,23 @@ def main():
             if getattr(m, "quant_dict", None) is not None:
                 print(json.dumps(dict(what="quant_dict", layer=nm, pairs=[(round(d["scale"], 6), d["zero_point"]) for d in m.quant_dict])), flush=True)
         models["int8_calibrated"] = cal
+        if args.flipout:
+            fcal = quantization.prepare(copy.deepcopy(fnet), fuse_conv_bn=True, flipout=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.calibrate):
+                mc.mc_forward(fcal, torch.randn(B, 3, 32, 32, device="cuda"), S, with_kl=False)
+            torch.cuda.synchronize()
+            print(json.dumps(dict(what="calibration_flipout", batches=args.calibrate, B=B, S=S, seconds=round(time.perf_counter() - t0, 3))), flush=True)
+            for (nm, kf, uf), (_, _, up) in zip(layer_times(fnet, x, S, args.n), layer_times(fcal, x, S, args.n)):
+                m = dict(fcal.named_modules())[nm]
+                print(json.dumps(dict(what="observer_flipout", layer=nm, float_flipout_us=uf, prepared_us=up, observer_us=round(up - uf, 1),
+                                      observer_kernels=m._last.get("observer_kernels"))), flush=True)
+            quantization.convert(fcal, fuse_conv_bn=True, flipout=True)
+            for nm, m in fcal.named_modules():
+                if getattr(m, "quant_dict", None) is not None:
+                    print(json.dumps(dict(what="quant_dict_flipout", layer=nm, pairs=[(round(d["scale"], 6), d["zero_point"]) for d in m.quant_dict])), flush=True)
+            models["int8_flipout_calibrated"] = fcal
     run = {k: (lambda m=m: mc.mc_forward(m, x, S, with_kl=False)) for k, m in models.items()}
     with torch.no_grad():
         for k in models:
@@ -162,6 +184,9 @@ def main():
             med = lambda k: statistics.median(rates[k])
             print(json.dumps(dict(what="ratio", int8_flipout_over_float_flipout=round(med("int8_flipout") / med("float_flipout"), 3),
                                   int8_flipout_over_int8=round(med("int8_flipout") / med("int8"), 3))), flush=True)
+            if "int8_flipout_calibrated" in rates:
+                print(json.dumps(dict(what="ratio", int8_flipout_calibrated_over_int8_flipout=round(med("int8_flipout_calibrated") / med("int8_flipout"), 3),
+                                      int8_flipout_calibrated_over_float_flipout=round(med("int8_flipout_calibrated") / med("float_flipout"), 3))), flush=True)
             for (nm, kq, uq), (_, kf, uf), (_, _, ur) in zip(layer_times(fq, x, S, args.n), layer_times(fnet, x, S, args.n), layer_times(q, x, S, args.n)):
                 print(json.dumps(dict(what="layer_flipout", layer=nm, int8_flipout_us=uq, float_flipout_us=uf, int8_reparam_us=ur, int8_flipout_kernel=kq,
                                       float_flipout_kernel=kf)), flush=True)
