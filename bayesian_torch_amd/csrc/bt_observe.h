@@ -1,5 +1,6 @@
-// What every observer kernel (bt_q8_observe.hip, the fused forward's OBS form in bt_fused_fwd.h, bt_fused_flipout_obs.hip) shares: a
-// running (min, max) pair, the two float atomics and the workgroup merge.
+// What every observer kernel (the three element sweeps of bt_q8_observe.hip; the fused forward's OBS form in bt_fused_fwd.h, launched
+// by bt_fused_flipout_obs.hip) shares: a running (min, max) pair, the two float atomics and the workgroup merge; and what the sweeps
+// share besides: the head / quads / tail walk over one fp32 run, and on the host their grid rule, alignment check and launch by draw source.
 // Reduction: per thread, wavefront shuffles, one LDS step per workgroup, then at most ONE vector atomic per statistic and workgroup on
 // the value's bit pattern (none when a plain load shows that the value would not widen the statistic). The bits of a non-negative float order like a signed integer's and those of a negative float in reverse like
 // an unsigned integer's, so a float maximum is a signed-integer atomic max for v >= 0 and an unsigned-integer atomic min for v < 0
@@ -27,6 +28,29 @@ struct Range {
     }
   }
 };
+
+template <int K>
+__device__ __forceinline__ void obs_init(Range (&r)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) r[k].lo = INFINITY, r[k].hi = -INFINITY;
+}
+
+// A grid row's walk over one fp32 run x[0, n): one(i, x[i]) before the first 16-byte boundary, quad(i0, x[i0 .. i0 + 4)) on 16-byte loads, one() for the rest.
+template <typename One, typename Quad>
+__device__ __forceinline__ void obs_walk(const float* x, long long n, One one, Quad quad) {
+  long long head = (long long)(((16u - (unsigned)(((uintptr_t)x) & 15u)) & 15u) >> 2);
+  if (head > n) head = n;
+  const long long nquad = (n - head) >> 2;
+  const long long tail0 = head + 4 * nquad;
+  const long long tid = (long long)blockIdx.x * kObsThreads + threadIdx.x, stride = (long long)gridDim.x * kObsThreads;
+  const float4* const x4 = reinterpret_cast<const float4*>(x + head);
+  for (long long g = tid; g < nquad; g += stride) {
+    const float4 v = x4[g];   // (a value, not a reference into memory: ONE 16-byte load)
+    quad(head + 4 * g, v);
+  }
+  if (tid < head) one(tid, x[tid]);                             // head < 4
+  if (tid < n - tail0) one(tail0 + tid, x[tail0 + tid]);        // n - tail0 < 4
+}
 
 __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
   v = __fadd_rn(v, 0.0f);   // -0 -> +0
@@ -96,5 +120,26 @@ __device__ __forceinline__ void obs_merge(Range (&r)[K], unsigned bad, float* co
 
 // A supplied sign as the observers (and the INT8 Flipout forward) read it: a negative value is -1, anything else +1.
 __device__ __forceinline__ float obs_sign(float v) { return v < 0.0f ? -1.0f : 1.0f; }
+
+// ---------------------------------------------------------------------------- host side of the element sweeps
+// `rows` grid rows (samples, segments) of at most `cap` workgroups, a thread taking at least one quad of its row's n elements; every
+// workgroup ends in a merge, so equal rows share about kObsGrid of them (obs_cap).
+inline dim3 obs_grid(long long n, int rows, long long cap) {
+  long long gx = (n + 4 * kObsThreads - 1) / (4 * kObsThreads);
+  return dim3((unsigned)(gx > cap ? cap : gx), (unsigned)rows);
+}
+inline long long obs_cap(int rows) { return (kObsGrid + rows - 1) / rows; }
+
+template <typename... T>
+inline bool obs_aligned4(const T*... p) {   // (a null pointer is aligned)
+  return ((((uintptr_t)p) | ...) & 3u) == 0;
+}
+
+// The <true> (draws regenerated on chip) or the <false> (draws supplied) instantiation of a sweep, under its name.
+template <typename Args>
+inline int obs_launch(bool on_chip, void (*kt)(Args), const char* name_t, void (*kf)(Args), const char* name_f, const char* who, dim3 grid, bt_stream_t stream,
+                      const Args& a) {
+  return launch_kernel(on_chip ? kt : kf, on_chip ? name_t : name_f, who, grid, dim3(kObsThreads), 0, 0, (hipStream_t)stream, a);
+}
 
 }  // namespace bt

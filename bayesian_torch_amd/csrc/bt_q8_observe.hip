@@ -1,12 +1,13 @@
 // Calibration of the INT8 layers (layers/_quantized.py): the seven MinMaxObservers of the reference's post-training flow
 // (layers/variational_layers/conv_variational.py:331-337, :387-397; the same in linear_variational.py) as two sweeps that keep their
-// statistics on the device. The reference materialises sigma, eps, sigma * eps and mu + sigma * eps as weight-sized tensors on the CPU
+// statistics on the device, and the input-side sweep of the Flipout layers' twelve (flipout_layers/conv_flipout.py:339-345, :419-434). The reference materialises sigma, eps, sigma * eps and mu + sigma * eps as weight-sized tensors on the CPU
 // and hands seven tensors to seven observers; here
 //   * bt_q8_observe_w reads (mu, rho) once per sample, regenerates the sample's draws from the call's RNG coordinates (or reads the
 //     supplied ones) and merges the ranges of q = sigma * coef, m = mu * coef, eps, t = q * eps and w = m + t -- the five qint8 stubs
 //     in the reference's order -- into stats[10]; nothing weight-sized is written;
-//   * bt_minmax_update merges the ranges of up to four fp32 tensors (a layer's input and output) into (min, max) pairs.
-// The reduction, the (min, max) pair and the merge: bt_observe.h (the INT8 Flipout layers' observers share them).
+//   * bt_minmax_update merges the ranges of up to four fp32 tensors (a layer's input and output) into (min, max) pairs;
+//   * bt_q8_flip_observe_x sweeps x once per sample and merges the ranges of x, sign_in and x * sign_in.
+// The reduction, the (min, max) pair, the merge, the walk over one fp32 run and the host helpers: bt_observe.h.
 #include "bt_observe.h"
 
 namespace bt {
@@ -35,16 +36,6 @@ struct ObsWArgs {
   uint32_t sample0;
   long long rows, inner, taps, n;
 };
-
-__device__ __forceinline__ void obs_init(Range (&r)[kObsStats]) {
-#pragma unroll
-  for (int k = 0; k < kObsStats; ++k) r[k].lo = INFINITY, r[k].hi = -INFINITY;
-}
-
-__device__ __forceinline__ void obs_finish(const ObsWArgs& a, Range (&r)[kObsStats], unsigned bad, float* lds) {
-  float* const dst[kObsStats] = {a.stats, a.stats + 2, a.stats + 4, a.stats + 6, a.stats + 8};
-  obs_merge<kObsStats>(r, bad, dst, a.nonfinite, lds);
-}
 
 // A thread per four consecutive elements of the weight's natural order, of sample blockIdx.y: 16-byte loads where mu, rho (and this
 // sample's supplied eps) are all 16-byte aligned, element by element for the last n & 3 elements and where they are not. kRng: the
@@ -110,7 +101,8 @@ __global__ __launch_bounds__(kObsThreads) void q8_observe_w_kernel(ObsWArgs a) {
         }
       }
   }
-  obs_finish(a, r, bad, lds);
+  float* const dst[kObsStats] = {a.stats, a.stats + 2, a.stats + 4, a.stats + 6, a.stats + 8};
+  obs_merge<kObsStats>(r, bad, dst, a.nonfinite, lds);
 }
 
 struct MinMaxArgs {
@@ -120,29 +112,67 @@ struct MinMaxArgs {
   unsigned* nonfinite;
 };
 
-// Segment blockIdx.y: the elements before the first 16-byte boundary one by one, whole quads as 16-byte loads, the rest one by one.
+// Segment blockIdx.y, walked as obs_walk walks a run.
 __global__ __launch_bounds__(kObsThreads) void minmax_update_kernel(MinMaxArgs a) {
   __shared__ float lds[4 * 3];
   const int sg = blockIdx.y;
-  const float* const x = a.x[sg];
-  const long long n = a.n[sg];
-  long long head = (long long)(((16u - (unsigned)(((uintptr_t)x) & 15u)) & 15u) >> 2);
-  if (head > n) head = n;
-  const long long nquad = (n - head) >> 2;
-  const long long tail0 = head + 4 * nquad;
   Range r[1];
-  r[0].lo = INFINITY, r[0].hi = -INFINITY;
   unsigned bad = 0;
-  const long long tid = (long long)blockIdx.x * kObsThreads + threadIdx.x, stride = (long long)gridDim.x * kObsThreads;
-  const float4* const x4 = reinterpret_cast<const float4*>(x + head);
-  for (long long g = tid; g < nquad; g += stride) {
-    const float4 v = x4[g];
-    r[0].take(v.x, bad), r[0].take(v.y, bad), r[0].take(v.z, bad), r[0].take(v.w, bad);
-  }
-  if (tid < head) r[0].take(x[tid], bad);                       // head < 4
-  if (tid < n - tail0) r[0].take(x[tail0 + tid], bad);          // n - tail0 < 4
+  obs_init(r);
+  obs_walk(
+      a.x[sg], a.n[sg], [&](long long, float v) { r[0].take(v, bad); },
+      [&](long long, float4 v) { r[0].take(v.x, bad), r[0].take(v.y, bad), r[0].take(v.z, bad), r[0].take(v.w, bad); });
   float* const dst[1] = {a.dst[sg]};
   obs_merge<1>(r, bad, dst, a.nonfinite, lds);
+}
+
+struct ObsXArgs {
+  const float* x;
+  const float* sign_in;   // [S][n] or null: tensor 2's stream of `key`
+  float* dst[3];          // (min, max) of x, sign_in, x * sign_in
+  unsigned* nonfinite;
+  const uint32_t* call_base;
+  RngKey key;             // tensor 2
+  uint32_t sample0;
+  long long n, x_sample_stride;
+};
+
+// Sample blockIdx.y's x, walked as obs_walk walks a run; supplied signs are read as 16-byte loads too where they share x's alignment.
+// kRng: the sign of element i is hash_sign of the sample's tensor 2 stream at i, the element's offset within ONE sample's tensor, as
+// the forward indexes it.
+template <bool kRng>
+__global__ __launch_bounds__(kObsThreads) void q8_flip_observe_x_kernel(ObsXArgs a) {
+  __shared__ float lds[(kObsThreads / 64) * 7];
+  const int s = blockIdx.y;
+  const float* const x = a.x + (long long)s * a.x_sample_stride;
+  const float* const sg = kRng ? nullptr : a.sign_in + (long long)s * a.n;
+  uint32_t skey = 0;
+  if (kRng) {
+    RngKey k = a.key;
+    if (a.call_base) k.call += *a.call_base;
+    skey = sign_stream_key(k, a.sample0 + (uint32_t)s);
+  }
+  const bool sg_quads = !kRng && ((((uintptr_t)sg) ^ ((uintptr_t)x)) & 15u) == 0;   // x's quads are the signs' quads
+  Range r[3];
+  unsigned bad = 0;
+  obs_init(r);
+  auto take = [&](float v, float sn) { r[0].take(v, bad), r[1].take(sn, bad), r[2].take(__fmul_rn(v, sn), bad); };
+  auto sign_of = [&](long long i) -> float { return kRng ? hash_sign(skey, (uint32_t)i) : obs_sign(sg[i]); };
+  obs_walk(
+      x, a.n, [&](long long i, float v) { take(v, sign_of(i)); },
+      [&](long long i0, float4 v) {
+        float sn[4];
+        if (sg_quads) {
+          const float4 s4 = *reinterpret_cast<const float4*>(sg + i0);
+          sn[0] = obs_sign(s4.x), sn[1] = obs_sign(s4.y), sn[2] = obs_sign(s4.z), sn[3] = obs_sign(s4.w);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) sn[j] = sign_of(i0 + j);
+        }
+        take(v.x, sn[0]), take(v.y, sn[1]), take(v.z, sn[2]), take(v.w, sn[3]);
+      });
+  float* const dst[3] = {a.dst[0], a.dst[1], a.dst[2]};
+  obs_merge<3>(r, bad, dst, a.nonfinite, lds);
 }
 
 static const char* const kMinMaxNames[BT_MINMAX_MAX_SEGS] = {"minmax_update<1 segs>", "minmax_update<2 segs>", "minmax_update<3 segs>", "minmax_update<4 segs>"};
@@ -155,8 +185,7 @@ extern "C" int bt_q8_observe_w(const float* mu, const float* rho, const float* c
   if (!mu || !rho || !stats || !nonfinite) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: null mu / rho / stats / nonfinite");
   if (S < 1 || rows < 1 || inner < 1 || taps < 1) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: S < 1 or an empty weight tensor (n < 1)");
   if (!eps == !rng) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: exactly one draw source, eps or rng");
-  if ((((uintptr_t)mu) | ((uintptr_t)rho) | ((uintptr_t)coef) | ((uintptr_t)eps) | ((uintptr_t)stats) | ((uintptr_t)nonfinite)) & 3u)
-    return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: a pointer that is not 4-byte aligned");
+  if (!obs_aligned4(mu, rho, coef, eps, stats, nonfinite)) return set_error(BT_ERR_BAD_ARG, "bt_q8_observe_w: a pointer that is not 4-byte aligned");
   if (S > 65535 || rows >= (1ll << 31) || inner >= (1ll << 31) || taps >= (1ll << 31)) return set_error(BT_ERR_UNSUPPORTED, "bt_q8_observe_w: S > 65535 or tensor too large");
   const long long nq = (long long)rows * taps * (((long long)inner + 3) >> 2);
   if ((long long)inner * taps >= (1ll << 31) || (long long)rows * inner >= (1ll << 40) / taps || nq > (1ll << 32)) return set_error(BT_ERR_UNSUPPORTED, "bt_q8_observe_w: weight tensor too large for the draw stream");
@@ -164,34 +193,44 @@ extern "C" int bt_q8_observe_w(const float* mu, const float* rho, const float* c
   a.mu = mu, a.rho = rho, a.coef = coef, a.eps = eps, a.stats = stats, a.nonfinite = nonfinite;
   a.rows = rows, a.inner = inner, a.taps = taps, a.n = (long long)rows * inner * taps;
   if (rng) a.call_base = rng->call_base_dev, a.key = make_key(*rng, 0), a.sample0 = rng->sample0;
-  // about kObsGrid workgroups over all samples (a few per CU), each walking its share of the quads: every workgroup ends in a merge
-  long long gx = (((a.n + 3) >> 2) + kObsThreads - 1) / kObsThreads;
-  const long long cap = (kObsGrid + S - 1) / S;
-  if (gx > cap) gx = cap;
-  const dim3 grid((unsigned)gx, (unsigned)S);
-  if (rng) return launch_kernel(q8_observe_w_kernel<true>, "q8_observe_w<eps on chip>", "bt_q8_observe_w", grid, dim3(kObsThreads), 0, 0, (hipStream_t)stream, a);
-  return launch_kernel(q8_observe_w_kernel<false>, "q8_observe_w<eps injected>", "bt_q8_observe_w", grid, dim3(kObsThreads), 0, 0, (hipStream_t)stream, a);
+  return obs_launch(rng != nullptr, q8_observe_w_kernel<true>, "q8_observe_w<eps on chip>", q8_observe_w_kernel<false>, "q8_observe_w<eps injected>",
+                    "bt_q8_observe_w", obs_grid(a.n, S, obs_cap(S)), stream, a);
 }
 
 extern "C" int bt_minmax_update(int32_t n_segs, const bt_minmax_seg* segs, uint32_t* nonfinite, bt_stream_t stream) {
   using namespace bt;
   if (n_segs < 1 || n_segs > BT_MINMAX_MAX_SEGS) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: 1 to 4 segments");
-  if (!segs || !nonfinite || (((uintptr_t)nonfinite) & 3u)) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: null segs / nonfinite");
+  if (!segs || !nonfinite || !obs_aligned4(nonfinite)) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: null segs / nonfinite");
   MinMaxArgs a = {};
   long long most = 0;
   for (int i = 0; i < BT_MINMAX_MAX_SEGS; ++i) {
     const bt_minmax_seg& s = segs[i < n_segs ? i : 0];   // (the unused slots repeat segment 0; no workgroup reads them)
     if (i < n_segs) {
       if (!s.x || !s.dst || s.n < 1) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: a segment with a null pointer or n < 1");
-      if ((((uintptr_t)s.x) | ((uintptr_t)s.dst)) & 3u) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: a pointer that is not 4-byte aligned");
+      if (!obs_aligned4(s.x, s.dst)) return set_error(BT_ERR_BAD_ARG, "bt_minmax_update: a pointer that is not 4-byte aligned");
       if (s.n >= (1ll << 40)) return set_error(BT_ERR_UNSUPPORTED, "bt_minmax_update: segment too large");
       if (s.n > most) most = s.n;
     }
     a.x[i] = s.x, a.n[i] = s.n, a.dst[i] = s.dst;
   }
   a.nonfinite = nonfinite;
-  long long gx = (most + 4 * kObsThreads - 1) / (4 * kObsThreads);   // a thread takes at least one quad
-  if (gx > kObsGrid) gx = kObsGrid;
-  return launch_kernel(minmax_update_kernel, kMinMaxNames[n_segs - 1], "bt_minmax_update", dim3((unsigned)gx, (unsigned)n_segs), dim3(kObsThreads), 0, 0,
+  // (segments differ in length: the longest one's row may take the whole cap)
+  return launch_kernel(minmax_update_kernel, kMinMaxNames[n_segs - 1], "bt_minmax_update", obs_grid(most, n_segs, kObsGrid), dim3(kObsThreads), 0, 0,
                        (hipStream_t)stream, a);
+}
+
+extern "C" int bt_q8_flip_observe_x(int64_t n, int32_t S, const float* x, int64_t x_sample_stride, const float* sign_in, const bt_rng* rng, float* in_mm,
+                                    float* sign_in_mm, float* xp_mm, uint32_t* nonfinite, bt_stream_t stream) {
+  using namespace bt;
+  if (!x || !in_mm || !sign_in_mm || !xp_mm || !nonfinite) return set_error(BT_ERR_BAD_ARG, "bt_q8_flip_observe_x: null x / statistics / nonfinite");
+  if (S < 1 || n < 1 || x_sample_stride < 0) return set_error(BT_ERR_BAD_ARG, "bt_q8_flip_observe_x: S < 1, n < 1 or a negative x_sample_stride");
+  if (!sign_in == !rng) return set_error(BT_ERR_BAD_ARG, "bt_q8_flip_observe_x: exactly one draw source, sign_in or rng");
+  if (!obs_aligned4(x, sign_in, in_mm, sign_in_mm, xp_mm, nonfinite)) return set_error(BT_ERR_BAD_ARG, "bt_q8_flip_observe_x: a pointer that is not 4-byte aligned");
+  if (S > 65535 || n >= (1ll << 32)) return set_error(BT_ERR_UNSUPPORTED, "bt_q8_flip_observe_x: S > 65535 or 2^32 or more elements in one sample's x (the sign stream's index)");
+  ObsXArgs a = {};
+  a.x = x, a.sign_in = sign_in, a.dst[0] = in_mm, a.dst[1] = sign_in_mm, a.dst[2] = xp_mm, a.nonfinite = nonfinite;
+  a.n = n, a.x_sample_stride = x_sample_stride;
+  if (rng) a.call_base = rng->call_base_dev, a.key = make_key(*rng, 2), a.sample0 = rng->sample0;
+  return obs_launch(rng != nullptr, q8_flip_observe_x_kernel<true>, "q8_flip_observe_x<signs on chip>", q8_flip_observe_x_kernel<false>,
+                    "q8_flip_observe_x<signs injected>", "bt_q8_flip_observe_x", obs_grid(n, S, obs_cap(S)), stream, a);
 }

@@ -137,6 +137,15 @@ def _epilogue(tens, out, S, relu, pool):
     return C.byref(_lib.bt_epilogue(_lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res), rstride, 1 if relu else 0, 1 if pool else 0))
 
 
+def _f32_on(dev, tens):
+    """Every tensor of the dict ``tens`` becomes contiguous fp32 (``_lib.dev_f32``; None stays None); one on another device than ``dev`` raises."""
+    for k, t in tens.items():
+        t = _lib.dev_f32(t, k)
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{k} on {t.device} but input on {dev}")
+        tens[k] = t
+
+
 def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=None, S=1, shared_x=True,
                    priors=None, eps_w=None, eps_b=None, sign_in=None, sign_out=None,
                    seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_kl=False, workspace_owner="functional",
@@ -169,11 +178,7 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
     tens = dict(mu_w=mu_w, rho_w=rho_w, mu_b=mu_b, rho_b=rho_b, eps_w=eps_w, eps_b=eps_b, sign_in=sign_in, sign_out=sign_out,
                 post_scale=post_scale, post_shift=post_shift, residual=residual, mu_packed=None if packed is None else packed[0],
                 sigma_packed=None if packed is None else packed[1])
-    for k, t in tens.items():
-        t = _lib.dev_f32(t, k)
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"{k} on {t.device} but input on {dev}")
-        tens[k] = t
+    _f32_on(dev, tens)
     B, geom, x_elems, tail = _geometry(x, mu_w, conv, S, shared_x)
     n_so = B * math.prod(tail)      # one sample's contraction output, before any fused pooling
     if pool:
@@ -763,7 +768,7 @@ def q8_flip_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=N
 # ---------------------------------------------------------------------------- calibration of the INT8 layers (csrc/bt_q8_observe.hip)
 CALIB_ROWS = ("sigma", "mu", "eps", "mul", "add", "in", "out")      # the rows of a layer's ``calib_minmax`` [7, 2]: (min, max) pairs
 # ... and of a Flipout layer's [13, 2]: bt_q8_observe_w's five rows ("add" is a quantity Flipout never forms: conversion ignores it), then
-# the reference's eight quint8 stubs. The ten a quant_dict takes (Q8_FLIP_PAIRS) are rows 2, 3 and 5..12.
+# the reference's eight quint8 stubs. Which rows are symmetric and which a quant_dict takes: layers/_calibration.py's schemas, which refer to these tuples.
 CALIB_FLIP_ROWS = ("sigma", "mu", "eps", "delta", "add", "in", "mean", "sign_in", "sign_out", "xp", "pert", "pert_signed", "out")
 
 
@@ -866,11 +871,7 @@ def q8_flip_observe(x, mu_w, rho_w, mu_b, rho_b, mean_mm, pert_mm, pert_signed_m
     x = _lib.dev_f32(x, "input")
     dev = x.device
     tens = dict(mu_w=mu_w, rho_w=rho_w, mu_b=mu_b, rho_b=rho_b, eps_w=eps_w, eps_b=eps_b, sign_in=sign_in, sign_out=sign_out, coef=coef, shift=shift)
-    for k, t in tens.items():
-        t = _lib.dev_f32(t, k)
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"{k} on {t.device} but input on {dev}")
-        tens[k] = t
+    _f32_on(dev, tens)
     _calib_dev(nonfinite, "nonfinite", torch.int32)
     _no_capture(dev, "q8_flip_observe")
     B, geom, x_elems, tail = _geometry(x, mu_w, conv, S, shared_x)

@@ -18,6 +18,7 @@ from torch.nn import Parameter
 
 from .. import _lib, mc, rng
 from .. import functional as F
+from ._calibration import CalibrationMixin
 from .base_variational_layer import BaseVariationalLayer_, check_prior_type, get_kernel_size
 
 _warned = [False]
@@ -30,20 +31,7 @@ BT_FUSED_KL = bool(_os.environ.get("BT_FUSED_KL"))         # A/B knob: inference
 MAX_TAPS = 128     # kernel positions (kh * kw of the Conv2d launch) the fused kernels and bt_pack_sync support (kMaxTaps)
 
 
-class _BnOutputObserver:
-    """Forward hook of the BatchNorm a calibrating layer will be folded with: the layer's ``out`` statistic is the range of the
-    BatchNorm's output. An object, not a closure: a deep copy of the model observes into the COPY's layer."""
-
-    def __init__(self, layer):
-        self.layer = layer
-
-    def __call__(self, module, args, output):
-        layer = self.layer
-        if layer.quant_prepare and not torch.is_grad_enabled():
-            F.minmax_update([(output, layer.calib_minmax[-1])], layer.calib_nonfinite)      # "out": the last row of either table
-
-
-class FusedBayesLayer(BaseVariationalLayer_):
+class FusedBayesLayer(BaseVariationalLayer_, CalibrationMixin):
     _kind = "linear"     # or "conv"
     _flip = False
     _wname = "weight"    # parameter suffix: mu_weight / mu_kernel
@@ -117,76 +105,8 @@ class FusedBayesLayer(BaseVariationalLayer_):
             self.mu_bias.data.normal_(mean=mu0, std=0.1)
             self.rho_bias.data.normal_(mean=rho0, std=0.1)
 
-    def prepare(self):
+    def prepare(self):      # (the four convertible classes calibrate: layers/_calibration.py's CalibrationMixin)
         raise NotImplementedError("post-training quantisation (QuantStub observers) is outside the MI355X hot path")
-
-    # ------------------------------------------------------------------ calibration (Linear / Conv2d, Reparameterization and Flipout)
-    def _calib_prepare(self, bn=None, flip=False):
-        """What ``prepare()`` of the two convertible classes does (reference conv_variational.py:331-337: seven QuantStub observers):
-        empty statistics in two persistent buffers, ``calib_minmax`` [7, 2] -- (min, max) of sigma, mu, eps, mul, add, in, out -- and
-        ``calib_nonfinite`` [1], filled on the device by every no-grad forward from now on (csrc/bt_q8_observe.hip). ``bn``: the
-        BatchNorm2d that ``bnn_to_qbnn(fuse_conv_bn=True)`` will fold into this layer: the weight rows are then those of
-        mu * coef and sigma * coef, and ``out`` is observed at the BatchNorm's output through a forward hook.
-        ``flip``: the Flipout classes (reference conv_flipout.py:339-345: twelve observers): ``calib_minmax`` is [13, 2], rows
-        ``functional.CALIB_FLIP_ROWS``, filled by four launches (csrc/bt_fused_flipout_obs.hip); the BatchNorm's shift joins the mean
-        output's statistic (``calib_shift``)."""
-        name = type(self).__name__
-        if getattr(self, "groups", 1) != 1:
-            raise NotImplementedError(f"{name}.prepare(): groups={self.groups} has no INT8 counterpart here (groups must be 1)")
-        if self.post_scale is not None or self.post_shift is not None or self.post_relu or self.post_pool:
-            raise RuntimeError(f"{name}.prepare(): the layer carries a folded output stage (fuse.py); calibrate the unfolded model")
-        if bn is not None and bn.training:
-            raise RuntimeError(f"{name}.prepare(): the BatchNorm to fold is in training mode; call model.eval() first")
-        self._calib_release()
-        mm, bad = F.calib_buffers(self._w("mu").device, len(F.CALIB_FLIP_ROWS if flip else F.CALIB_ROWS))
-        self.register_buffer("calib_minmax", mm)
-        self.register_buffer("calib_nonfinite", bad)
-        coef = shift = None
-        if bn is not None:
-            from ._quantized import _sqrt
-            coef = (bn.weight.detach() / _sqrt(bn.running_var + bn.eps)).to(torch.float32).contiguous()      # quantize()'s bn_coef
-            if flip:
-                shift = (bn.bias.detach() - coef * bn.running_mean).to(torch.float32).contiguous()           # ... and its folded bias, less mu_b * coef
-            self._calib_hook = bn.register_forward_hook(_BnOutputObserver(self))
-        self.register_buffer("calib_coef", coef, persistent=False)
-        if flip:
-            self.register_buffer("calib_shift", shift, persistent=False)
-        self._calib_fused = bn is not None
-        self.quant_prepare = True
-
-    def _calib_release(self):
-        """Take the BatchNorm's observer hook out again (``convert()``; a second ``prepare()``)."""
-        hook = self.__dict__.pop("_calib_hook", None)
-        if hook is not None:
-            hook.remove()
-
-    def _calib_observe(self, x, out, mu_t, rho_t, S, coords, draw, conv=None, shared=True):
-        """The two observer launches of a calibrating forward: the weight side with the call's own draws (the supplied tensor, or the
-        forward's RNG coordinates), then the input and -- unless the folded BatchNorm's hook observes it -- the output. Flipout: four --
-        between the two, the input-side sweep (x, sign_in, x * sign_in) and the observing two-contraction launch (mean, pert,
-        pert_signed, sign_out), on the same draws."""
-        if self.post_scale is not None or self.post_shift is not None or self.post_relu or self.post_pool:
-            raise RuntimeError(f"{type(self).__name__}: folded an output stage (fuse.py) after prepare(); calibrate the unfolded model")
-        mm, bad = self.calib_minmax, self.calib_nonfinite
-        F.q8_observe_w(mu_t, rho_t, mm, bad, S=S, coef=self.calib_coef, eps=draw.get("eps_w"), seed=coords.seed, call=coords.call, layer_id=coords.layer_id,
-                       sample0=coords.sample0, call_base=coords.call_base)
-        kernels = [_lib.lib().bt_last_kernel_name().decode()]
-        if self._flip:
-            rows = {n: mm[i] for i, n in enumerate(F.CALIB_FLIP_ROWS)}
-            at = dict(S=S, shared_x=shared, seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base)
-            F.q8_flip_observe_x(x, rows["in"], rows["sign_in"], rows["xp"], bad, sign_in=draw.get("sign_in"), **at)
-            kernels.append(_lib.lib().bt_last_kernel_name().decode())
-            F.q8_flip_observe(x, mu_t, rho_t, self.mu_bias, self.rho_bias, rows["mean"], rows["pert"], rows["pert_signed"], rows["sign_out"], bad, conv=conv,
-                              coef=self.calib_coef, shift=self.calib_shift, eps_w=draw.get("eps_w"), eps_b=draw.get("eps_b"), sign_in=draw.get("sign_in"),
-                              sign_out=draw.get("sign_out"), **at)
-            kernels.append(_lib.lib().bt_last_kernel_name().decode())
-            segs = [] if self._calib_fused else [(out, rows["out"])]
-        else:
-            segs = [(x, mm[5])] + ([] if self._calib_fused else [(out, mm[6])])
-        if segs:
-            F.minmax_update(segs, bad)
-            kernels.append(_lib.lib().bt_last_kernel_name().decode())
-        self._last.update(observed=True, observer_kernel=kernels[0], observer_kernels=tuple(kernels))
 
     def _w(self, what):
         return getattr(self, f"{what}_{self._wname}")

@@ -26,6 +26,7 @@ import torch
 
 from .. import _lib, rng
 from .. import functional as F
+from ._calibration import FLIPOUT, REPARAM, _sqrt, bn_coef      # noqa: F401 -- (_sqrt: the tests' own bn_coef reads it here)
 from ._fused import FusedBayesLayer
 from .base_variational_layer import BaseVariationalLayer_, get_kernel_size
 
@@ -34,18 +35,14 @@ def _softplus(rho):
     return torch.log1p(torch.exp(rho))       # the reference's two fp32 operations (their last bit follows the host's exp / log1p)
 
 
-def _sqrt(t):
-    """The IEEE (correctly rounded) fp32 square root: taken in double and rounded once. torch's CPU fp32 sqrt is not correctly rounded
-    on every host: one ulp in one BatchNorm coefficient moved a folded layer's scale between two machines."""
-    return torch.sqrt(t.double()).to(t.dtype)
-
-
 class _QuantizedLayer(BaseVariationalLayer_):
     _kl_muted = True       # the KL of a quantised layer is 0: an mc_samples context collects nothing from it
     _rng_layer = True      # rng.assign_layer_ids numbers it with the other Bayesian layers
     _mc_frame = FusedBayesLayer._mc_frame
     _call_coords = FusedBayesLayer._call_coords
     _take_injected = FusedBayesLayer._take_injected
+    _schema = REPARAM      # its ``pairs`` are what a quant_dict holds, in order
+    _sign_keys = ()        # the sign tensors of a draw, beside eps_w and eps_b
 
     def _init_common(self, wshape, bias):
         self._wshape = tuple(wshape)
@@ -141,12 +138,16 @@ class _QuantizedLayer(BaseVariationalLayer_):
             self._cache = (key, float(self.quantized_mu_scale.item()), float(self.quantized_sigma_scale.item()), packs)
         return self._cache[1:]
 
-    def _pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
-        """The five (scale, zero point) pairs of this call: eps, mul, add, in, out."""
-        if self.quant_dict is not None:
-            if len(self.quant_dict) != 5:
-                raise ValueError("quant_dict must hold five {'scale', 'zero_point'} entries: eps, mul, add, in, out")
-            return [(float(d["scale"]), int(d["zero_point"])) for d in self.quant_dict]
+    def _pairs(self, *default_args):
+        """The (scale, zero point) pairs of this call, in ``_schema.pairs``' order: the ``quant_dict``'s, or the class's defaults."""
+        if self.quant_dict is None:
+            return self._default_pairs(*default_args)
+        names = self._schema.pairs
+        if len(self.quant_dict) != len(names):
+            raise ValueError(f"quant_dict must hold { {5: 'five', 10: 'ten'}[len(names)] } {{'scale', 'zero_point'}} entries: {', '.join(names)}")
+        return [(float(d["scale"]), int(d["zero_point"])) for d in self.quant_dict]
+
+    def _default_pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
         s_mul = s_sigma * float(normal_scale)
         return [(float(normal_scale), 0), (s_mul, 0), (max(s_mul, s_mu), 0), (float(default_scale), int(default_zero_point)),
                 (float(default_scale), int(default_zero_point))]
@@ -185,26 +186,35 @@ class _QuantizedLayer(BaseVariationalLayer_):
             out = out.reshape(lead + (self._wshape[0],))
         return (out, 0) if return_kl else out
 
+    def _out_tail(self, x):
+        conv = self._conv()
+        if conv is None:
+            return (self._wshape[0],)
+        return (self._wshape[0],) + F.conv_out_hw(x.shape[2], x.shape[3], self._wshape[2], self._wshape[3], *conv["stride"], *conv["padding"], *conv["dilation"])
+
     def _has_sampled_bias(self):
         return self.quantized_mu_bias is not None and self.quantized_sigma_bias is not None
 
     def _supplied_draw(self, inj, S, x, shared):
-        """The draw this call reads instead of the on-chip streams -- the injected one, or in rng mode "torch" eps_w then eps_b per sample,
-        the reference's draw order -- as dict(eps_w, eps_b), or None."""
+        """The draw this call reads instead of the on-chip streams -- the injected one, or in rng mode "torch" eps_w, eps_b, then the
+        ``_sign_keys`` per sample, the reference's draw order -- as dict(eps_w, eps_b, *_sign_keys), or None."""
         if inj is not None:
-            eps_w, eps_b = inj["eps_w"], inj.get("eps_b")
-            if eps_w.shape[0] != S:
-                raise RuntimeError(f"inject_draw holds {eps_w.shape[0]} samples, this call computes {S}")
-            return dict(eps_w=eps_w, eps_b=eps_b)
+            d = dict(eps_w=inj["eps_w"], eps_b=inj.get("eps_b"), **{k: inj[k] for k in self._sign_keys})
+            if d["eps_w"].shape[0] != S:
+                raise RuntimeError(f"inject_draw holds {d['eps_w'].shape[0]} samples, this call computes {S}")
+            return d
         if rng.get_mode() != "torch":
             return None
-        eps_w = torch.empty((S,) + self._wshape, device=x.device)
-        eps_b = torch.empty((S, self._wshape[0]), device=x.device) if self._has_sampled_bias() else None
+        dev, B = x.device, x.shape[0] // (1 if shared else S)
+        d = dict(eps_w=torch.empty((S,) + self._wshape, device=dev), eps_b=torch.empty((S, self._wshape[0]), device=dev) if self._has_sampled_bias() else None)
+        d.update({k: torch.empty((S, B) + tail, device=dev) for k, tail in zip(self._sign_keys, (tuple(x.shape[1:]), self._out_tail(x)))})
         for s in range(S):
-            eps_w[s].normal_()
-            if eps_b is not None:
-                eps_b[s].normal_()
-        return dict(eps_w=eps_w, eps_b=eps_b)
+            d["eps_w"][s].normal_()
+            if d["eps_b"] is not None:
+                d["eps_b"][s].normal_()
+            for k in self._sign_keys:
+                d[k][s].uniform_(-1, 1).sign_()
+        return d
 
     _forward_fn = staticmethod(F.q8_forward)      # the functional forward of the estimator: what _launch calls
 
@@ -214,9 +224,9 @@ class _QuantizedLayer(BaseVariationalLayer_):
                                 want_q=self.want_q, **(draw or {}))
 
     def materialize_last_draw(self):
-        """The draw the last forward used: ``eps_w`` [S, *weight shape] and ``eps_b`` [S, Co] (None without a sampled bias) -- the
-        tensors that were read, or, after an on-chip draw, the streams regenerated from the call's coordinates (bt_rng_normal_fill,
-        tensors 0 and 1)."""
+        """The draw the last forward used: ``eps_w`` [S, *weight shape], ``eps_b`` [S, Co] (None without a sampled bias) and the
+        ``_sign_keys`` -- the tensors that were read, or, after an on-chip draw, the streams regenerated from the call's coordinates
+        (bt_rng_normal_fill, tensors 0 and 1; bt_rng_sign_fill, tensors 2 and 3)."""
         if self._last is None:
             raise RuntimeError("no forward has run yet")
         st = self._last
@@ -226,13 +236,10 @@ class _QuantizedLayer(BaseVariationalLayer_):
             raise RuntimeError("draws made under a graph call_base cannot be replayed after the word advanced")
         seed, call_base, call, lid, sample0 = st["rng"]
         dev = self.quantized_mu_weight.device
-        eps_w = F.rng_fill_normal(seed, call, lid, sample0, 0, st["S"], self._wshape, dev)
-        eps_b = None
-        if self._has_sampled_bias():
-            eps_b = F.rng_fill_normal(seed, call, lid, sample0, 1, st["S"], (self._wshape[0],), dev)
-        return self._with_signs(dict(eps_w=eps_w, eps_b=eps_b), st, dev)
-
-    def _with_signs(self, d, st, dev):
+        d = dict(eps_w=F.rng_fill_normal(seed, call, lid, sample0, 0, st["S"], self._wshape, dev),
+                 eps_b=F.rng_fill_normal(seed, call, lid, sample0, 1, st["S"], (self._wshape[0],), dev) if self._has_sampled_bias() else None)
+        for i, k in enumerate(self._sign_keys):
+            d[k] = F.rng_fill_sign(seed, call, lid, sample0, 2 + i, st["S"], st[("x_shape", "out_shape")[i]], dev)
         return d
 
 
@@ -295,14 +302,14 @@ class _Conv2dShell:
             if has_b:
                 mu_b, sigma_b = src.mu_bias.detach(), _softplus(src.rho_bias.detach())
         else:
-            bn_coef = self.bn_weight.detach() / _sqrt(self.bn_running_var + self.bn_eps)
-            mu = mu * (bn_coef.view(-1, 1, 1, 1).expand(mu.shape))
-            sigma = sigma * (bn_coef.view(-1, 1, 1, 1).expand(sigma.shape))
+            coef = bn_coef(self, "bn_")
+            mu = mu * (coef.view(-1, 1, 1, 1).expand(mu.shape))
+            sigma = sigma * (coef.view(-1, 1, 1, 1).expand(sigma.shape))
             if has_b:
-                mu_b = (src.mu_bias.detach() - self.bn_running_mean) * bn_coef + self.bn_bias.detach()
-                sigma_b = _softplus(src.rho_bias.detach()) * bn_coef
+                mu_b = (src.mu_bias.detach() - self.bn_running_mean) * coef + self.bn_bias.detach()
+                sigma_b = _softplus(src.rho_bias.detach()) * coef
             else:
-                mu_b = self.bn_weight.detach() / _sqrt(self.bn_running_var + self.bn_eps) * (-self.bn_running_mean) + self.bn_bias.detach()
+                mu_b = coef * (-self.bn_running_mean) + self.bn_bias.detach()
         self.bias = mu_b is not None
         self._store(mu, sigma, mu_b, sigma_b)
         self.bn_weight = self.bn_bias = self.bn_running_mean = self.bn_running_var = self.bn_eps = None
@@ -332,53 +339,17 @@ class _QuantizedFlipoutLayer(_QuantizedLayer):
     tensor a negative value means -1 and anything else +1. rng mode "torch" draws eps_w, eps_b, sign_in, sign_out per sample."""
 
     _forward_fn = staticmethod(F.q8_flip_forward)
+    _schema = FLIPOUT
+    _sign_keys = ("sign_in", "sign_out")
 
     def prepare(self):
         raise NotImplementedError("calibration happens on the float Flipout layer (quantization.prepare(model, flipout=True), forwards, then "
                                   "convert(model, flipout=True)), not on the converted one; or supply quant_dict, a list of ten "
                                   f"{{'scale', 'zero_point'}} entries ({', '.join(F.Q8_FLIP_PAIRS)})")
 
-    def _pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
-        """The ten (scale, zero point) pairs of this call, in ``functional.Q8_FLIP_PAIRS``' order."""
-        if self.quant_dict is not None:
-            if len(self.quant_dict) != 10:
-                raise ValueError(f"quant_dict must hold ten {{'scale', 'zero_point'}} entries: {', '.join(F.Q8_FLIP_PAIRS)}")
-            return [(float(d["scale"]), int(d["zero_point"])) for d in self.quant_dict]
+    def _default_pairs(self, s_mu, s_sigma, normal_scale, default_scale, default_zero_point):
         dflt = (float(default_scale), int(default_zero_point))
         return [(float(normal_scale), 0), (s_sigma * float(normal_scale), 0)] + [dflt] * 8
-
-    def _out_tail(self, x):
-        conv = self._conv()
-        if conv is None:
-            return (self._wshape[0],)
-        return (self._wshape[0],) + F.conv_out_hw(x.shape[2], x.shape[3], self._wshape[2], self._wshape[3], *conv["stride"], *conv["padding"], *conv["dilation"])
-
-    def _supplied_draw(self, inj, S, x, shared):
-        if inj is not None:
-            d = dict(eps_w=inj["eps_w"], eps_b=inj.get("eps_b"), sign_in=inj["sign_in"], sign_out=inj["sign_out"])
-            if d["eps_w"].shape[0] != S:
-                raise RuntimeError(f"inject_draw holds {d['eps_w'].shape[0]} samples, this call computes {S}")
-            return d
-        if rng.get_mode() != "torch":
-            return None
-        dev, B = x.device, x.shape[0] // (1 if shared else S)
-        d = dict(eps_w=torch.empty((S,) + self._wshape, device=dev), eps_b=torch.empty((S, self._wshape[0]), device=dev) if self._has_sampled_bias() else None,
-                 sign_in=torch.empty((S, B) + tuple(x.shape[1:]), device=dev), sign_out=torch.empty((S, B) + self._out_tail(x), device=dev))
-        for s in range(S):
-            d["eps_w"][s].normal_()
-            if d["eps_b"] is not None:
-                d["eps_b"][s].normal_()
-            d["sign_in"][s].uniform_(-1, 1).sign_()
-            d["sign_out"][s].uniform_(-1, 1).sign_()
-        return d
-
-    def _with_signs(self, d, st, dev):
-        """materialize_last_draw after an on-chip draw: the two sign streams (bt_rng_sign_fill, tensors 2 and 3) beside eps_w and eps_b."""
-        seed, _, call, lid, sample0 = st["rng"]
-        d["sign_in"] = F.rng_fill_sign(seed, call, lid, sample0, 2, st["S"], st["x_shape"], dev)
-        d["sign_out"] = F.rng_fill_sign(seed, call, lid, sample0, 3, st["S"], st["out_shape"], dev)
-        return d
-
 
 class QuantizedLinearFlipout(_LinearShell, _QuantizedFlipoutLayer):
     """Drop-in for reference ``quantized_linear_flipout.py:44-261``. Build it with ``bnn_to_qbnn(flipout=True)``."""

@@ -28,11 +28,11 @@ class Conv2dFlipout(FusedBayesLayer):
         return self._forward(x, return_kl, residual)
 
     def prepare(self, flipout=False, bn=None):
-        """``prepare(flipout=True)``: start calibrating for ``bnn_to_qbnn(flipout=True)`` -- see ``FusedBayesLayer._calib_prepare``.
+        """``prepare(flipout=True)``: start calibrating for ``bnn_to_qbnn(flipout=True)`` -- see ``CalibrationMixin._calib_prepare``.
         On request only, like the conversion; without the keyword, and on subclasses, it keeps raising."""
         if type(self) is not Conv2dFlipout or not flipout:
             return super().prepare()
-        self._calib_prepare(bn, flip=True)
+        self._calib_prepare(bn)
 
 
 class Conv1dFlipout(FusedBayesLayer):

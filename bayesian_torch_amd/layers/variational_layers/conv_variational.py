@@ -36,7 +36,7 @@ class Conv2dReparameterization(FusedBayesLayer):
         return self._forward(input, return_kl, residual)
 
     def prepare(self, bn=None):
-        """Start calibrating for ``bnn_to_qbnn``: see ``FusedBayesLayer._calib_prepare`` (subclasses keep raising)."""
+        """Start calibrating for ``bnn_to_qbnn``: see ``CalibrationMixin._calib_prepare`` (subclasses keep raising)."""
         if type(self) is not Conv2dReparameterization:
             return super().prepare()
         self._calib_prepare(bn)

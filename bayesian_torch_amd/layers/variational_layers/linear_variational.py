@@ -24,7 +24,7 @@ class LinearReparameterization(FusedBayesLayer):
         return self._forward(input, return_kl, residual)
 
     def prepare(self, bn=None):
-        """Start calibrating for ``bnn_to_qbnn``: see ``FusedBayesLayer._calib_prepare`` (subclasses keep raising)."""
+        """Start calibrating for ``bnn_to_qbnn``: see ``CalibrationMixin._calib_prepare`` (subclasses keep raising)."""
         if type(self) is not LinearReparameterization:
             return super().prepare()
         self._calib_prepare(bn)

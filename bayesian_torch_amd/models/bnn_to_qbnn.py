@@ -18,6 +18,7 @@ import warnings
 from torch.nn import Identity
 
 import bayesian_torch_amd.layers as bayesian_layers
+from bayesian_torch_amd.layers._calibration import quant_dict_from_stats
 
 _CONVERTIBLE = ("LinearReparameterization", "Conv2dReparameterization")
 _CONVERTIBLE_FLIPOUT = ("LinearFlipout", "Conv2dFlipout")      # converted on request only: bnn_to_qbnn(flipout=True)
@@ -36,42 +37,13 @@ def _quantized_class(d, flipout=False):
     return getattr(bayesian_layers, "Quantized" + name)
 
 
-def _calibrated_dict(d, name):
-    """The ``quant_dict`` of a layer that was calibrated (``prepare()`` + forwards): [eps, mul, add, in, out] as {'scale', 'zero_point'} --
-    the reference's ``quant_dict[2:] + quint`` selection (models/bnn_to_qbnn.py:105-111) -- from the statistics the observer kernels
-    left on the device; a Flipout layer's ten entries in ``functional.Q8_FLIP_PAIRS`` order. ONE host read: the seven (thirteen)
-    (min, max) pairs and whether any non-finite value was met."""
-    import torch
-    from bayesian_torch_amd.functional import CALIB_FLIP_ROWS, CALIB_ROWS, Q8_FLIP_PAIRS
-    from bayesian_torch_amd.quantization.quantize import observer_qparams
-    flip = bool(getattr(d, "_flip", False))
-    if flip:      # ten of the thirteen rows, in the quant_dict's order: eps and delta symmetric qint8, the other eight affine quint8
-        CALIB_ROWS = CALIB_FLIP_ROWS
-        take = [(CALIB_FLIP_ROWS.index(n), torch.qint8 if n in ("eps", "delta") else torch.quint8) for n in Q8_FLIP_PAIRS]
-    else:
-        take = [(row, torch.qint8 if row < 5 else torch.quint8) for row in range(2, len(CALIB_ROWS))]
-    who = f"{type(d).__name__} '{name}'" if name else type(d).__name__
-    host = torch.cat([d.calib_minmax.detach().reshape(-1).to(torch.float32), (d.calib_nonfinite.detach().reshape(-1) != 0).to(torch.float32)]).cpu()
-    mm, bad = host[:-1].reshape(len(CALIB_ROWS), 2), bool(host[-1])
-    if bad:
-        raise RuntimeError(f"bnn_to_qbnn: {who} met non-finite values while calibrating (calib_nonfinite != 0): its ranges cannot be trusted")
-    out = []
-    for row, dtype in take:
-        if not bool(torch.isfinite(mm[row]).all()):
-            raise RuntimeError(f"bnn_to_qbnn: {who} was prepared but its '{CALIB_ROWS[row]}' statistics are still empty: run the calibration batches "
-                               "(under torch.no_grad()) between prepare() and convert()")
-        scale, zp = observer_qparams(mm[row, 0], mm[row, 1], dtype)
-        out.append({"scale": float(scale), "zero_point": int(zp)})
-    return out
-
-
 def _finish(qbnn_layer, d, fused=False, name=None):
     if d.quant_prepare:
         if bool(getattr(d, "_calib_fused", False)) != bool(fused):
             how = lambda f: "fuse_conv_bn=True" if f else "fuse_conv_bn=False"
             raise RuntimeError(f"bnn_to_qbnn: {type(d).__name__}{' ' + repr(name) if name else ''} was prepared with {how(d._calib_fused)} and is being converted "
                                f"with {how(fused)}: its statistics describe a different layer")
-        qbnn_layer.quant_dict = _calibrated_dict(d, name)
+        qbnn_layer.quant_dict = quant_dict_from_stats(d._schema, d.calib_minmax, d.calib_nonfinite, f"{type(d).__name__} '{name}'" if name else type(d).__name__)
         d._calib_release()
     qbnn_layer.__dict__["_float"] = d          # (not a submodule: quantize() takes it out again)
     qbnn_layer.quantize()

@@ -21,37 +21,8 @@ deterministic layers alone. ``fuse_conv_bn=True`` calibrates the layers ``bnn_to
 the BatchNorm's coefficient, output observed behind the BatchNorm -- which the reference's flow (``convert`` calls ``bnn_to_qbnn``
 without it) cannot express.
 """
-import torch
-
+from ..layers._calibration import observer_qparams      # noqa: F401 -- (its home; re-exported here, where the reference has it)
 from ..models import bnn_to_qbnn as _Q
-
-_F32_EPS = torch.finfo(torch.float32).eps
-
-
-def _f32(v):
-    return v.detach().to(device="cpu", dtype=torch.float32) if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64).to(torch.float32)
-
-
-def observer_qparams(min_val, max_val, dtype=torch.qint8):
-    """``MinMaxObserver.calculate_qparams`` for a recorded range, in fp32 tensor arithmetic on the CPU -> (scale, zero point) as 0-dim
-    fp32 / int64 tensors. ``torch.qint8``: the per-tensor symmetric quantiser of the five weight-side observers, scale =
-    max(|min(min, 0)|, max(max, 0)) / 127.5, zero point 0. ``torch.quint8``: the affine quantiser of the input and output observers,
-    scale = (max(max, 0) - min(min, 0)) / 255, zero point = clamp(0 - round(min(min, 0) / scale), 0, 255). Either scale is floored at
-    the fp32 epsilon."""
-    lo, hi = _f32(min_val), _f32(max_val)
-    zero = torch.zeros_like(lo)
-    min_neg, max_pos = torch.min(lo, zero), torch.max(hi, zero)
-    eps = torch.tensor(_F32_EPS, dtype=torch.float32)
-    if dtype == torch.qint8:
-        max_pos = torch.max(-min_neg, max_pos)
-        scale = torch.max(max_pos / (float(127 - (-128)) / 2), eps)
-        return scale, torch.zeros_like(scale, dtype=torch.int64)
-    if dtype == torch.quint8:
-        scale = torch.max((max_pos - min_neg) / float(255 - 0), eps)
-        zp = 0 - torch.round(min_neg / scale).to(torch.int64)
-        return scale, torch.clamp(zp, 0, 255)
-    raise ValueError(f"observer_qparams: dtype must be torch.qint8 (symmetric) or torch.quint8 (affine), got {dtype}")
-
 
 class _Prepare:
     """What the converter's walk (models/bnn_to_qbnn.py: ``_walk``) does to a model that is being prepared: the layer at every site the

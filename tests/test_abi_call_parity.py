@@ -5,14 +5,17 @@ scripted status, and lets the layers, the autograd bridge, ``functional`` and ``
 every layer class with and without bias, bare / ``mc_samples`` shared / stacked, on-chip / ``"torch"`` / ``inject_draw`` draws, the
 ``"split"`` inject path with its natural-layout retry and ``declined`` memo, the folded output stage (pool accepted and declined),
 Laplace priors, the scratch answer, training (plain, ``train_fused`` with ``kl_stub`` both ways, the ATen checker), a model with
-``mc.sync_model_packs``, ``materialize_last_draw`` and the refusals. A record holds the function name, every scalar, every field of
+``mc.sync_model_packs``, ``materialize_last_draw`` and the refusals; and the INT8 side: the calibrating forwards of the four prepared
+classes (on-chip / ``"torch"`` / ``inject_draw`` draws, ``mc_samples`` shared and stacked, a BatchNorm to fold), ``convert()`` of planted
+statistics with its refusals, and the four quantised classes after ``bnn_to_qbnn``. A record holds the function name, every scalar, every field of
 every struct and struct array, pointers by identity (tensor name + offset, or first-appearance index), and per case the output shapes,
 ``_last``, the call counter before and after, gradient shapes or the exception. This module replays the table against
 
 - ``tests/golden/abi_calls.txt``: the full text of the first and the last case that reaches each C function;
 - ``tests/golden/abi_calls_sha256.json``: one SHA-256 per case.
 
-Both were recorded from the commit before the forward path was split into named helpers, with the recorder as its only addition. A
+Both were recorded from the commit before the forward path was split into named helpers, with the recorder as its only addition; the
+``q8`` cases likewise from the commit before calibration moved into ``layers/_calibration.py``. A
 digest that differs is diffed with ``python tools/record_abi_calls.py --dump FILE`` on the two trees.
 """
 import importlib.util
@@ -60,7 +63,9 @@ def test_table_covers_every_c_function_the_cases_reach(recorded, golden_cases):
     reached = {c for _, calls in rec.values() for c in calls}
     assert {"bt_pack_sync", "bt_pack_sync_kl", "bt_fused_scratch_bytes", "bt_reparam_linear_fwd", "bt_flipout_linear_fwd", "bt_reparam_conv2d_fwd",
             "bt_flipout_conv2d_fwd", "bt_last_kernel_name", "bt_last_launch_info", "bt_pack_eps", "bt_pack_signs", "bt_maxpool_3x3s2", "bt_kl_normal",
-            "bt_kl_normal_bwd", "bt_kl_normal_bwd_segs", "bt_conv2d_bwd_workspace", "bt_conv2d_bwd_kl", "bt_rng_normal_fill", "bt_rng_sign_fill"} <= reached
+            "bt_kl_normal_bwd", "bt_kl_normal_bwd_segs", "bt_conv2d_bwd_workspace", "bt_conv2d_bwd_kl", "bt_rng_normal_fill", "bt_rng_sign_fill", "bt_q8_pack", "bt_q8_linear_fwd", "bt_q8_conv2d_fwd",
+            "bt_q8_flip_linear_fwd", "bt_q8_flip_conv2d_fwd", "bt_q8_observe_w", "bt_minmax_update", "bt_q8_flip_observe_x", "bt_q8_flip_observe_linear",
+            "bt_q8_flip_observe_conv2d"} <= reached
     in_table = {c for name in golden_cases for c in rec[name][1]}
     assert reached == in_table
 

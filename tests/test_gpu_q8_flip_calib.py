@@ -1,4 +1,4 @@
-"""GPU: the observers of the INT8 Flipout layers (csrc/bt_fused_flipout_obs.hip, the fused forward's OBS form) and the
+"""GPU: the observers of the INT8 Flipout layers (csrc/bt_q8_observe.hip's input sweep; csrc/bt_fused_flipout_obs.hip, the fused forward's OBS form) and the
 prepare(flipout=True) / calibrate / convert(flipout=True) flow built on them.
 
 The oracle of the ranges is tests/_q8_flip_model.py's ``float_flipout`` (double) through tests/_q8cal_flip_cases.py. Operands and the
@@ -429,3 +429,44 @@ def test_mc_forward_observes_every_sample():
     coef, shift = KF.bn_affine(net.bn1)
     want, mags = KF.host_stats(xs[0], c.mu_kernel, c.rho_kernel, d["eps_w"], d["sign_in"], d["sign_out"], c.mu_bias, c.rho_bias, d["eps_b"], KF.CONV1, coef.cpu(), shift.cpu())
     KF.check_rows(c.calib_minmax.cpu(), want, mags, "mc_forward conv1", skip=("add", "out"))          # (out: the BatchNorm output's range, checked in the folded test)
+
+
+def test_input_sweep_with_signs_off_xs_alignment():
+    """bt_q8_flip_observe_x over the walk's every branch: x starts 0 to 3 elements past a 16-byte boundary and the supplied signs 0 to
+    3, independently (only equal offsets read the signs as 16-byte quads); n of 1, 3, 4, 5, 8, 9 (head only; head and tail; one quad;
+    ...) and 1030 (more than one workgroup's threads); S = 2 with x shared and stacked (a stacked sample 1 starts n elements on: its
+    head differs from sample 0's). The extremes of x and of x * sign_in are planted, launch by launch, at the first element, the last
+    head element, the first quad element and the last tail element of one sample. The three rows are exact: ``torch.equal`` to
+    ``torch.aminmax`` of the host tensors. Operands and statistics sit inside guard bands; all of them are held intact."""
+    from bayesian_torch_amd import functional as F
+    S, rows = 2, ("in", "sign_in", "xp")
+    g = torch.Generator().manual_seed(11)
+    mm, bad = fresh_stats()
+    got, want = [], []
+    stray = torch.zeros((), dtype=torch.int64, device=dev())       # words of an operand's bands that no longer hold NaN, over all launches
+    for n in (1, 3, 4, 5, 8, 9, 1030):
+        for shared in (True, False):
+            for x_off in range(4):
+                for s_off in range(4):
+                    for sp in range(1 if shared else S):
+                        head = min((4 - (x_off + sp * n)) % 4, n)
+                        tail0 = head + (n - head) // 4 * 4
+                        spots = sorted({0, n - 1} | ({head - 1} if head else set()) | ({head} if tail0 > head else set()))
+                        for k, hi in enumerate(spots):
+                            x = torch.rand((1 if shared else S, n), generator=g) * 2 - 1
+                            sg = torch.where(torch.rand((S, n), generator=g) < 0.5, -1.0, 1.0)
+                            lo = spots[(k + 1) % len(spots)]
+                            x[sp, lo], x[sp, hi] = -9.0, 9.0                        # (one spot: the maximum stays)
+                            sg[:, lo] = sg[:, hi] = -1.0                            # x * sign: 9 at ``lo``, -9 at ``hi``
+                            xd, sd = G.place(x.reshape(-1).to(dev()), x_off), G.place(sg.reshape(-1).to(dev()), s_off)
+                            assert xd.data_ptr() % 16 == 4 * x_off and sd.data_ptr() % 16 == 4 * s_off
+                            mm.view[:, 0], mm.view[:, 1] = INF, -INF
+                            F.q8_flip_observe_x(xd, mm.view[R("in")], mm.view[R("sign_in")], mm.view[R("xp")], bad.view, S=S, shared_x=shared, sign_in=sd)
+                            got.append(mm.view[[R(r) for r in rows]])
+                            want.append(torch.tensor([K.aminmax(x), K.aminmax(sg), K.aminmax(x * sg)]))
+                            for t in (xd, sd):
+                                stray += t._base.numel() - t.numel() - t._base.view(torch.float32).isnan().sum()
+    got, (_, nonfinite) = torch.stack(got).cpu(), read(mm, bad)
+    print(f"{len(want)} launches; non-finite values met: {nonfinite}; operand band words changed: {int(stray)}")
+    assert len(want) == 876 and nonfinite == 0 and int(stray) == 0
+    assert torch.equal(got, torch.stack(want))

@@ -93,6 +93,8 @@ class Env:
                 out.append("%s=%s" % (fname, self.ptr(v)))
             elif isinstance(v, C.Structure):
                 out.append("%s=%s" % (fname, self.struct(v)))
+            elif ftype in (C.c_float, C.c_double):
+                out.append("%s=%r" % (fname, v))
             else:
                 out.append("%s=%d" % (fname, v))
         return "%s{%s}" % (type(s).__name__, " ".join(out))
@@ -113,7 +115,7 @@ class Env:
             if elem is C.c_void_p:
                 return "[%s]" % ", ".join(self.ptr(e) for e in a)
             return "[%s]" % ", ".join(str(int(e)) for e in a)
-        return str(int(a))
+        return repr(float(a)) if atype in (C.c_float, C.c_double) else str(int(a))
 
     # ---------------------------------------------------------------- the stand-in library
     def default(self, name):
@@ -177,7 +179,7 @@ def stand_in(env, cuda_tensors=False):
     """The replacements, for the duration of one case. ``cuda_tensors``: tensors also claim ``is_cuda`` (mc.sync_model_packs only
     takes layers whose parameters do)."""
     saved = [(o, n, getattr(o, n)) for o, n in ((_lib, "lib"), (_lib, "dev_f32"), (_lib, "on"), (_lib, "stream_ptr"), (torch.cuda, "current_device"),
-                                                 (torch, "empty"), (torch, "zeros"), (torch, "empty_like"))]
+                                                 (torch.cuda, "is_current_stream_capturing"), (torch, "empty"), (torch, "zeros"), (torch, "empty_like"))]
 
     def keeping(fn):
         def wrapped(*a, **k):
@@ -195,6 +197,7 @@ def stand_in(env, cuda_tensors=False):
 
     _lib.lib, _lib.dev_f32, _lib.on, _lib.stream_ptr = (lambda: env), dev_f32, (lambda device: contextlib.nullcontext()), (lambda device=None: 0)
     torch.cuda.current_device = lambda: 0
+    torch.cuda.is_current_stream_capturing = lambda: False      # (the real one raises without a GPU)
     torch.empty, torch.zeros, torch.empty_like = keeping(torch.empty), keeping(torch.zeros), keeping(torch.empty_like)
     if cuda_tensors:
         torch.Tensor.is_cuda = property(lambda self: True)
@@ -657,9 +660,9 @@ def _(env):
 
 
 # ---------------------------------------------------------------- refusals
-def refusal(name):
+def refusal(name, cuda_tensors=False):
     def deco(fn):
-        @case("refusal/" + name)
+        @case("refusal/" + name, cuda_tensors)
         def _(env):
             m, run = fn(env)
             try:
@@ -801,6 +804,226 @@ def _(env):
     with torch.no_grad(), mc.mc_samples(1, 2, call_base=env.tensor("call_base", 1)):
         m(x_for(env, "LinearFlipout"))
     return m, m.materialize_last_draw
+
+
+# ---------------------------------------------------------------- INT8: calibration (prepare / convert) and the quantised layers
+Q8_CLASSES = ("LinearReparameterization", "Conv2dReparameterization", "LinearFlipout", "Conv2dFlipout")
+
+
+def _prepared(env, cls, bn=None):
+    """A float layer of LAYERS' shape that observes from now on (the Flipout classes on request: ``prepare(flipout=True)``)."""
+    m = env.layer(cls, **LAYERS[cls][0])
+    kw = dict(flipout=True) if m._flip else {}
+    if bn is not None:
+        kw["bn"] = bn
+    m.prepare(**kw)
+    return m
+
+
+def _q8_calib(cls):
+    kw = LAYERS[cls][0]
+
+    @case("q8-calib/bare/" + cls, cuda_tensors=True)
+    def _(env):
+        m = _prepared(env, cls)
+        with torch.no_grad():
+            fwd(env, m, x_for(env, cls))
+            fwd(env, m, x_for(env, cls, name="x2"), return_kl=False)
+
+    @case("q8-calib/inject/" + cls, cuda_tensors=True)
+    def _(env):
+        m = _prepared(env, cls)
+        m.inject_draw = draw_for(env, m, cls, kw, 1)
+        with torch.no_grad():
+            fwd(env, m, x_for(env, cls))
+
+    @case("q8-calib/torch-mode/" + cls, cuda_tensors=True)
+    def _(env):
+        m = _prepared(env, cls)
+        rng.set_mode("torch")
+        with torch.no_grad():
+            fwd(env, m, x_for(env, cls))
+
+    @case("q8-calib/mc/" + cls, cuda_tensors=True)
+    def _(env):
+        m = _prepared(env, cls)
+        with torch.no_grad(), mc.mc_samples(2, 2, sample0=3):
+            env.lines.append("  -- x shared")
+            fwd(env, m, x_for(env, cls))
+            env.lines.append("  -- x stacked")
+            fwd(env, m, x_for(env, cls, S=2, name="x2"))
+
+    if cls.startswith("Conv"):
+        @case("q8-calib/batchnorm/" + cls, cuda_tensors=True)
+        def _(env):
+            bn = torch.nn.BatchNorm2d(kw["out_channels"]).eval()
+            env.modules.append(("bn.", bn))
+            m = _prepared(env, cls, bn)
+            env.note("calib", {k: getattr(m, k, "-") for k in ("calib_coef", "calib_shift", "_calib_fused")})
+            with torch.no_grad():
+                out, _ = fwd(env, m, x_for(env, cls))
+                env.lines.append("  -- the BatchNorm's hook: out is observed behind it")
+                env.note("bn(out)", bn(out))
+            m._calib_release()
+            with torch.no_grad():
+                env.lines.append("  -- released: the hook is gone")
+                env.note("bn(out)", bn(out))
+
+
+for _c in Q8_CLASSES:
+    _q8_calib(_c)
+
+
+def _quantised(env, cls, quant_dict=None):
+    """-> (the float layer, its INT8 twin after ``bnn_to_qbnn`` of a one-layer model). The two weight scales are planted (exact binary
+    fractions): everything the launch is handed is then the same on every host."""
+    from bayesian_torch_amd.models.bnn_to_qbnn import bnn_to_qbnn
+    f = getattr(BL, cls)(**LAYERS[cls][0])
+    model = torch.nn.Sequential(f)
+    env.layer(model, prefix="model.")
+    bnn_to_qbnn(model, flipout=f._flip)
+    q = model[0]
+    q.quantized_mu_scale.fill_(0.5)
+    q.quantized_sigma_scale.fill_(0.25)
+    q.quant_dict, q._cache = quant_dict, None
+    env.note("converted", type(q).__name__)
+    return f, q
+
+
+def _dict_of(n):
+    return [{"scale": 0.5 ** (k + 1), "zero_point": 0 if k < 2 else 100 + k} for k in range(n)]
+
+
+def _q8_layer(cls):
+    kw = LAYERS[cls][0]
+    n_pairs = 10 if "Flipout" in cls else 5
+
+    @case("q8/bare/" + cls, cuda_tensors=True)
+    def _(env):
+        _, q = _quantised(env, cls)
+        with torch.no_grad():
+            fwd(env, q, x_for(env, cls))
+            env.note("materialize", q.materialize_last_draw())
+            env.lines.append("  -- the packs are kept: no second bt_q8_pack")
+            fwd(env, q, x_for(env, cls, name="x2"), return_kl=False)
+
+    @case("q8/mc/" + cls, cuda_tensors=True)
+    def _(env):
+        _, q = _quantised(env, cls)
+        with torch.no_grad(), mc.mc_samples(2, 2, sample0=3):
+            env.lines.append("  -- x shared")
+            fwd(env, q, x_for(env, cls))
+            env.lines.append("  -- x stacked")
+            fwd(env, q, x_for(env, cls, S=2, name="x2"))
+
+    @case("q8/inject/" + cls, cuda_tensors=True)
+    def _(env):
+        f, q = _quantised(env, cls)
+        q.inject_draw = draw_for(env, f, cls, kw, 1)
+        with torch.no_grad():
+            fwd(env, q, x_for(env, cls))
+            env.note("materialize", q.materialize_last_draw())
+
+    @case("q8/torch-mode/" + cls, cuda_tensors=True)
+    def _(env):
+        _, q = _quantised(env, cls)
+        rng.set_mode("torch")
+        with torch.no_grad(), mc.mc_samples(2, 2):
+            fwd(env, q, x_for(env, cls))
+            env.note("materialize", q.materialize_last_draw())
+
+    @case("q8/want-q-and-quant-dict/" + cls, cuda_tensors=True)
+    def _(env):
+        _, q = _quantised(env, cls, _dict_of(n_pairs))
+        q.want_q = True
+        with torch.no_grad():
+            fwd(env, q, x_for(env, cls))
+
+    @refusal("q8-quant-dict-of-wrong-length/" + cls, cuda_tensors=True)
+    def _(env):
+        _, q = _quantised(env, cls, _dict_of(n_pairs - 1))
+        return q, _nograd(q, x_for(env, cls))
+
+
+for _c in Q8_CLASSES:
+    _q8_layer(_c)
+
+
+def _planted(m):
+    """Statistics as calibration batches would have left them, written on the host: row k is (-(k + 1) / 4, (k + 1) / 2)."""
+    k = torch.arange(1, m.calib_minmax.shape[0] + 1, dtype=torch.float32)
+    m.calib_minmax.copy_(torch.stack([-k / 4, k / 2], 1))
+    return m
+
+
+def _convert(env, m, **kw):
+    from bayesian_torch_amd.quantization import convert
+    model = torch.nn.Sequential()
+    model.add_module("conv1" if type(m).__name__.startswith("Conv") else "fc", m)
+    model.add_module("bn1", kw.pop("bn", torch.nn.Identity()))
+    convert(model, flipout=m._flip, **kw)
+    q = model[0]
+    env.note("converted", type(q).__name__)
+    env.note("quant_dict", q.quant_dict)
+    return q
+
+
+for _cls in Q8_CLASSES:
+    @case("q8-convert/planted/" + _cls)
+    def _(env, cls=_cls):
+        m = _planted(_prepared(env, cls))
+        _convert(env, m)
+
+    @refusal("q8-convert/empty-row/" + _cls)
+    def _(env, cls=_cls):
+        m = _planted(_prepared(env, cls))
+        m.calib_minmax[-1, 0] = float("inf")
+        return m, lambda: _convert(env, m)
+
+    @refusal("q8-convert/nonfinite/" + _cls)
+    def _(env, cls=_cls):
+        m = _planted(_prepared(env, cls))
+        m.calib_nonfinite.fill_(3)
+        return m, lambda: _convert(env, m)
+
+for _cls in ("Conv2dReparameterization", "Conv2dFlipout"):
+    @case("q8-convert/planted-with-batchnorm/" + _cls)
+    def _(env, cls=_cls):
+        bn = torch.nn.BatchNorm2d(LAYERS[cls][0]["out_channels"]).eval()
+        m = _planted(_prepared(env, cls, bn))
+        q = _convert(env, m, bn=bn, fuse_conv_bn=True)
+        env.note("bias", q.quantized_mu_bias)
+        env.note("hooks left on the BatchNorm", len(bn._forward_hooks))
+
+    @refusal("q8-convert/fuse-mismatch/" + _cls)
+    def _(env, cls=_cls):
+        bn = torch.nn.BatchNorm2d(LAYERS[cls][0]["out_channels"]).eval()
+        m = _planted(_prepared(env, cls, bn))
+        return m, lambda: _convert(env, m, bn=bn)
+
+    @refusal("q8-convert/fuse-mismatch-the-other-way/" + _cls)
+    def _(env, cls=_cls):
+        m = _planted(_prepared(env, cls))
+        return m, lambda: _convert(env, m, bn=torch.nn.BatchNorm2d(LAYERS[cls][0]["out_channels"]).eval(), fuse_conv_bn=True)
+
+
+for _cls in ("Conv2dReparameterization", "LinearFlipout"):
+    @refusal("q8-calib/forward-that-needs-grad/" + _cls)
+    def _(env, cls=_cls):
+        m = _prepared(env, cls)
+        return m, lambda: m(x_for(env, cls))
+
+    @refusal("q8-calib/stage-folded-after-prepare/" + _cls)
+    def _(env, cls=_cls):
+        m = _prepared(env, cls)
+        m.post_relu = True
+        return m, _nograd(m, x_for(env, cls))
+
+    @refusal("q8-calib/prepare-of-a-folded-layer/" + _cls)
+    def _(env, cls=_cls):
+        m = env.layer(cls, **LAYERS[cls][0])
+        m.post_relu = True
+        return m, lambda: m.prepare(flipout=True) if m._flip else m.prepare()
 
 
 # ==================================================================== running
