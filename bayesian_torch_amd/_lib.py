@@ -155,8 +155,25 @@ _PROTOS = {
     "bt_q8_flip_observe_conv2d": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, C.POINTER(bt_params), C.POINTER(bt_draws)] + [_vp] * 8),
     "bt_q8_flip_observe_linear": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int64, C.POINTER(bt_params), C.POINTER(bt_draws)] + [_vp] * 8),
     "bt_q8_flip_observe_x": (C.c_int, [C.c_int64, C.c_int32, _vp, C.c_int64, _vp, C.POINTER(bt_rng)] + [_vp] * 5),
+    # u8 activations between the INT8 layers (csrc/bt_q8_act.hip and the *_act forwards): x, x_kind, x_sample_stride, ..., out, out_blocked
+    "bt_q8_conv2d_fwd_act": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int32, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp,
+                                      _vp]),
+    "bt_q8_linear_fwd_act": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32, C.c_int64, C.POINTER(bt_q8_params), _vp, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_q8_flip_conv2d_fwd_act": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int32, C.c_int64, C.POINTER(bt_q8_flip_params), _vp, _vp, _vp, _vp,
+                                           C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_q8_flip_linear_fwd_act": (C.c_int, [C.c_int32] * 4 + [_vp, C.c_int32, C.c_int64, C.POINTER(bt_q8_flip_params), _vp, _vp, _vp, _vp, C.POINTER(bt_rng), _vp, _vp,
+                                           _vp]),
+    "bt_q8_act_quantize": (C.c_int, [_vp] + [C.c_int64] * 4 + [C.c_double, C.c_int32, _vp, _vp]),
+    "bt_q8_act_dequantize": (C.c_int, [_vp] + [C.c_int64] * 4 + [C.c_double, C.c_int32, _vp, _vp]),
+    "bt_q8_act_relu": (C.c_int, [_vp] + [C.c_int64] * 4 + [C.c_int32, _vp, _vp]),
+    "bt_q8_act_add": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_double, C.c_int32, _vp, C.POINTER(C.c_int64), C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                               _vp, _vp]),
+    "bt_q8_act_max_pool2d": (C.c_int, [_vp] + [C.c_int64] * 4 + [C.c_int32] * 6 + [_vp, _vp]),
+    "bt_q8_act_avg_pool": (C.c_int, [_vp] + [C.c_int64] * 4 + [C.c_int32, _vp, _vp]),
+    "bt_q8_act_unblock": (C.c_int, [_vp] + [C.c_int64] * 4 + [C.c_int32, _vp, _vp]),
 }
 EXPORTS = tuple(_PROTOS)
+Q8_X_F32, Q8_X_U8 = 0, 1      # BT_Q8_X_F32, BT_Q8_X_U8
 
 
 def lib():

@@ -17,6 +17,7 @@ struct Q8Args : Q8Core {
 
 struct Q8Reparam {
   static constexpr int kC = 1;
+  static constexpr bool kWords = true;   // xq - 128 of four levels is one sign-bit flip of their word
   typedef Q8Args Args;
   const Args& a;
   __device__ __forceinline__ Q8Reparam(const Args& args, int, uint32_t, uint32_t) : a(args) {}
@@ -41,6 +42,7 @@ struct Q8Reparam {
   }
   __device__ __forceinline__ void pads(int (&p)[1]) const { p[0] = (a.z_in - 128) & 0xFF; }
   __device__ __forceinline__ void activation(int xq, long long, int (&b)[1]) const { b[0] = (xq - 128) & 0xFF; }
+  __device__ __forceinline__ void activation_words(int lv, int (&w)[1]) const { w[0] = lv ^ (int)0x80808080u; }
   __device__ __forceinline__ void corrections(int (&zc)[1]) const { zc[0] = 128 - a.z_in; }
   // fbgemm's: ONE rounding of b * (1 / a) + float(acc)
   __device__ __forceinline__ float output(const int (&acc)[1], const float (&b)[1], long long) const {
@@ -66,10 +68,24 @@ __global__ __launch_bounds__(256) void q8_pack_kernel(const int8_t* __restrict__
   }
 }
 
-static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const float* x, long long x_sample_stride, const bt_q8_params* p, const float* eps_w,
-                      const float* eps_b, const bt_rng* rng, float* out, uint8_t* out_q, hipStream_t stream) {
+// [x u8][blocked destination][draws on chip]
+static const char* const kQ8Names[2][2][2] = {
+    {{"q8_fwd<i8 32x32x32,64x128,eps injected>", "q8_fwd<i8 32x32x32,64x128,eps on chip>"},
+     {"q8_fwd<i8 32x32x32,64x128,eps injected,out u8 blocked>", "q8_fwd<i8 32x32x32,64x128,eps on chip,out u8 blocked>"}},
+    {{"q8_fwd<i8 32x32x32,64x128,eps injected,x u8 blocked>", "q8_fwd<i8 32x32x32,64x128,eps on chip,x u8 blocked>"},
+     {"q8_fwd<i8 32x32x32,64x128,eps injected,x u8 blocked,out u8 blocked>", "q8_fwd<i8 32x32x32,64x128,eps on chip,x u8 blocked,out u8 blocked>"}}};
+
+// act: the *_act entry points -- x_kind says what x is, out_q is the BLOCKED image and out is optional beside it.
+static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const void* x, long long x_sample_stride, const bt_q8_params* p, const float* eps_w,
+                      const float* eps_b, const bt_rng* rng, float* out, uint8_t* out_q, hipStream_t stream, bool act = false, int x_kind = BT_Q8_X_F32) {
   const Q8Fail fail = {who};
-  if (int rc = q8_check_operands(fail, x, p, out, S, x_sample_stride, p ? p->mu_packed : nullptr, p ? p->sigma_packed : nullptr, g)) return rc;
+  if (act)
+    if (int rc = q8_check_act(fail, x_kind, x, out, out_q)) return rc;
+  if (int rc = q8_check_operands(fail, x, p, act && !out ? (const void*)out_q : (const void*)out, S, x_sample_stride, p ? p->mu_packed : nullptr,
+                                 p ? p->sigma_packed : nullptr, g))
+    return rc;
+  if (act)
+    if (int rc = q8_check_act_stride(fail, x_kind, x_sample_stride)) return rc;
   if (!eps_w && !rng) return fail(BT_ERR_BAD_ARG, "neither eps_w nor rng");
   if (eps_w && !eps_b && p->mu_b && p->sigma_b) return fail(BT_ERR_BAD_ARG, "eps_w without eps_b for a bias that has a sigma");
   const bt_q8_pair* pairs[5] = {&p->eps, &p->mul, &p->add, &p->in, &p->out};
@@ -95,8 +111,7 @@ static int q8_forward(const char* who, const bt_conv2d_geom& g, int S, const flo
   // With z_in == 128 a padding position is the MFMA's zero and no correction term reads the row sum.
   dim3 grid;
   if (int rc = q8_plan(fail, g, S, Ho, Wo, npix, {x, x_sample_stride, eps_w, eps_b, rng, out, out_q}, *p, p->in.zero_point == 128, a, grid)) return rc;
-  return launch_kernel(q8_walk_kernel<Q8Reparam>, eps_w ? "q8_fwd<i8 32x32x32,64x128,eps injected>" : "q8_fwd<i8 32x32x32,64x128,eps on chip>", who, grid,
-                       dim3(kQ8Threads), 0, 0, stream, a);
+  return q8_launch_walk<Q8Reparam>(act && x_kind == BT_Q8_X_U8, act && out_q, !eps_w, kQ8Names, who, grid, stream, a);
 }
 
 }  // namespace bt
@@ -123,4 +138,16 @@ extern "C" int bt_q8_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t S, c
                                 const float* eps_w, const float* eps_b, const bt_rng* rng, float* out, uint8_t* out_q, bt_stream_t stream) {
   const bt_conv2d_geom g = {B, In, 1, 1, Out, 1, 1, 1, 1, 0, 0, 1, 1, 1};
   return bt::q8_forward("bt_q8_linear_fwd", g, S, x, x_sample_stride, p, eps_w, eps_b, rng, out, out_q, (hipStream_t)stream);
+}
+
+extern "C" int bt_q8_conv2d_fwd_act(const bt_conv2d_geom* g, int32_t S, const void* x, int32_t x_kind, int64_t x_sample_stride, const bt_q8_params* p,
+                                    const float* eps_w, const float* eps_b, const bt_rng* rng, float* out, uint8_t* out_blocked, bt_stream_t stream) {
+  if (!g) return bt::set_error(BT_ERR_BAD_ARG, "bt_q8_conv2d_fwd_act: null geometry");
+  return bt::q8_forward("bt_q8_conv2d_fwd_act", *g, S, x, x_sample_stride, p, eps_w, eps_b, rng, out, out_blocked, (hipStream_t)stream, true, x_kind);
+}
+
+extern "C" int bt_q8_linear_fwd_act(int32_t B, int32_t In, int32_t Out, int32_t S, const void* x, int32_t x_kind, int64_t x_sample_stride, const bt_q8_params* p,
+                                    const float* eps_w, const float* eps_b, const bt_rng* rng, float* out, uint8_t* out_blocked, bt_stream_t stream) {
+  const bt_conv2d_geom g = {B, In, 1, 1, Out, 1, 1, 1, 1, 0, 0, 1, 1, 1};
+  return bt::q8_forward("bt_q8_linear_fwd_act", g, S, x, x_sample_stride, p, eps_w, eps_b, rng, out, out_blocked, (hipStream_t)stream, true, x_kind);
 }

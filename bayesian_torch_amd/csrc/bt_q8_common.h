@@ -34,16 +34,16 @@ constexpr int kQ8SU = 4;     // units (16 K positions each) per stage
 
 // What the walk reads; a chain's argument block derives from it.
 struct Q8Core {
-  const float* x;
-  long long x_sample_stride;
+  const void* x;   // fp32 [B][Ci][H][W], or (kXU8) the u8 blocked image [B][CB][H][W][16]
+  long long x_sample_stride;   // in elements of x's own layout
   const int8_t* qmu;
   const int8_t* qsg;
   const float* eps_w;
   const float* eps_b;
   const float* mu_b;
   const float* sigma_b;
-  float* out;
-  uint8_t* out_q;
+  float* out;        // fp32 [S][B][Co][Ho][Wo]; optional where the kernel writes the blocked image (kOutB)
+  uint8_t* out_q;    // u8, optional: [S][B][Co][Ho][Wo] beside out, or (kOutB) the blocked image [S][B][CBo][Ho][Wo][16]
   const uint32_t* call_base;
   RngKey kw, kb;
   uint32_t sample0;
@@ -110,7 +110,12 @@ __device__ __forceinline__ Q8Tap q8_tap(const Q8Core& a, int v, int ih0, int iw0
 //   activation(xq, off, b)               a quantised x and its offset in one sample's x -> kC bytes;
 //   corrections(zc)                      what multiplies the kC row sums;
 //   output(acc, b, off)                  kC corrected accumulators, bias terms, the offset in one sample's output -> the u8 level.
-template <class Chain>
+//   activation_words(lv, w)              (kWords only) four u8 levels in one word -> kC words, where no byte needs its own offset.
+// kXU8: x is the u8 blocked image at the pair (s_in, z_in) -- the 16 channels of one (pixel, tap) are one
+// aligned 16-byte load and the producer quantises nothing; bytes of channels >= Ci hold anything (the packs hold 0 there).
+// kOutB: the u8 level goes to the blocked image a.out_q, four consecutive channels of a lane as one dword (channels >= Co of the last
+// block: z_out), and the fp32 a.out is optional.
+template <class Chain, bool kXU8 = false, bool kOutB = false>
 __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Args a) {
   constexpr int kC = Chain::kC;
   __shared__ v4i lds_a[kC][kQ8SU * kQ8TM];   // 4 KiB each
@@ -177,8 +182,11 @@ __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Arg
     iw0 = ow * a.sw - a.pw;
     xoff0 = bi * (long long)a.Ci * a.H * a.W;
   }
-  const float* xb = a.x + (long long)s * a.x_sample_stride + xoff0;
   const long long plane = (long long)a.H * a.W;
+  // this pixel's image: fp32 [Ci][H][W], or the blocked u8 [CB][H][W][16]
+  const float* xb = static_cast<const float*>(a.x) + (long long)s * a.x_sample_stride + xoff0;
+  const uint8_t* xb8 = nullptr;
+  if constexpr (kXU8) xb8 = static_cast<const uint8_t*>(a.x) + (long long)s * a.x_sample_stride + (b_live ? (b_n / ((long long)a.Ho * a.Wo)) : 0) * a.CB * plane * 16;
   int pad[kC];
   chain.pads(pad);
 
@@ -190,10 +198,11 @@ __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Arg
   const int wm = wv & 1, wn = wv >> 1;
 
   // The global operands of a stage are fetched one stage ahead, into registers: this thread's 16 bytes of either pack and its 2 x 16
-  // fp32 values of x (0 where nothing is read). The loads are issued behind the barrier that publishes the current stage and are in
-  // flight under its MFMAs and the next stage's Philox rounds.
+  // fp32 values of x (0 where nothing is read) -- kXU8: its 2 x 16 bytes. The loads are issued behind the barrier that publishes the
+  // current stage and are in flight under its MFMAs and the next stage's Philox rounds.
   v4i pqm = {0, 0, 0, 0}, pqs = {0, 0, 0, 0};
-  float px[2][16];
+  float px[kXU8 ? 1 : 2][kXU8 ? 1 : 16];
+  v4i pxq[kXU8 ? 2 : 1];
   auto prefetch = [&](int u0) {
     const int va = u0 + a_ul;
     if (a_live && va < a.VU) {
@@ -207,13 +216,22 @@ __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Arg
     for (int k = 0; k < 2; ++k) {
       const int v = u0 + b_u2 + k;
       Q8Tap tp = {0, false, 0};
-      const float* xp = xb;
-      if (b_live && v < a.VU) {
-        tp = q8_tap(a, v, ih0, iw0, plane);
-        if (tp.inside) xp = xb + tp.off;
-      }
+      if constexpr (kXU8) {
+        pxq[k] = v4i{0, 0, 0, 0};
+        if (b_live && v < a.VU) {
+          tp = q8_tap(a, v, ih0, iw0, plane);
+          // (c0, ih, iw) of [CB][H][W][16]: block c0 / 16, pixel off - c0 * plane
+          if (tp.inside) pxq[k] = *reinterpret_cast<const v4i*>(xb8 + ((long long)(tp.c0 >> 4) * plane + (tp.off - (long long)tp.c0 * plane)) * 16);
+        }
+      } else {
+        const float* xp = xb;
+        if (b_live && v < a.VU) {
+          tp = q8_tap(a, v, ih0, iw0, plane);
+          if (tp.inside) xp = xb + tp.off;
+        }
 #pragma unroll
-      for (int j = 0; j < 16; ++j) px[k][j] = (tp.inside && tp.c0 + j < a.Ci) ? xp[(long long)j * plane] : 0.f;
+        for (int j = 0; j < 16; ++j) px[k][j] = (tp.inside && tp.c0 + j < a.Ci) ? xp[(long long)j * plane] : 0.f;
+      }
     }
   };
   prefetch(0);
@@ -263,6 +281,18 @@ __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Arg
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           int word[kC];
+          if constexpr (kXU8 && Chain::kWords) {
+            // whole words: a byte of a channel >= Ci meets a zero weight, whatever it holds
+            if (tp.inside) {
+              chain.activation_words(pxq[k][q], word);
+            } else {
+#pragma unroll
+              for (int c = 0; c < kC; ++c) word[c] = pad[c] * 0x01010101;
+            }
+#pragma unroll
+            for (int c = 0; c < kC; ++c) xq[c][q] = word[c];
+            continue;
+          }
 #pragma unroll
           for (int c = 0; c < kC; ++c) word[c] = 0;
 #pragma unroll
@@ -274,7 +304,10 @@ __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Arg
 #pragma unroll
               for (int c = 0; c < kC; ++c) byte[c] = 0;
             } else if (tp.inside) {
-              chain.activation(q8_quant_x(px[k][4 * q + j], a.inv_in, a.z_in), xoff0 + tp.off + (long long)(4 * q + j) * plane, byte);
+              int lv;
+              if constexpr (kXU8) lv = (int)(((unsigned)pxq[k][q] >> (8 * j)) & 0xFFu);
+              else lv = q8_quant_x(px[k][4 * q + j], a.inv_in, a.z_in);
+              chain.activation(lv, xoff0 + tp.off + (long long)(4 * q + j) * plane, byte);
             }
 #pragma unroll
             for (int c = 0; c < kC; ++c) word[c] |= byte[c] << (8 * j);
@@ -315,27 +348,65 @@ __global__ __launch_bounds__(kQ8Threads) void q8_walk_kernel(typename Chain::Arg
   const long long hw = (long long)a.Ho * a.Wo;
   int zc[kC];
   chain.corrections(zc);
-  float* const out_s = a.out + (long long)s * a.npix * a.Co;   // this sample's [B][Co][Ho][Wo]
-  uint8_t* const outq_s = a.out_q ? a.out_q + (long long)s * a.npix * a.Co : nullptr;
+  if constexpr (kOutB) {
+    const int CBo = (a.Co + 15) >> 4;
+    float* const out_s = a.out ? a.out + (long long)s * a.npix * a.Co : nullptr;
+    uint8_t* const outb_s = a.out_q + (long long)s * a.npix * CBo * 16;   // this sample's [B][CBo][Ho][Wo][16]
 #pragma unroll
-  for (int blk = 0; blk < 2; ++blk) {
-    const long long n = n0 + 64 * wn + 32 * blk + (lane & 31);
-    if (n >= a.npix) continue;
-    const long long bi = n / hw;
-    const long long obase = bi * a.Co * hw + (n - bi * hw);
+    for (int blk = 0; blk < 2; ++blk) {
+      const long long n = n0 + 64 * wn + 32 * blk + (lane & 31);
+      if (n >= a.npix) continue;
+      const long long bi = n / hw, pix = n - bi * hw;
+      const long long obase = bi * a.Co * hw + pix;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = 32 * wm + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-      const int co = co0 + row;
-      if (co >= a.Co) continue;
-      const long long oi = obase + (long long)co * hw;
-      int av[kC];
-      float bt[kC];
+      for (int g = 0; g < 4; ++g) {
+        // the lane's rows (i & 3) of register group g: four consecutive channels, one dword of the blocked image
+        const int row0 = 32 * wm + 8 * g + 4 * (lane >> 5);
+        const int cg = co0 + row0;
+        if (cg >= CBo * 16) continue;
+        unsigned word = 0;
 #pragma unroll
-      for (int c = 0; c < kC; ++c) av[c] = acc[c][blk][i] + zc[c] * row_sum[c][row], bt[c] = bias_term[c][row];
-      const float oq = chain.output(av, bt, oi);
-      out_s[oi] = __fmul_rn(__fsub_rn(oq, (float)a.z_out), a.s_out);
-      if (outq_s) outq_s[oi] = (uint8_t)oq;
+        for (int j = 0; j < 4; ++j) {
+          const int co = cg + j, row = row0 + j;
+          unsigned lv = (unsigned)a.z_out;
+          if (co < a.Co) {
+            const long long oi = obase + (long long)co * hw;
+            int av[kC];
+            float bt[kC];
+#pragma unroll
+            for (int c = 0; c < kC; ++c) av[c] = acc[c][blk][4 * g + j] + zc[c] * row_sum[c][row], bt[c] = bias_term[c][row];
+            const float oq = chain.output(av, bt, oi);
+            if (out_s) out_s[oi] = __fmul_rn(__fsub_rn(oq, (float)a.z_out), a.s_out);
+            lv = (unsigned)oq;
+          }
+          word |= lv << (8 * j);
+        }
+        *reinterpret_cast<unsigned*>(outb_s + ((bi * CBo + (cg >> 4)) * hw + pix) * 16 + (cg & 15)) = word;
+      }
+    }
+  } else {
+    float* const out_s = a.out + (long long)s * a.npix * a.Co;   // this sample's [B][Co][Ho][Wo]
+    uint8_t* const outq_s = a.out_q ? a.out_q + (long long)s * a.npix * a.Co : nullptr;
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk) {
+      const long long n = n0 + 64 * wn + 32 * blk + (lane & 31);
+      if (n >= a.npix) continue;
+      const long long bi = n / hw;
+      const long long obase = bi * a.Co * hw + (n - bi * hw);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = 32 * wm + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+        const int co = co0 + row;
+        if (co >= a.Co) continue;
+        const long long oi = obase + (long long)co * hw;
+        int av[kC];
+        float bt[kC];
+#pragma unroll
+        for (int c = 0; c < kC; ++c) av[c] = acc[c][blk][i] + zc[c] * row_sum[c][row], bt[c] = bias_term[c][row];
+        const float oq = chain.output(av, bt, oi);
+        out_s[oi] = __fmul_rn(__fsub_rn(oq, (float)a.z_out), a.s_out);
+        if (outq_s) outq_s[oi] = (uint8_t)oq;
+      }
     }
   }
 }
@@ -402,7 +473,7 @@ inline int q8_check_sizes(const Q8Fail& fail, const bt_conv2d_geom& g, int S, lo
 
 // What an entry point hands the plan besides the geometry: the operands both chains have. P: bt_q8_params or bt_q8_flip_params.
 struct Q8Operands {
-  const float* x;
+  const void* x;
   long long x_sample_stride;
   const float* eps_w;
   const float* eps_b;
@@ -432,6 +503,36 @@ inline int q8_plan(const Q8Fail& fail, const bt_conv2d_geom& g, int S, long long
   grid = dim3((unsigned)((npix + kQ8TN - 1) / kQ8TN), (unsigned)((g.Co + kQ8TM - 1) / kQ8TM), (unsigned)S);
   if (grid.y > 65535u) return fail(BT_ERR_UNSUPPORTED, "more than 65535 * 64 output channels");
   return BT_OK;
+}
+
+// The *_act entry points: x is fp32 NCHW or the u8 blocked image, the result goes to fp32 `out`, to the u8
+// blocked image `out_b`, or to both. What they refuse beyond q8_check_operands, before any launch.
+inline int q8_check_act(const Q8Fail& fail, int x_kind, const void* x, const float* out, const uint8_t* out_b) {
+  if (x_kind != BT_Q8_X_F32 && x_kind != BT_Q8_X_U8) return fail(BT_ERR_BAD_ARG, "x_kind is neither BT_Q8_X_F32 nor BT_Q8_X_U8");
+  if (!out && !out_b) return fail(BT_ERR_BAD_ARG, "neither out nor out_blocked");
+  if (x_kind == BT_Q8_X_U8 && (((uintptr_t)x) & 15u)) return fail(BT_ERR_BAD_ARG, "a u8 blocked x must be 16-byte aligned");
+  if (((uintptr_t)out_b) & 15u) return fail(BT_ERR_BAD_ARG, "out_blocked must be 16-byte aligned");
+  return BT_OK;
+}
+
+// One sample's x in elements of its own layout: what x_sample_stride must be a multiple of 16 of for the blocked image.
+inline int q8_check_act_stride(const Q8Fail& fail, int x_kind, long long x_sample_stride) {
+  if (x_kind == BT_Q8_X_U8 && (x_sample_stride & 15)) return fail(BT_ERR_BAD_ARG, "the sample stride of a u8 blocked x must be a multiple of 16");
+  return BT_OK;
+}
+
+// The walk's instantiation for (x source, destination). names: [x u8][blocked destination][draws on chip].
+template <class Chain>
+inline int q8_launch_walk(bool x_u8, bool out_b, bool on_chip, const char* const (&names)[2][2][2], const char* who, dim3 grid, hipStream_t stream,
+                          const typename Chain::Args& a) {
+  const char* name = names[x_u8][out_b][on_chip];
+  const dim3 block(kQ8Threads);
+  if (x_u8) {
+    if (out_b) return launch_kernel(q8_walk_kernel<Chain, true, true>, name, who, grid, block, 0, 0, stream, a);
+    return launch_kernel(q8_walk_kernel<Chain, true, false>, name, who, grid, block, 0, 0, stream, a);
+  }
+  if (out_b) return launch_kernel(q8_walk_kernel<Chain, false, true>, name, who, grid, block, 0, 0, stream, a);
+  return launch_kernel(q8_walk_kernel<Chain, false, false>, name, who, grid, block, 0, 0, stream, a);
 }
 
 }  // namespace bt

@@ -33,6 +33,7 @@ struct Q8FlipArgs : Q8Core {
 
 struct Q8Flip {
   static constexpr int kC = 2;
+  static constexpr bool kWords = false;   // every element has a sign of its own: bytes, with their offsets
   typedef Q8FlipArgs Args;
   const Args& a;
   uint32_t skey_in, skey_out;       // the sample's sign streams
@@ -93,11 +94,26 @@ static int q8_sign_level(float v, float s, int z) {
   return (int)q - z;
 }
 
-static int q8_flip_forward(const char* who, const bt_conv2d_geom& g, int S, const float* x, long long x_sample_stride, const bt_q8_flip_params* p,
+// [x u8][blocked destination][draws on chip]
+static const char* const kQ8FlipNames[2][2][2] = {
+    {{"q8_flip_fwd<i8 32x32x32,64x128,draws injected>", "q8_flip_fwd<i8 32x32x32,64x128,draws on chip>"},
+     {"q8_flip_fwd<i8 32x32x32,64x128,draws injected,out u8 blocked>", "q8_flip_fwd<i8 32x32x32,64x128,draws on chip,out u8 blocked>"}},
+    {{"q8_flip_fwd<i8 32x32x32,64x128,draws injected,x u8 blocked>", "q8_flip_fwd<i8 32x32x32,64x128,draws on chip,x u8 blocked>"},
+     {"q8_flip_fwd<i8 32x32x32,64x128,draws injected,x u8 blocked,out u8 blocked>",
+      "q8_flip_fwd<i8 32x32x32,64x128,draws on chip,x u8 blocked,out u8 blocked>"}}};
+
+// act: the *_act entry points -- x_kind says what x is, out_q is the BLOCKED image and out is optional beside it.
+static int q8_flip_forward(const char* who, const bt_conv2d_geom& g, int S, const void* x, long long x_sample_stride, const bt_q8_flip_params* p,
                            const float* eps_w, const float* eps_b, const float* sign_in, const float* sign_out, const bt_rng* rng, float* out, uint8_t* out_q,
-                           hipStream_t stream) {
+                           hipStream_t stream, bool act = false, int x_kind = BT_Q8_X_F32) {
   const Q8Fail fail = {who};
-  if (int rc = q8_check_operands(fail, x, p, out, S, x_sample_stride, p ? p->mu_packed : nullptr, p ? p->sigma_packed : nullptr, g)) return rc;
+  if (act)
+    if (int rc = q8_check_act(fail, x_kind, x, out, out_q)) return rc;
+  if (int rc = q8_check_operands(fail, x, p, act && !out ? (const void*)out_q : (const void*)out, S, x_sample_stride, p ? p->mu_packed : nullptr,
+                                 p ? p->sigma_packed : nullptr, g))
+    return rc;
+  if (act)
+    if (int rc = q8_check_act_stride(fail, x_kind, x_sample_stride)) return rc;
   if (!eps_w && !rng) return fail(BT_ERR_BAD_ARG, "neither eps_w nor rng");
   if (eps_w && (!sign_in || !sign_out)) return fail(BT_ERR_BAD_ARG, "eps_w without sign_in and sign_out: a supplied draw is whole or absent");
   if (!eps_w && (sign_in || sign_out)) return fail(BT_ERR_BAD_ARG, "a sign tensor without eps_w: a supplied draw is whole or absent");
@@ -139,8 +155,7 @@ static int q8_flip_forward(const char* who, const bt_conv2d_geom& g, int S, cons
   dim3 grid;
   if (int rc = q8_plan(fail, g, S, Ho, Wo, npix, {x, x_sample_stride, eps_w, eps_b, rng, out, out_q}, *p, p->in.zero_point == 128 && p->xp.zero_point == 128, a, grid))
     return rc;
-  return launch_kernel(q8_walk_kernel<Q8Flip>, eps_w ? "q8_flip_fwd<i8 32x32x32,64x128,draws injected>" : "q8_flip_fwd<i8 32x32x32,64x128,draws on chip>", who, grid,
-                       dim3(kQ8Threads), 0, 0, stream, a);
+  return q8_launch_walk<Q8Flip>(act && x_kind == BT_Q8_X_U8, act && out_q, !eps_w, kQ8FlipNames, who, grid, stream, a);
 }
 
 }  // namespace bt
@@ -157,4 +172,20 @@ extern "C" int bt_q8_flip_linear_fwd(int32_t B, int32_t In, int32_t Out, int32_t
                                      uint8_t* out_q, bt_stream_t stream) {
   const bt_conv2d_geom g = {B, In, 1, 1, Out, 1, 1, 1, 1, 0, 0, 1, 1, 1};
   return bt::q8_flip_forward("bt_q8_flip_linear_fwd", g, S, x, x_sample_stride, p, eps_w, eps_b, sign_in, sign_out, rng, out, out_q, (hipStream_t)stream);
+}
+
+extern "C" int bt_q8_flip_conv2d_fwd_act(const bt_conv2d_geom* g, int32_t S, const void* x, int32_t x_kind, int64_t x_sample_stride, const bt_q8_flip_params* p,
+                                         const float* eps_w, const float* eps_b, const float* sign_in, const float* sign_out, const bt_rng* rng, float* out,
+                                         uint8_t* out_blocked, bt_stream_t stream) {
+  if (!g) return bt::set_error(BT_ERR_BAD_ARG, "bt_q8_flip_conv2d_fwd_act: null geometry");
+  return bt::q8_flip_forward("bt_q8_flip_conv2d_fwd_act", *g, S, x, x_sample_stride, p, eps_w, eps_b, sign_in, sign_out, rng, out, out_blocked, (hipStream_t)stream,
+                             true, x_kind);
+}
+
+extern "C" int bt_q8_flip_linear_fwd_act(int32_t B, int32_t In, int32_t Out, int32_t S, const void* x, int32_t x_kind, int64_t x_sample_stride,
+                                         const bt_q8_flip_params* p, const float* eps_w, const float* eps_b, const float* sign_in, const float* sign_out,
+                                         const bt_rng* rng, float* out, uint8_t* out_blocked, bt_stream_t stream) {
+  const bt_conv2d_geom g = {B, In, 1, 1, Out, 1, 1, 1, 1, 0, 0, 1, 1, 1};
+  return bt::q8_flip_forward("bt_q8_flip_linear_fwd_act", g, S, x, x_sample_stride, p, eps_w, eps_b, sign_in, sign_out, rng, out, out_blocked, (hipStream_t)stream,
+                             true, x_kind);
 }

@@ -696,11 +696,55 @@ def q8_pack(q_mu, q_sigma):
     return mp, sp
 
 
-def _q8_launch(who, x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, rng, want_q, params, draws=None):
+def _dev_u8(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what} is on {t.device}: the INT8 forward runs on a HIP (MI355X) device only; there is no CPU implementation of this path")
+    if t.dtype != torch.uint8:
+        raise TypeError(f"{what} must be uint8, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _XShape:
+    """What ``_geometry`` reads of an input: the LOGICAL shape of a blocked u8 image."""
+
+    def __init__(self, shape):
+        self.shape = tuple(int(v) for v in shape)
+
+    def dim(self):
+        return len(self.shape)
+
+    def numel(self):
+        return math.prod(self.shape)
+
+
+def q8_blocked_shape(shape):
+    """The storage of a quantised activation of logical shape [N, C, H, W] or [N, F]: u8 [N, CB, H, W, 16] / [N, CB * 16], CB = ceil(C / 16)
+    (include/bt_hip.h)."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 2:
+        return (shape[0], (shape[1] + 15) // 16 * 16)
+    if len(shape) != 4:
+        raise RuntimeError(f"a quantised activation is [N, C, H, W] or [N, F], got {shape}")
+    return (shape[0], (shape[1] + 15) // 16, shape[2], shape[3], 16)
+
+
+def _q8_launch(who, x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, rng, want_q, params, draws=None, x_shape=None, dest="f32"):
     """What the two INT8 forwards share: the operands, the draw sizes, the geometry, the outputs and the linear / conv2d call of
     ``bt_<who>_*_fwd``. params(mu_packed, sigma_packed, mu_b, sigma_b) -> the entry's params struct; draws(B, x_elems, tail) -> the
-    pointers the entry takes between eps_b and rng (checked against the geometry there)."""
-    x = _lib.dev_f32(x, "input")
+    pointers the entry takes between eps_b and rng (checked against the geometry there). x_shape: x is the u8 BLOCKED image of that
+    logical shape; dest "f32" / "u8" / "both": what is written -- with either a ``bt_<who>_*_fwd_act`` call, whose u8 result is the
+    blocked image (want_q does not apply)."""
+    act = x_shape is not None or dest != "f32"
+    if dest not in ("f32", "u8", "both"):
+        raise ValueError(f"{who}_forward: dest must be 'f32', 'u8' or 'both', got {dest!r}")
+    if x_shape is None:
+        x = _lib.dev_f32(x, "input")
+        xs = x
+    else:
+        x = _dev_u8(x, "input")
+        xs = _XShape(x_shape)
+        if x.numel() != math.prod(q8_blocked_shape(xs.shape)):
+            raise RuntimeError(f"{who}_forward: the blocked image of {xs.shape} holds {math.prod(q8_blocked_shape(xs.shape))} bytes, got {x.numel()}")
     mu_b, sigma_b = _lib.dev_f32(mu_b, "mu_b"), _lib.dev_f32(sigma_b, "sigma_b")
     eps_w, eps_b = _lib.dev_f32(eps_w, "eps_w"), _lib.dev_f32(eps_b, "eps_b")
     mp, sp = _dev_i8(packs[0], "mu_packed"), _dev_i8(packs[1], "sigma_packed")
@@ -711,43 +755,53 @@ def _q8_launch(who, x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, e
     if eps_b is not None and eps_b.numel() != S * wshape[0]:
         raise RuntimeError(f"{who}_forward: eps_b must be [S={S}, {wshape[0]}]")
     dev = x.device
-    B, geom, x_elems, tail = _geometry(x, _Shape(wshape), conv, S, shared_x)
+    B, geom, x_elems, tail = _geometry(xs, _Shape(wshape), conv, S, shared_x)
     more = draws(B, x_elems, tail) if draws else ()
-    out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev)
-    out_q = torch.empty((S * B,) + tail, dtype=torch.uint8, device=dev) if want_q else None
+    out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev) if dest != "u8" else None
+    if act:
+        out_q = torch.empty(q8_blocked_shape((S * B,) + tail), dtype=torch.uint8, device=dev) if dest != "f32" else None
+    else:
+        out_q = torch.empty((S * B,) + tail, dtype=torch.uint8, device=dev) if want_q else None
     P = params(mp.data_ptr(), sp.data_ptr(), _lib.ptr(mu_b), _lib.ptr(sigma_b))
     Rg = _rng(*rng)
-    tail_args = (x.data_ptr(), 0 if shared_x else x_elems, C.byref(P), _lib.ptr(eps_w), _lib.ptr(eps_b), *more, C.byref(Rg), out.data_ptr(), _lib.ptr(out_q),
+    stride = 0 if shared_x else (x_elems if x_shape is None else x.numel() // S)
+    kind = (_lib.Q8_X_F32 if x_shape is None else _lib.Q8_X_U8,) if act else ()
+    tail_args = (x.data_ptr(), *kind, stride, C.byref(P), _lib.ptr(eps_w), _lib.ptr(eps_b), *more, C.byref(Rg), _lib.ptr(out), _lib.ptr(out_q),
                  _lib.stream_ptr(dev))
+    sfx = "_act" if act else ""
     with _lib.on(dev):
         if conv is None:
-            _lib.check(getattr(_lib.lib(), f"bt_{who}_linear_fwd")(B, wshape[1], wshape[0], S, *tail_args))
+            _lib.check(getattr(_lib.lib(), f"bt_{who}_linear_fwd{sfx}")(B, wshape[1], wshape[0], S, *tail_args))
         else:
-            _lib.check(getattr(_lib.lib(), f"bt_{who}_conv2d_fwd")(C.byref(geom), S, *tail_args))
+            _lib.check(getattr(_lib.lib(), f"bt_{who}_conv2d_fwd{sfx}")(C.byref(geom), S, *tail_args))
     return out, out_q
 
 
 def q8_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, *, conv=None, S=1, shared_x=True, eps_w=None, eps_b=None,
-               seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False):
+               seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False, x_shape=None, dest="f32"):
     """The INT8 fused forward (bt_q8_conv2d_fwd / bt_q8_linear_fwd; the arithmetic is include/bt_hip.h's). x: fp32 [B, Ci, H, W]
     (conv: dict(stride, padding, dilation, groups)) or [B, In] (conv None); packs: q8_pack's; wshape: the weight's natural shape;
     pairs: five (scale, zero point) -- eps, mul, add, in, out; eps_w [S, *wshape] and eps_b [S, Co] supplied, or None for the on-chip
-    streams. -> (out fp32 [S * B, Co, ...], the u8 image or None)."""
+    streams. -> (out fp32 [S * B, Co, ...], the u8 image or None).
+    u8 activations (bt_q8_*_fwd_act): x_shape -- x is the u8 BLOCKED image (``q8_blocked_shape``) of that
+    logical shape at the pair ``pairs[in]``; dest "u8" / "both" -- the result is the blocked image at ``pairs[out]`` (and out is None
+    for "u8": nothing fp32-sized is written). -> (out or None, the blocked image or None)."""
     pr = [_lib.bt_q8_pair(float(s), int(z), 0) for s, z in pairs]
     return _q8_launch("q8", x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, (seed, call, layer_id, sample0, call_base), want_q,
-                      lambda *ptrs: _lib.bt_q8_params(pr[0], pr[1], pr[2], pr[3], pr[4], float(s_mu), float(s_sigma), *ptrs))
+                      lambda *ptrs: _lib.bt_q8_params(pr[0], pr[1], pr[2], pr[3], pr[4], float(s_mu), float(s_sigma), *ptrs), x_shape=x_shape, dest=dest)
 
 
 Q8_FLIP_PAIRS = ("eps", "delta", "in", "mean", "sign_in", "sign_out", "xp", "pert", "pert_signed", "out")      # the order of a ten-entry quant_dict
 
 
 def q8_flip_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=None, *, conv=None, S=1, shared_x=True, eps_w=None, eps_b=None,
-                    sign_in=None, sign_out=None, seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False):
+                    sign_in=None, sign_out=None, seed=0, call=0, layer_id=0, sample0=0, call_base=None, want_q=False, x_shape=None, dest="f32"):
     """The INT8 Flipout forward (bt_q8_flip_conv2d_fwd / bt_q8_flip_linear_fwd; the arithmetic is include/bt_hip.h's): both
     contractions and the operator chain between them in one launch. Arguments as ``q8_forward``, but ``pairs`` holds TEN (scale, zero
     point) in the order ``Q8_FLIP_PAIRS``, and a supplied draw is whole or absent: eps_w [S, *wshape], eps_b [S, Co] (when there is a
     sigma_b), sign_in fp32 [S, B, *x.shape[1:]] and sign_out fp32 [S, B, Co, ...] (a negative value means -1, anything else +1), or
-    all None for the on-chip streams (tensors 0 to 3). -> (out fp32 [S * B, Co, ...], the u8 image or None)."""
+    all None for the on-chip streams (tensors 0 to 3). -> (out fp32 [S * B, Co, ...], the u8 image or None). ``x_shape`` / ``dest``: as
+    ``q8_forward``; the sign tensors stay in the LOGICAL (natural) order."""
     sign_in, sign_out = _lib.dev_f32(sign_in, "sign_in"), _lib.dev_f32(sign_out, "sign_out")
     if len(pairs) != len(Q8_FLIP_PAIRS):
         raise ValueError(f"q8_flip_forward: pairs must hold ten (scale, zero point): {', '.join(Q8_FLIP_PAIRS)}")
@@ -762,7 +816,99 @@ def q8_flip_forward(x, packs, wshape, s_mu, s_sigma, pairs, mu_b=None, sigma_b=N
 
     pr = [_lib.bt_q8_pair(float(s), int(z), 0) for s, z in pairs]
     return _q8_launch("q8_flip", x, packs, wshape, mu_b, sigma_b, conv, S, shared_x, eps_w, eps_b, (seed, call, layer_id, sample0, call_base), want_q,
-                      lambda *ptrs: _lib.bt_q8_flip_params(*pr, float(s_mu), float(s_sigma), *ptrs), signs)
+                      lambda *ptrs: _lib.bt_q8_flip_params(*pr, float(s_mu), float(s_sigma), *ptrs), signs, x_shape=x_shape, dest=dest)
+
+
+# ---------------------------------------------------------------------------- u8 activations between the INT8 layers (csrc/bt_q8_act.hip)
+# The launches quantization/qact.py's carrier is built on: blocked u8 images (``q8_blocked_shape``) in, blocked u8 images out, each ONE
+# launch on the current stream with no host synchronisation. ``shape`` is always the LOGICAL shape, [N, C, H, W] or [N, F].
+def _nchw(shape):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 2:
+        return (shape[0], shape[1], 1, 1)
+    if len(shape) != 4:
+        raise RuntimeError(f"a quantised activation is [N, C, H, W] or [N, F], got {shape}")
+    return shape
+
+
+def _act_call(name, dev, *args):
+    with _lib.on(dev):
+        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr(dev)))
+
+
+def _blocked(q, shape, what):
+    q = _dev_u8(q, what)
+    if q.numel() != math.prod(q8_blocked_shape(shape)):
+        raise RuntimeError(f"{what}: the blocked image of {tuple(shape)} holds {math.prod(q8_blocked_shape(shape))} bytes, got {q.numel()}")
+    return q
+
+
+def q8_act_quantize(x, scale, zero_point):
+    """fp32 [N, C, H, W] or [N, F] -> its blocked u8 image at (scale, zero_point) (bt_q8_act_quantize: quantize_per_tensor)."""
+    x = _lib.dev_f32(x, "input")
+    q = torch.empty(q8_blocked_shape(x.shape), dtype=torch.uint8, device=x.device)
+    _act_call("bt_q8_act_quantize", x.device, x.data_ptr(), *_nchw(x.shape), float(scale), int(zero_point), q.data_ptr())
+    return q
+
+
+def q8_act_dequantize(q, shape, scale, zero_point):
+    """The blocked image of ``shape`` -> fp32 in natural order, (q - z) * s (bt_q8_act_dequantize)."""
+    q = _blocked(q, shape, "q8_act_dequantize")
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=q.device)
+    _act_call("bt_q8_act_dequantize", q.device, q.data_ptr(), *_nchw(shape), float(scale), int(zero_point), out.data_ptr())
+    return out
+
+
+def q8_act_relu(q, shape, zero_point, inplace=False):
+    """max(q, z) on a blocked image (bt_q8_act_relu); inplace: q itself is overwritten and returned."""
+    q = _blocked(q, shape, "q8_act_relu")
+    out = q if inplace else torch.empty_like(q)
+    _act_call("bt_q8_act_relu", q.device, q.data_ptr(), *_nchw(shape), int(zero_point), out.data_ptr())
+    return out
+
+
+def q8_act_add(a, a_shape, a_pair, b, b_shape, b_pair, out_pair, relu=False):
+    """torch.ops.quantized.add / add_relu of two blocked images of one shape -> the blocked image at out_pair (bt_q8_act_add)."""
+    a, b = _blocked(a, a_shape, "q8_act_add"), _blocked(b, b_shape, "q8_act_add")
+    out = torch.empty_like(a)
+    sa, sb = (C.c_int64 * 4)(*_nchw(a_shape)), (C.c_int64 * 4)(*_nchw(b_shape))
+    _act_call("bt_q8_act_add", a.device, a.data_ptr(), sa, float(a_pair[0]), int(a_pair[1]), b.data_ptr(), sb, float(b_pair[0]), int(b_pair[1]), float(out_pair[0]),
+              int(out_pair[1]), int(bool(relu)), out.data_ptr())
+    return out
+
+
+def q8_act_max_pool2d(q, shape, kernel, stride, padding):
+    """The maximum of the levels over kernel windows, padding ignored -> (blocked image, its logical shape) (bt_q8_act_max_pool2d)."""
+    q = _blocked(q, shape, "q8_act_max_pool2d")
+    N, Cc, H, W = _nchw(shape)
+    (kh, kw), (sh, sw), (ph, pw) = kernel, stride, padding
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    if min(kh, kw, sh, sw) < 1 or Ho < 1 or Wo < 1:
+        raise RuntimeError("q8_act_max_pool2d: pooling output would be empty")
+    oshape = (N, Cc, Ho, Wo)
+    out = torch.empty(q8_blocked_shape(oshape), dtype=torch.uint8, device=q.device)
+    _act_call("bt_q8_act_max_pool2d", q.device, q.data_ptr(), N, Cc, H, W, kh, kw, sh, sw, ph, pw, out.data_ptr())
+    return out, oshape
+
+
+def q8_act_avg_pool(q, shape, zero_point):
+    """The global average pool [N, C, H, W] -> (blocked image, [N, C, 1, 1]) at the same pair (bt_q8_act_avg_pool)."""
+    q = _blocked(q, shape, "q8_act_avg_pool")
+    N, Cc, H, W = _nchw(shape)
+    oshape = (N, Cc, 1, 1)
+    out = torch.empty(q8_blocked_shape(oshape), dtype=torch.uint8, device=q.device)
+    _act_call("bt_q8_act_avg_pool", q.device, q.data_ptr(), N, Cc, H, W, int(zero_point), out.data_ptr())
+    return out, oshape
+
+
+def q8_act_unblock(q, shape, zero_point):
+    """Flatten [N, C, H, W] to [N, C * H * W] in NCHW feature order -> (blocked image, its logical shape) (bt_q8_act_unblock)."""
+    q = _blocked(q, shape, "q8_act_unblock")
+    N, Cc, H, W = _nchw(shape)
+    oshape = (N, Cc * H * W)
+    out = torch.empty(q8_blocked_shape(oshape), dtype=torch.uint8, device=q.device)
+    _act_call("bt_q8_act_unblock", q.device, q.data_ptr(), N, Cc, H, W, int(zero_point), out.data_ptr())
+    return out, oshape
 
 
 # ---------------------------------------------------------------------------- calibration of the INT8 layers (csrc/bt_q8_observe.hip)

@@ -17,6 +17,11 @@ import torch
 import torch.nn as nn
 
 
+def _qact():
+    from ..quantization import qact
+    return qact
+
+
 class _Basic(nn.Module):
     expansion = 1
 
@@ -35,6 +40,8 @@ class _Basic(nn.Module):
             return self.conv2(self.conv1(x), residual=skip)
         y = self.relu(self.bn1(self.conv1(x)))
         y = self.bn2(self.conv2(y))
+        if getattr(self, "u8", False):             # u8_inference(): y and skip are quint8 carriers, added as the reference's QResNet adds them
+            return _qact().add_relu(y, skip)
         return self.relu(y + skip)
 
 
@@ -60,6 +67,8 @@ class _Bottle(nn.Module):
         y = self.relu(self.bn1(self.conv1(x)))
         y = self.relu(self.bn2(self.conv2(y)))
         y = self.bn3(self.conv3(y))
+        if getattr(self, "u8", False):
+            return _qact().add_relu(y, skip)
         return self.relu(y + skip)
 
 
@@ -157,4 +166,32 @@ def fuse_inference(model):
                 blk.downsample[1] = nn.Identity()
             blk.fused = True
     model.fused = True
+    return model
+
+
+def u8_inference(model):
+    """Keep the activations of an INT8 ResNet u8 from the stem to the classifier (quantization/qact.py). The
+    model must come from ``bnn_to_qbnn(fuse_conv_bn=True)`` (or ``quantization.convert(fuse_conv_bn=True)``): every conv quantised,
+    every BatchNorm folded. The stem returns a quint8 carrier; ReLU, the max-pool, the average pool and flatten reach it through the
+    model's own modules; every block ends in ``add_relu(y, skip)`` at the reference QResNet's scale, max(y.q_scale(), skip.q_scale())
+    with zero point 0; ``fc`` dequantises."""
+    from ..layers._quantized import _QuantizedLayer
+    convs = [model.conv1]
+    for stage in (model.layer1, model.layer2, model.layer3, model.layer4):
+        for blk in stage:
+            last = 3 if isinstance(blk, _Bottle) else 2
+            convs += [getattr(blk, f"conv{i}") for i in range(1, last + 1)]
+            bns = [getattr(blk, f"bn{i}") for i in range(1, last + 1)]
+            if blk.downsample is not None:
+                convs.append(blk.downsample[0])
+                bns.append(blk.downsample[1])
+            if not all(isinstance(b, nn.Identity) for b in bns):
+                raise RuntimeError("u8_inference: an unfolded BatchNorm (convert with fuse_conv_bn=True): there is no quantised BatchNorm")
+    if not isinstance(model.bn1, nn.Identity) or not all(isinstance(c, _QuantizedLayer) for c in convs) or not isinstance(model.fc, _QuantizedLayer):
+        raise RuntimeError("u8_inference: the model must be converted by bnn_to_qbnn(fuse_conv_bn=True): every conv and the fc quantised, every BatchNorm folded")
+    model.conv1.return_quantized = True
+    for stage in (model.layer1, model.layer2, model.layer3, model.layer4):
+        for blk in stage:
+            blk.u8 = True
+    model.u8 = True
     return model

@@ -14,8 +14,11 @@ is the arithmetic in plain torch).
 (``quantized_mu_scale`` / ``quantized_sigma_scale``), and the fp32 ``quantized_mu_bias`` / ``quantized_sigma_bias`` (the reference
 does not quantise the bias either). ROCm tensors have no quantised dtype: ``get_quantized_tensor`` returns ``(int8 tensor, scale)``.
 
-Deviations from the reference: the conv layer returns the DEQUANTISED fp32 output where the reference returns a quint8 tensor (the
-Linear layer dequantises there too); ``_last["out_q"]`` holds the u8 image when ``want_q`` is set. ``enable_int8_compute=False`` (the
+Deviations from the reference: BY DEFAULT the conv layer returns the DEQUANTISED fp32 output where the reference returns a quint8 tensor
+(the Linear layer dequantises there too); ``_last["out_q"]`` holds the u8 image when ``want_q`` is set. A caller opts into the
+reference's data path with a ``QActivation`` (quantization/qact.py): a layer handed one reads the u8 image as it
+is, with the CARRIER's (scale, zero point) in place of the ``in`` pair, and a conv layer then returns a ``QActivation`` at its ``out``
+pair (``return_quantized = True``: for an fp32 input as well -- the first layer of a u8 network); nothing fp32-sized is written. ``enable_int8_compute=False`` (the
 reference's deprecated dequantise-and-run-fp32 branch) raises NotImplementedError -- with the reference's precedence: a layer that has a
 ``quant_dict`` takes the calibrated int8 branch whatever ``enable_int8_compute`` says, there and here -- and so does ``prepare()`` of a
 quantised layer: calibration happens on the FLOAT layer (``quantization.prepare`` / ``convert``), and the
@@ -26,6 +29,7 @@ import torch
 
 from .. import _lib, rng
 from .. import functional as F
+from ..quantization.qact import QActivation
 from ._calibration import FLIPOUT, REPARAM, _sqrt, bn_coef      # noqa: F401 -- (_sqrt: the tests' own bn_coef reads it here)
 from ._fused import FusedBayesLayer
 from .base_variational_layer import BaseVariationalLayer_, get_kernel_size
@@ -61,6 +65,7 @@ class _QuantizedLayer(BaseVariationalLayer_):
         self._cache = None         # (key, s_mu, s_sigma, packs): the scales as Python floats and the [Co][taps][Ci16] packs
         self.inject_draw = None    # test hook: dict(eps_w [S, *wshape], eps_b [S, Co] or None) consumed instead of a fresh draw (or a list)
         self.want_q = False        # keep the u8 output image of every forward in _last["out_q"]
+        self.return_quantized = False      # a conv layer: return a QActivation for an fp32 input as well (the first layer of a u8 network)
 
     # ------------------------------------------------------------------ conversion
     def get_scale_and_zero_point(self, x, upper_bound=100, target_range=255):
@@ -159,7 +164,11 @@ class _QuantizedLayer(BaseVariationalLayer_):
         if not enable_int8_compute and self.quant_dict is None:
             raise NotImplementedError("enable_int8_compute=False (dequantise and run in fp32) is deprecated in the reference and not implemented here")
         ctx, _, _, return_kl = self._mc_frame(return_kl)
-        x = _lib.dev_f32(x, "input")
+        qin = x if isinstance(x, QActivation) else None      # a quint8 input: read as it is, with ITS pair (the reference's quint8 branch)
+        if qin is None:
+            x = _lib.dev_f32(x, "input")
+        elif not qin.is_cuda:
+            raise RuntimeError(f"input is on {qin.device}: the INT8 forward runs on a HIP (MI355X) device only; there is no CPU implementation of this path")
         conv = self._conv()
         lead = None
         if conv is None:
@@ -176,12 +185,26 @@ class _QuantizedLayer(BaseVariationalLayer_):
             raise RuntimeError("empty batch")
         s_mu, s_sigma, packs = self._frozen()
         pairs = self._pairs(s_mu, s_sigma, normal_scale, default_scale, default_zero_point)
+        i_in, i_out = self._schema.pairs.index("in"), self._schema.pairs.index("out")
+        if qin is not None:
+            pairs = list(pairs)
+            pairs[i_in] = qin.pair
         S, shared, coords = self._call_coords(ctx, x.shape[0])
         draw = self._supplied_draw(self._take_injected(), S, x, shared)
-        out, out_q = self._launch(x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw)
+        as_q = conv is not None and (qin is not None or self.return_quantized)      # (a Linear layer dequantises, as the reference's does)
+        if qin is None and not as_q:
+            out, out_q = self._launch(x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw)
+        else:
+            out, out_q = self._launch(x if qin is None else qin.data, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw,
+                                      x_shape=None if qin is None else tuple(x.shape), dest="u8" if as_q else "f32")
         B = x.shape[0] // (1 if shared else S)
+        tail = self._out_tail(x)
+        if as_q:
+            out = QActivation(out_q, pairs[i_out][0], pairs[i_out][1], (S * B,) + tail)
         self._last = dict(draw=draw, rng=coords, S=S, shared_x=shared, pairs=pairs, out_q=out_q, x_shape=(B,) + tuple(x.shape[1:]),
-                          out_shape=(B,) + tuple(out.shape[1:]), kernel=_lib.lib().bt_last_kernel_name().decode())
+                          out_shape=(B,) + tail, kernel=_lib.lib().bt_last_kernel_name().decode())
+        if as_q:
+            self._last["out"] = out      # the carrier this call returned
         if lead is not None:
             out = out.reshape(lead + (self._wshape[0],))
         return (out, 0) if return_kl else out
@@ -218,10 +241,10 @@ class _QuantizedLayer(BaseVariationalLayer_):
 
     _forward_fn = staticmethod(F.q8_forward)      # the functional forward of the estimator: what _launch calls
 
-    def _launch(self, x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw):
+    def _launch(self, x, packs, s_mu, s_sigma, pairs, conv, S, shared, coords, draw, **act):
         return self._forward_fn(x, packs, self._wshape, s_mu, s_sigma, pairs, self.quantized_mu_bias, self.quantized_sigma_bias, conv=conv, S=S, shared_x=shared,
                                 seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
-                                want_q=self.want_q, **(draw or {}))
+                                want_q=self.want_q, **act, **(draw or {}))
 
     def materialize_last_draw(self):
         """The draw the last forward used: ``eps_w`` [S, *weight shape], ``eps_b`` [S, Co] (None without a sampled bias) and the

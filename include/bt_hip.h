@@ -652,6 +652,59 @@ int bt_q8_flip_observe_linear(int32_t B, int32_t In, int32_t Out, int32_t S, con
 int bt_q8_flip_observe_x(int64_t n, int32_t S, const float *x, int64_t x_sample_stride, const float *sign_in, const bt_rng *rng,
                          float *in_mm, float *sign_in_mm, float *xp_mm, uint32_t *nonfinite, bt_stream_t stream);
 
+/* u8 activations between the INT8 layers. A quantised activation is a u8 image at one (scale, zero point)
+ * pair in the CHANNEL-BLOCKED layout [N][CB][H][W][16], CB = ceil(C / 16): byte j of the 16-byte unit (n, cb, h, w) is channel 16 * cb + j
+ * of pixel (h, w), and the bytes of channels >= C hold the zero point. [N][F] features are the same layout at H = W = 1 (rows padded to a
+ * multiple of 16). Every blocked image must be 16-byte aligned.
+ *
+ * The forwards: bt_q8_conv2d_fwd / bt_q8_linear_fwd / bt_q8_flip_* with an x source and two destinations. x_kind BT_Q8_X_F32: x is fp32
+ * [B][Ci][H][W], quantised at p->in where it is fetched, as there. BT_Q8_X_U8: x is the blocked image of [B][Ci][H][W] at the pair p->in
+ * (the CALLER's pair of that image: nothing is requantised), x_sample_stride counts its bytes. out: fp32 [S][B][Co][Ho][Wo] or NULL;
+ * out_blocked: the blocked image of [S * B][Co][Ho][Wo] at p->out, or NULL (then nothing u8 is written). The arithmetic, the draws and the
+ * sign streams (indexed by the element's offset in the LOGICAL [B][Ci][H][W] / [B][Co][Ho][Wo]) are those of the entry points above,
+ * bit for bit. BT_ERR_BAD_ARG before any launch, beside theirs: an x_kind that is neither, a null x, neither destination, a u8 x or an
+ * out_blocked that is not 16-byte aligned, a u8 sample stride that is no multiple of 16. */
+#define BT_Q8_X_F32 0
+#define BT_Q8_X_U8 1
+int bt_q8_conv2d_fwd_act(const bt_conv2d_geom *g, int32_t S, const void *x, int32_t x_kind, int64_t x_sample_stride, const bt_q8_params *p,
+                         const float *eps_w, const float *eps_b, const bt_rng *rng, float *out, uint8_t *out_blocked, bt_stream_t stream);
+int bt_q8_linear_fwd_act(int32_t B, int32_t In, int32_t Out, int32_t S, const void *x, int32_t x_kind, int64_t x_sample_stride,
+                         const bt_q8_params *p, const float *eps_w, const float *eps_b, const bt_rng *rng, float *out, uint8_t *out_blocked,
+                         bt_stream_t stream);
+int bt_q8_flip_conv2d_fwd_act(const bt_conv2d_geom *g, int32_t S, const void *x, int32_t x_kind, int64_t x_sample_stride,
+                              const bt_q8_flip_params *p, const float *eps_w, const float *eps_b, const float *sign_in,
+                              const float *sign_out, const bt_rng *rng, float *out, uint8_t *out_blocked, bt_stream_t stream);
+int bt_q8_flip_linear_fwd_act(int32_t B, int32_t In, int32_t Out, int32_t S, const void *x, int32_t x_kind, int64_t x_sample_stride,
+                              const bt_q8_flip_params *p, const float *eps_w, const float *eps_b, const float *sign_in,
+                              const float *sign_out, const bt_rng *rng, float *out, uint8_t *out_blocked, bt_stream_t stream);
+/* The element-wise operators on blocked images: each ONE launch, no allocation, no host synchronisation; torch's CPU quantised
+ * operators bit for bit (rne: round to nearest even; every operation one fp32 rounding but for the fma named). N, C, H, W: the logical
+ * shape. BT_ERR_BAD_ARG before any launch: a null pointer, N / C / H / W < 1, a blocked image that is not 16-byte aligned, a scale <= 0
+ * (or not finite), a zero point outside 0..255; BT_ERR_UNSUPPORTED: an image of 2^40 bytes or more.
+ *   bt_q8_act_quantize    q = clamp(rne(x * (1 / s)) + z, 0, 255) of fp32 x [N][C][H][W] (quantize_per_tensor).
+ *   bt_q8_act_dequantize  out fp32 [N][C][H][W] = float(q - z) * s.
+ *   bt_q8_act_relu        out = max(q, z); out may be q (in place).
+ *   bt_q8_act_add         quantized.add / add_relu of images a, b of ONE shape (the caller's shapes (N, C, H, W) of a and b are both
+ *                         given: a mismatch is BT_ERR_BAD_ARG): clamp(rne((fmaf(float(a), s_a, -(float(z_a) * s_a)) + fmaf(float(b), s_b,
+ *                         -(float(z_b) * s_b))) * (1 / s_o)) + z_o, 0, 255); relu != 0: the maximum of that and z_o.
+ *   bt_q8_act_max_pool2d  the maximum of the levels over a kh x kw window (stride, padding; padding positions are ignored): out is the
+ *                         blocked image of [N][C][Ho][Wo], Ho = (H + 2 ph - kh) / sh + 1. BT_ERR_BAD_ARG: kernel / stride < 1, padding < 0
+ *                         or > half the kernel, an empty output.
+ *   bt_q8_act_avg_pool    the global average pool to [N][C][1][1], at q's pair: clamp(rne(float(sum - z * n) * float(1 / n) + z), 0, 255),
+ *                         n = H * W. BT_ERR_UNSUPPORTED: n >= 2^23.
+ *   bt_q8_act_unblock     flatten: the blocked image of [N][C][H][W] -> the blocked image of [N][F], F = C * H * W in NCHW order (rows
+ *                         padded with z to a multiple of 16). */
+int bt_q8_act_quantize(const float *x, int64_t N, int64_t C, int64_t H, int64_t W, double scale, int32_t zero_point, uint8_t *q, bt_stream_t stream);
+int bt_q8_act_dequantize(const uint8_t *q, int64_t N, int64_t C, int64_t H, int64_t W, double scale, int32_t zero_point, float *out,
+                         bt_stream_t stream);
+int bt_q8_act_relu(const uint8_t *q, int64_t N, int64_t C, int64_t H, int64_t W, int32_t zero_point, uint8_t *out, bt_stream_t stream);
+int bt_q8_act_add(const uint8_t *a, const int64_t *a_shape, double s_a, int32_t z_a, const uint8_t *b, const int64_t *b_shape, double s_b,
+                  int32_t z_b, double s_out, int32_t z_out, int32_t relu, uint8_t *out, bt_stream_t stream);
+int bt_q8_act_max_pool2d(const uint8_t *q, int64_t N, int64_t C, int64_t H, int64_t W, int32_t kh, int32_t kw, int32_t sh, int32_t sw,
+                         int32_t ph, int32_t pw, uint8_t *out, bt_stream_t stream);
+int bt_q8_act_avg_pool(const uint8_t *q, int64_t N, int64_t C, int64_t H, int64_t W, int32_t zero_point, uint8_t *out, bt_stream_t stream);
+int bt_q8_act_unblock(const uint8_t *q, int64_t N, int64_t C, int64_t H, int64_t W, int32_t zero_point, uint8_t *out, bt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

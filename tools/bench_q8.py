@@ -30,7 +30,11 @@ N calls of ``mc_forward``, ``quantization.convert(fuse_conv_bn=True, flipout=Tru
 ``int8_flipout_calibrated`` beside the default-pair ``int8_flipout`` and ``float_flipout``; per layer the float Flipout layer's time, the
 prepared layer's (forward + the four observer launches) and their difference, the observers alone -- DESIGN.md 4.6i.
 
-    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10] [--calibrate N] [--flipout]
+``--u8``: a copy of every converted model gets ``harness.resnet.u8_inference`` -- quint8 carriers from the stem to the classifier
+(quantization/qact.py: the convs read and write the u8 channel-blocked image, ReLU / max-pool / add_relu run on it, fc dequantises) --
+and joins the alternation as ``<model>_u8``; per layer the u8 layer's time beside the fp32-between-layers int8 layer's -- DESIGN.md 4.6k.
+
+    python tools/bench_q8.py [--B 128] [--S 32] [--window 1.0] [--repeats 5] [--warmup 3] [--n 10] [--calibrate N] [--flipout] [--u8]
 """
 import argparse
 import copy
@@ -98,6 +102,7 @@ def main():
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--calibrate", type=int, default=0, metavar="N", help="also calibrate a copy on N batches and report it beside the default-branch model")
     ap.add_argument("--flipout", action="store_true", help="also run the Flipout ResNet18, float and converted to the INT8 Flipout layers")
+    ap.add_argument("--u8", action="store_true", help="also run every converted model with u8 activations between its layers (harness.resnet.u8_inference)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_q8 needs a GPU: a CPU run measures nothing")
@@ -163,6 +168,9 @@ def main():
                 if getattr(m, "quant_dict", None) is not None:
                     print(json.dumps(dict(what="quant_dict_flipout", layer=nm, pairs=[(round(d["scale"], 6), d["zero_point"]) for d in m.quant_dict])), flush=True)
             models["int8_flipout_calibrated"] = fcal
+    if args.u8:
+        for k in [k for k in models if k.startswith("int8")]:
+            models[k + "_u8"] = H.u8_inference(copy.deepcopy(models[k]))
     run = {k: (lambda m=m: mc.mc_forward(m, x, S, with_kl=False)) for k, m in models.items()}
     with torch.no_grad():
         for k in models:
@@ -190,6 +198,13 @@ def main():
             for (nm, kq, uq), (_, kf, uf), (_, _, ur) in zip(layer_times(fq, x, S, args.n), layer_times(fnet, x, S, args.n), layer_times(q, x, S, args.n)):
                 print(json.dumps(dict(what="layer_flipout", layer=nm, int8_flipout_us=uq, float_flipout_us=uf, int8_reparam_us=ur, int8_flipout_kernel=kq,
                                       float_flipout_kernel=kf)), flush=True)
+        for k in [k for k in rates if k.endswith("_u8")]:
+            base = k[:-3]
+            print(json.dumps(dict(what="ratio", **{f"{k}_over_{base}": round(statistics.median(rates[k]) / statistics.median(rates[base]), 3)},
+                                  base_spread=round(max(rates[base]) - min(rates[base])), median_difference=round(statistics.median(rates[k]) - statistics.median(rates[base])))),
+                  flush=True)
+            for (nm, ku, uu), (_, kq, uq) in zip(layer_times(models[k], x, S, args.n), layer_times(models[base], x, S, args.n)):
+                print(json.dumps(dict(what="layer_u8", model=k, layer=nm, u8_us=uu, fp32_between_us=uq, u8_kernel=ku, fp32_between_kernel=kq)), flush=True)
         tq, tf = layer_times(q, x, S, args.n), layer_times(net, x, S, args.n)
         for (nm, kq, uq), (nf, kf, uf) in zip(tq, tf):
             print(json.dumps(dict(what="layer", layer=nm, int8_us=uq, float_us=uf, int8_kernel=kq, float_kernel=kf)), flush=True)
