@@ -10,7 +10,15 @@ order from the sigma = softplus(rho) the kernels read (the packed tensor of pack
 two ulps): with a softplus that differs in the last bit, about one weight in 2^16 lands on the other side of a bf16 rounding boundary,
 and ONE such weight moves a whole output channel by a bf16 ulp of its products (~2^-8 |x w|, measured 1e-4 .. 2e-4 of max|ref| with
 the host's own softplus) -- past the tolerance, although the kernel is right. Against the UNROUNDED oracle the distance is bounded per
-element by 1.01 * 2^-8 * (|x| conv |W_s|) + atol, because (1 + 2^-9)^2 - 1 < 1.01 * 2^-8."""
+element by 1.01 * 2^-8 * (|x| conv |W_s|) + atol, because (1 + 2^-9)^2 - 1 < 1.01 * 2^-8.
+
+That last constant takes 2^-9 for the relative error of one rounding. It is the typical size, not the worst case: bf16 carries an 8-bit
+significand, so round-to-nearest is off by up to 2^-8 of the value and a product of two rounded operands by up to
+(1 + 2^-8)^2 - 1 < 1.01 * 2^-7. Over the K >= 24 products of the rows this file started with the errors average and the tighter constant
+holds; they keep it. The depthwise row (SHORT_K: nine products per output, one input channel) has no such averaging: a correct kernel,
+8.2e-8 of max|ref| from the oracle on rounded operands, exceeded the 2^-8 form at 10 of 12288 elements, by up to 8.0e-4 (MI355X). That
+row is held to the worst-case constant; the check on rounded operands, which is what catches a truncating or double-rounding kernel, is
+the same for every row."""
 import ctypes
 import zlib
 
@@ -35,6 +43,9 @@ GENERAL = {
     "28x28 -> 14x14 1x1 s2 (every second column, XM 4)": (64, 128, (1, 1), 2, 0, 1, 1, 28, 28, 8, 2, True),
     "28x28 -> 14x14 3x3 s2 (strided window: row quads)": (32, 64, (3, 3), 2, 1, 1, 1, 28, 28, 8, 2, False),
     "groups 2, 3x2 kernel, stride (2,1)": (32, 48, (3, 2), (2, 1), (1, 0), 1, 2, 16, 9, 8, 1, True),
+    # rows dw3 and cog70 of tests/_group_cases.py: grouped launches on the stem kernel (one live row of 64; a partial second channel tile)
+    "depthwise 12 groups 3x3 8x8 (stem kernel, Cig 1, Cog 1)": (12, 12, (3, 3), 1, 1, 1, 12, 8, 8, 8, 2, True),
+    "groups 2, 8->140 3x3 8x8 (stem kernel, Cig 4, Cog 70)": (8, 140, (3, 3), 1, 1, 1, 2, 8, 8, 8, 2, True),
 }
 # rows of DIRECT in test_gpu_round3.py (there: Ci, Co, groups, H, W, B, S, bias, extras[, stride]) in the layout above; EXTRAS below
 DIRECT = {
@@ -48,6 +59,7 @@ STEMS = {
     "CIFAR stem 3->64 k7 s2 p3 on 32x32, B = 10, S = 3, shared x, pool": (3, 64, (7, 7), 2, 3, 1, 1, 32, 32, 10, 3, False),
 }
 ROWS = {**GENERAL, **DIRECT, **STEMS}
+SHORT_K = {"depthwise 12 groups 3x3 8x8 (stem kernel, Cig 1, Cog 1)"}      # held to the worst-case rounding constant (module docstring)
 EXTRAS = {"K=256 -> 96 (partial channel tile), 7x7 (odd plane), b200, M % 64 != 0", "streamed W: K=1024 -> 96 (partial tile), 7x7, b180, ragged tiles",
           "CIFAR downsample 64 -> 128, 1x1 s2, 8x8 -> 4x4, b128 (few pixels: one sub-tile per wave)"}      # DIRECT's rows carry an output stage there
 FLIP_ROW = ("flip layer1 64x64 3x3 8x8 (row pieces, xm=3)", (64, 64, (3, 3), 1, 1, 1, 1, 8, 8, 128, 2, True))      # FLIP_GEOMS, test_gpu_split.py
@@ -171,9 +183,10 @@ def _check_against_oracles(name, c, out3, stage=None, scale_mag=None):
         assert_close(got, rounded, RTOL, ATOL, f"{name}[s={s}] bf16 mode vs the oracle on rounded operands")
         if scale_mag is not None:
             mag = scale_mag(mag)
-        bound = 1.01 * 2.0 ** -8 * mag + ATOL * float(exact.abs().max())
+        lg = -7 if name in SHORT_K else -8
+        bound = 1.01 * 2.0 ** lg * mag + ATOL * float(exact.abs().max())
         over = (got.double() - exact).abs() - bound
-        assert float(over.max()) <= 0.0, f"{name}[s={s}]: {int((over > 0).sum())} elements past 1.01 * 2^-8 * (|x| conv |W|) + atol, worst by {float(over.max()):.3e}"
+        assert float(over.max()) <= 0.0, f"{name}[s={s}]: {int((over > 0).sum())} elements past 1.01 * 2^{lg} * (|x| conv |W|) + atol, worst by {float(over.max()):.3e}"
 
 
 # ------------------------------------------------------------------------------------------------ 1. rounded-operand oracle
