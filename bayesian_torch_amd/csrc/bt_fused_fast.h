@@ -208,7 +208,8 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_fast_kernel(const FwdArg
   constexpr bool kReadoutAll = XMODE == 1;
   auto readout_quads = [&](int i, int t0) {
     constexpr int SROW = BM + 4, SROWS = 32 * CWN, QROW = BM / 4, NQ = SROWS * QROW, NT = kReadoutAll ? 256 + kProducers : 256;
-    constexpr int NITc = (NQ + NT - 1) / NT, U = NITc < 8 ? NITc : 8;
+    // (two-pass read-outs of the 12-wave kernels, 168 registers a lane: batches of 4, so that the batch's addresses and quads stay in registers)
+    constexpr int NITc = (NQ + NT - 1) / NT, UCAP = (NPW == 8 && TN > 1 && !kReadoutAll) ? 4 : 8, U = NITc < UCAP ? NITc : UCAP;
     const float* const stage = smem + 4 * BN;
     for (int c0q = t0; c0q < NQ; c0q += NT * U) {
       uint32_t oidx[U];

@@ -67,6 +67,12 @@ def test_table_covers_every_kernel_name_the_sweep_reaches(sweep, golden_rows):
     # every name of the split-precision library but the stems' sample walk (needs a device): 68 kernels, the two skinny ones under two names each
     assert len(split) == 70
     assert not any("walk" in n for n in split)
+    # the same statement from the library's own symbol table: the swept split names are the names its four split families' stubs run
+    # under, minus exactly the input-dilated (xm=5), depth-window (xm=6) and sample-walk instantiations (other entry points / a device)
+    from bayesian_torch_amd import _lib
+    fam, _ = rec.library_names(_lib.LIB_PATH)
+    have = set().union(*(names for f, names in fam.items() if f.startswith("fused_split_")))
+    assert split == {n for n in have if "xm=5" not in n and "xm=6" not in n and "walk" not in n}
     assert not any(",flip," in n and "xm=2" in n for n in split)      # Flipout's 128-wide whole-plane fetch is not instantiated
     per_name = {}
     for row in golden_rows:

@@ -167,6 +167,63 @@ def table(lines):
     return rows
 
 
+FAMILIES = ("fused_fwd_kernel", "fused_fast_kernel", "fused_split_kernel", "fused_split_quad_kernel", "fused_split_direct_kernel", "fused_split_skinny_kernel")
+
+
+def _terms(np_, flip):
+    """split_terms of bt_fused_split_launch.h."""
+    return "2x6" if flip else {3: "6", 2: "3", 1: "1"}[np_]
+
+
+def library_names(lib_path):
+    """family -> the set of names its instantiations run under, for the six forward-kernel families of the library: from the symbol
+    table's host stubs, through the name builders of bt_fused_split_launch.h (split_kernel_names and its neighbours) and the
+    snprintf calls of bt_fused_dispatch.h, bt_fused_lowrank.hip and bt_fused_flipout_obs.hip. A skinny stub runs under two names
+    (split-K 64 and 128: both are entries); a low-rank name is keyed without its run-time ``,R=``. -> (names, number of stubs)."""
+    import re
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    assert nm, "nm (binutils) or llvm-nm is needed to list the library's kernels"
+    out = subprocess.run([nm, "-C", lib_path], check=True, capture_output=True, text=True).stdout
+    names = {f: set() for f in FAMILIES}
+    word = {"true": 1, "false": 0}
+    stubs = set(re.findall(r"__device_stub__(fused_[a-z_]+_kernel)<([^>]*)>", out))
+    n_stubs = {f: 0 for f in FAMILIES}
+    for kind, targs in stubs:
+        if kind not in names:
+            continue
+        n_stubs[kind] += 1
+        t = [word[v] if v in word else int(v) for v in (s.strip() for s in targs.split(","))]
+        add = names[kind].add
+        if kind in ("fused_fwd_kernel", "fused_fast_kernel"):
+            # <BN, BM, CWN, FLIP, LINEAR, TRANS, INJ, then fwd: UPD, DWIN, LOWRANK, OBS; fast: XMODE, NPW, POOL>
+            form = "%s,%s" % ("linear" if t[4] else "conv", "trans" if t[5] else "notrans")
+            if kind == "fused_fast_kernel":
+                add("fused_fast_kernel<%d,%d,%d,%s,%s,inj=%d,xmode=%d,npw=%d,pool=%d>" % (t[0], t[1], t[2], "flip" if t[3] else "reparam", form, t[6], t[7], t[8], t[9]))
+            else:
+                upd, dwin, lowrank, obs = (t[7:] + [0, 0, 0, 0])[:4]
+                src = "lowrank" if lowrank else "flip" if t[3] else "reparam"
+                add("fused_fwd_kernel<%d,%d,%d,%s,%s,inj=%d%s>" % (t[0], t[1], t[2], src, form, t[6], ",obs" if obs else ",dwin" if dwin else ",updil" if upd else ""))
+        elif kind == "fused_split_kernel":      # <BN, BM, NP, NPW, XM, FLIP, INJ>
+            add("fused_split_kernel<%d,%d,bf16x%d,%s terms%s,npw=%d,xm=%d%s>" % (t[0], t[1], t[2], _terms(t[2], t[5]), ",flip" if t[5] else "", t[3], t[4], ",inj" if t[6] else ""))
+        elif kind == "fused_split_quad_kernel":      # <NP, POOL, FLIP, WALK, INJ>
+            add("fused_split_quad_kernel<64,%d,bf16x%d,%s terms%s,pool=%d%s%s>" % (256 if t[2] else 512, t[0], _terms(t[0], t[2]), ",flip" if t[2] else "", t[1],
+                                                                                    ",walk" if t[3] else "", ",inj" if t[4] else ""))
+        elif kind == "fused_split_direct_kernel":      # <RESIDENT, INJ, NP>
+            add("fused_split_direct_kernel<64,8x64,bf16x%d,%s terms,%s W%s>" % (t[2], _terms(t[2], 0), "resident" if t[0] else "streamed", ",inj" if t[1] else ""))
+        else:      # fused_split_skinny_kernel<INJ>: the launch's K slice is an argument, the name says which
+            for ks in (64, 128):
+                add("fused_split_skinny_kernel<64,4x32,bf16x3,6 terms,split-K %d%s>" % (ks, ",inj" if t[0] else ""))
+    return names, n_stubs
+
+
+def lowrank_key(name):
+    """A low-rank launch's name without its run-time rank: the key ``library_names`` lists it under."""
+    import re
+    return re.sub(r",R=\d+>$", ">", name)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dump", metavar="FILE", help="write the whole sweep's text")
