@@ -136,6 +136,13 @@ _PROTOS = {
     "bt_lowrank_mean": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.POINTER(bt_rng), _vp, _vp]),
     "bt_kl_lowrank_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
     "bt_kl_lowrank": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bt_lowrank_conv2d_bwd_workspace": (C.c_size_t, [C.POINTER(bt_conv2d_geom), C.c_int32, C.c_int32]),
+    "bt_lowrank_conv2d_bwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int32, C.c_float, _vp, C.POINTER(bt_rng), _vp,
+                                        _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bt_lowrank_conv2d_bwd_info": (C.c_int, [C.POINTER(C.c_int64), C.c_int32]),
+    "bt_lowrank_wgrad_finish": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.POINTER(bt_rng), _vp, _vp, _vp]),
+    "bt_kl_lowrank_bwd_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "bt_kl_lowrank_bwd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bt_lstm_cell_fwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
     "bt_lstm_cell_bwd": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp]),
     "bt_avu_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
@@ -203,6 +210,16 @@ def last_launch_info():
     v = (C.c_int64 * 16)()
     check(lib().bt_last_launch_info(v, 16))
     return dict(zip(LAUNCH_INFO_FIELDS, (int(x) for x in v)))
+
+
+LOWRANK_BWD_INFO_FIELDS = ("dgrad_launches", "wgrad_launches", "dgrad_pieces", "wgrad_chunks", "dgrid_x", "dgrid_y", "dgrid_z", "wgrid_x", "wgrid_y", "wgrid_z")
+
+
+def lowrank_bwd_info():
+    """What the calling thread's last bt_lowrank_conv2d_bwd planned (bt_lowrank_conv2d_bwd_info) as a dict."""
+    v = (C.c_int64 * 10)()
+    check(lib().bt_lowrank_conv2d_bwd_info(v, 10))
+    return dict(zip(LOWRANK_BWD_INFO_FIELDS, (int(x) for x in v)))
 
 
 ERR_UNSUPPORTED = -2  # BT_ERR_UNSUPPORTED

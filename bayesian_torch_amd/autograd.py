@@ -237,6 +237,89 @@ class KLNormal(torch.autograd.Function):
         return tuple(grads)
 
 
+_LOWRANK_COORDS = ("seed", "call", "layer_id", "sample0", "call_base")
+
+
+class LowRankForward(torch.autograd.Function):
+    """out[S*B, ...] of the low-rank multivariate Conv2d layer on the fused inference launch (bt_lowrank_conv2d_fwd; behind the
+    bt_lowrank_mean pre-pass for a rank above the in-kernel bound); differentiable in x, mu and L on the HIP backward of
+    csrc/bt_lowrank_bwd.hip: the data gradient regenerates the sampled weights from the forward's coordinates (or reads the supplied
+    draws), the weight gradient stays per sample and one finishing launch applies the chain rule to (mu, L). Nothing weight-sized is
+    saved; a rank above the bound recomputes its pre-pass in the backward (the layer's forward workspace may have been rewritten by
+    then). Nothing synchronises with the host.
+    opts: d, wshape, conv, S, shared_x, path ("in_kernel" | "mean_prepass"), z / eps_w (supplied draws or None), the call's
+    coordinates (seed, call, layer_id, sample0, call_base), mean_out (the pre-pass's destination in the forward, or None), record (a
+    dict that receives the backward's launch record, or None)."""
+
+    @staticmethod
+    def forward(ctx, x, mu, L, opts):
+        o = dict(opts)
+        co = {k: o.get(k) for k in _LOWRANK_COORDS}
+        kw = dict(S=o["S"], shared_x=o["shared_x"], **co)
+        if o["path"] == "in_kernel":
+            out = F.lowrank_conv2d(x, mu.detach(), L.detach(), o["d"], o["wshape"], o["conv"], z=o.get("z"), eps_w=o.get("eps_w"), **kw)
+        else:
+            m = F.lowrank_mean(mu.detach(), L.detach(), o["S"], o.get("z"), out=o.get("mean_out"), **co)
+            out = F.lowrank_conv2d(x, m, None, o["d"], o["wshape"], o["conv"], eps_w=o.get("eps_w"), **kw)
+        o.pop("mean_out", None)
+        ctx.o = o
+        ctx.save_for_backward(x, mu, L)
+        ctx.out_shape = tuple(out.shape)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, mu, L = ctx.saved_tensors
+        o = ctx.o
+        need_x, need_mu, need_L = ctx.needs_input_grad[:3]
+        if g is None or not (need_x or need_mu or need_L):
+            return None, None, None, None
+        co = {k: o.get(k) for k in _LOWRANK_COORDS}
+        S, z, eps = o["S"], o.get("z"), o.get("eps_w")
+        mu_d, L_d = mu.detach(), L.detach()
+        if o["path"] == "in_kernel":
+            mean, Lk, zk = mu_d, L_d, z
+        else:      # the pre-pass again, from the saved coordinates, into a buffer of the backward's own (the data gradient alone reads it)
+            mean = F.lowrank_mean(mu_d, L_d, S, z, **co) if need_x else mu_d
+            Lk, zk = None, None
+        dx, dw, info = F.lowrank_backward(x.detach(), g, mean, Lk, o["d"], o["wshape"], o["conv"], S=S, shared_x=o["shared_x"], need_x=need_x,
+                                          need_w=need_mu or need_L, z=zk, eps_w=eps, **co)
+        dmu = dL = None
+        if dw is not None:
+            dmu, dL = F.lowrank_wgrad_finish(dw, L.shape[1], z, need_mu=need_mu, need_L=need_L, **co)
+            dmu = None if dmu is None else dmu.view(mu.shape)
+        if o.get("record") is not None:
+            o["record"].update(info, finish_launches=0 if dw is None else 1)
+        return dx, dmu, dL, None
+
+
+class KLLowRank(torch.autograd.Function):
+    """(KL, KL / n) of N(mu, L L^T + d I) against N(prior_mean, diag(prior_var)) on bt_kl_lowrank; gradients to mu and L from
+    bt_kl_lowrank_bwd (fp64, the factor kept). opts: d, prior_mean, prior_var, owner, bad_pivots. Nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, mu, L, opts):
+        o = dict(opts)
+        out = F.kl_lowrank(mu.detach(), L.detach(), o["d"], o["prior_mean"], o["prior_var"], owner=o.get("owner", "kl_lowrank"), bad_pivots=o.get("bad_pivots"))
+        ctx.o = o
+        ctx.save_for_backward(mu, L)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_kl, g_mean):
+        mu, L = ctx.saved_tensors
+        o = ctx.o
+        need_mu, need_L = ctx.needs_input_grad[:2]
+        if (g_kl is None and g_mean is None) or not (need_mu or need_L):
+            return None, None, None
+        c = g_kl if g_mean is None else (g_mean / L.shape[0] if g_kl is None else g_kl + g_mean / L.shape[0])
+        dmu, dL = F.kl_lowrank_backward(mu.detach(), L.detach(), o["d"], o["prior_mean"], o["prior_var"], c, need_mu=need_mu, need_L=need_L,
+                                        bad_pivots=o.get("bad_pivots"))
+        return (None if dmu is None else dmu.view(mu.shape)), dL, None
+
+
 class KLHier(torch.autograd.Function):
     """kl = sum over the given (mu, rho, prior_mu, log_a, log_b, a0, b0) groups of SUM_i(A_i + B_i), the hierarchical layers' kl_loss()
     (reference hiearchial_variational_layers.py:331-381), on bt_kl_hier: one launch forward, one launch backward (bt_kl_hier_bwd) for

@@ -154,11 +154,14 @@ __global__ __launch_bounds__(256) void kl_lowrank_sweep_kernel(const float* __re
 // logdet = sum log pivot, and the closed form
 //   KL = 1/2 [ sum log P - n log d - logdet + sum (d + sum_j L_ij^2) / P + sum (mu - m)^2 / P - n ]   -> kl[0], kl[1] = KL / n.
 // A pivot that is not positive: NaN in both, and one more in *bad (when given).
+// KEEP (bt_kl_lowrank_bwd): the factor C (A = C C^T) is left in A's lower triangle, kl may be null, and *status says whether every
+// pivot was positive (1.0) or not (NaN).
 constexpr int kFinThreads = 1024;
 constexpr int kFinPanelDoubles = 8192;   // LDS doubles of one panel (64 KiB): nb = min(16, 8192 / r) columns, >= 1 up to the rank limit
 static_assert(kFinPanelDoubles >= kKlLrMaxRank, "a panel holds at least one column");
+template <bool KEEP>
 __global__ __launch_bounds__(kFinThreads) void kl_lowrank_finish_kernel(const double* __restrict__ part, int C, long long stride, long long n, int r, int NB, double d,
-                                                                        double* A, float* kl, int* bad) {
+                                                                        double* A, float* kl, int* bad, double* status) {
   extern __shared__ double pan[];   // [NB][r]: column p of the panel at pan + p * r (rows below the panel's first are used)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long rr = (long long)r * r;
@@ -202,6 +205,12 @@ __global__ __launch_bounds__(kFinThreads) void kl_lowrank_finish_kernel(const do
       for (int i = k + 1 + tid; i < r; i += kFinThreads) cp[i] *= inv;
       __syncthreads();
     }
+    if constexpr (KEEP) {   // the panel's columns of the factor, diagonal included (the trailing update below touches later columns only)
+      for (int e = tid; e < (r - k0) * nb; e += kFinThreads) {
+        const int i = k0 + e / nb, p = e - (e / nb) * nb;
+        if (i >= k0 + p) A[(long long)i * r + k0 + p] = i == k0 + p ? sqrt(pan[(long long)p * r + i]) : pan[(long long)p * r + i];
+      }
+    }
     const int t0 = k0 + nb;   // trailing matrix: rows and columns from t0
     // (a wave takes four rows at a time: one LDS read of the panel's column entry serves four multiply-adds, and the rows' own
     // entries are wave-uniform reads -- the update is LDS-bound: one row at a time ran the r = 432 call in 1577 us)
@@ -229,9 +238,32 @@ __global__ __launch_bounds__(kFinThreads) void kl_lowrank_finish_kernel(const do
       v = (double)NAN;
       if (bad) *bad += 1;
     }
-    kl[0] = (float)v;
-    kl[1] = (float)(v / (double)n);
+    if (kl) {
+      kl[0] = (float)v;
+      kl[1] = (float)(v / (double)n);
+    }
+    if constexpr (KEEP) *status = neg ? (double)NAN : 1.0;
   }
+}
+
+// The sweep and the factorisation: bt_kl_lowrank's two launches (keep = false), and the first two of bt_kl_lowrank_bwd's.
+int kl_lowrank_factor(const char* who_sweep, const char* who_finish, const float* mu, const float* L, long long n, int r, float d, const float* prior_mean,
+                      const float* prior_var, float* kl_out, int32_t* bad_pivots, double* part, double* A, bool keep, double* status, hipStream_t stream) {
+  const KlLrPlan p = kl_lowrank_plan(n, r);
+  const dim3 grid((unsigned)(p.nt * p.nt + 1), (unsigned)p.C);
+  if (int rc = launch_kernel(p.T == 16 ? kl_lowrank_sweep_kernel<16> : kl_lowrank_sweep_kernel<4>, nullptr, who_sweep, grid, dim3(256), 0, 0, stream, mu, L, prior_mean,
+                             prior_var, n, r, (double)d, p.nt, p.chunk, p.stride, part))
+    return rc;
+  int NB = kFinPanelDoubles / r;
+  NB = NB > 16 ? 16 : NB;
+  const int lds = NB * r * (int)sizeof(double);   // <= 64 KiB
+  return launch_kernel(keep ? kl_lowrank_finish_kernel<true> : kl_lowrank_finish_kernel<false>, nullptr, who_finish, dim3(1), dim3(kFinThreads), lds,
+                       kFinPanelDoubles * (int)sizeof(double), stream, part, p.C, p.stride, n, r, NB, (double)d, A, kl_out, bad_pivots, status);
+}
+
+long long kl_lowrank_partials(long long n, int r) {   // doubles of the sweep's partials (A begins behind them)
+  const KlLrPlan p = kl_lowrank_plan(n, r);
+  return (long long)p.C * p.stride;
 }
 
 }  // namespace bt
@@ -260,16 +292,7 @@ extern "C" int bt_kl_lowrank(const float* mu, const float* L, int64_t n, int32_t
   if (r > kKlLrMaxRank || (long long)n * r >= (1ll << 40)) return set_error(BT_ERR_UNSUPPORTED, "bt_kl_lowrank: rank above 4096 or L too large");
   if (!workspace || (((uintptr_t)workspace) & 7u) || workspace_bytes < bt_kl_lowrank_workspace(n, r))
     return set_error(BT_ERR_WORKSPACE, "bt_kl_lowrank: workspace smaller than bt_kl_lowrank_workspace(n, r), or not 8-byte aligned");
-  const KlLrPlan p = kl_lowrank_plan(n, r);
   double* const part = reinterpret_cast<double*>(workspace);
-  double* const A = part + (long long)p.C * p.stride;
-  const dim3 grid((unsigned)(p.nt * p.nt + 1), (unsigned)p.C);
-  if (int rc = launch_kernel(p.T == 16 ? kl_lowrank_sweep_kernel<16> : kl_lowrank_sweep_kernel<4>, nullptr, "bt_kl_lowrank (sweep)", grid, dim3(256), 0, 0,
-                             (hipStream_t)stream, mu, L, prior_mean, prior_var, (long long)n, (int)r, (double)d, p.nt, p.chunk, p.stride, part))
-    return rc;
-  int NB = kFinPanelDoubles / r;
-  NB = NB > 16 ? 16 : NB;
-  const int lds = NB * r * (int)sizeof(double);   // <= 64 KiB
-  return launch_kernel(kl_lowrank_finish_kernel, nullptr, "bt_kl_lowrank (finish)", dim3(1), dim3(kFinThreads), lds, kFinPanelDoubles * (int)sizeof(double),
-                       (hipStream_t)stream, part, p.C, p.stride, (long long)n, (int)r, NB, (double)d, A, kl_out, bad_pivots);
+  return kl_lowrank_factor("bt_kl_lowrank (sweep)", "bt_kl_lowrank (finish)", mu, L, (long long)n, (int)r, d, prior_mean, prior_var, kl_out, bad_pivots, part,
+                           part + kl_lowrank_partials(n, r), false, nullptr, (hipStream_t)stream);
 }

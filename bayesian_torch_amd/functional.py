@@ -351,6 +351,89 @@ def kl_lowrank(mu, L, d, prior_mean, prior_var, owner="kl_lowrank", bad_pivots=N
     return out
 
 
+def lowrank_backward(x, grad_out, mean, L, d, wshape, conv, *, S=1, shared_x=True, need_x=True, need_w=True, z=None, eps_w=None, seed=0, call=0, layer_id=0,
+                     sample0=0, call_base=None):
+    """Gradients of ``lowrank_conv2d`` on the HIP backward kernels (bt_lowrank_conv2d_bwd): the data gradient regenerates
+    w_s = mean_s + L @ z_s + sqrt(d) * eps_s per LDS stage from the forward's RNG coordinates (or reads the supplied draws); the weight
+    gradient is kept per sample. The arguments are ``lowrank_conv2d``'s (mean [n] or [S, n], L [n, R] with R <= _lib.LOWRANK_MAX_R or
+    None), x / grad_out as the forward saw / produced them. -> (dx like x or None -- summed over the samples for a shared x --,
+    dW [S, n] or None: feed it to ``lowrank_wgrad_finish``, launch record of the call as a dict)."""
+    x, g = _lib.dev_f32(x, "input"), _lib.dev_f32(grad_out, "grad_out")
+    mean, L = _lib.dev_f32(mean, "mean"), _lib.dev_f32(L, "L")
+    z, eps_w = _lib.dev_f32(z, "z"), _lib.dev_f32(eps_w, "eps_w")
+    dev = x.device
+    wshape = tuple(int(v) for v in wshape)
+    n = math.prod(wshape)
+    R = 0 if L is None else L.shape[1]
+    if mean.numel() not in (n, S * n) or (L is not None and L.shape[0] != n):
+        raise RuntimeError(f"lowrank_backward: mean [{mean.numel()}] / L do not fit a kernel of {n} weights and S={S}")
+    if (eps_w is not None and R > 0 and z is None) or (eps_w is None and z is not None):
+        raise RuntimeError("lowrank_backward: supply both draws (z, eps_w) or neither")
+    if eps_w is not None and (eps_w.numel() != S * n or (R > 0 and tuple(z.shape) != (S, R))):
+        raise RuntimeError(f"lowrank_backward: the supplied draws do not hold S={S} samples")
+    B, geom, x_elems, tail = _geometry(x, _Shape(wshape), conv, S, shared_x)
+    if g.numel() != S * B * math.prod(tail):
+        raise RuntimeError(f"lowrank_backward: grad_out {tuple(g.shape)} is not the forward's output [{S * B}, {tail}]")
+    lib = _lib.lib()
+    dx = torch.empty((S, B) + tuple(x.shape[1:]), dtype=torch.float32, device=dev) if need_x else None
+    dw = torch.empty((S, n), dtype=torch.float32, device=dev) if need_w else None
+    # partials of wgrad's reduction chunks and of dgrad's output-channel pieces (contents need not be initialised)
+    ws = torch.empty(max(16, lib.bt_lowrank_conv2d_bwd_workspace(C.byref(geom), S, R)), dtype=torch.uint8, device=dev)
+    Rg = _rng(seed, call, layer_id, sample0, call_base)
+    sd = C.c_float(math.sqrt(C.c_float(float(d)).value)).value      # the forward's sqrtf(d): a double root of a float rounds to the float root
+    with _lib.on(dev):
+        _lib.check(lib.bt_lowrank_conv2d_bwd(C.byref(geom), S, x.data_ptr(), 0 if shared_x else x_elems, g.data_ptr(), mean.data_ptr(),
+                                             n if mean.numel() == S * n and S > 1 else 0, _lib.ptr(L), R, sd, _lib.ptr(z) if R > 0 else None, C.byref(Rg), _lib.ptr(eps_w),
+                                             _lib.ptr(dx), _lib.ptr(dw), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+    info = _lib.lowrank_bwd_info()
+    if need_x:
+        dx = dx.sum(0) if shared_x else dx.reshape(x.shape)
+    return dx, dw, info
+
+
+def lowrank_wgrad_finish(dw, r, z=None, *, need_mu=True, need_L=True, seed=0, call=0, layer_id=0, sample0=0, call_base=None):
+    """The chain rule over the per-sample weight gradients dw [S, n] of ``lowrank_backward`` (bt_lowrank_wgrad_finish):
+    dmu[i] = sum_s dw[s, i], dL[i, j] = sum_s dw[s, i] * z_s[j], s ascending, for any rank r. z: [S, r], or None for the on-chip stream
+    (tensor 4 of the call's coordinates). -> (dmu [n] or None, dL [n, r] or None)."""
+    dw, z = _lib.dev_f32(dw, "dw"), _lib.dev_f32(z, "z")
+    S, n = dw.shape
+    if z is not None and tuple(z.shape) != (S, r):
+        raise RuntimeError(f"lowrank_wgrad_finish: z {tuple(z.shape)} does not hold S={S} samples of rank {r}")
+    dmu = torch.empty((n,), dtype=torch.float32, device=dw.device) if need_mu else None
+    dL = torch.empty((n, r), dtype=torch.float32, device=dw.device) if need_L else None
+    if dmu is None and dL is None:
+        return None, None
+    Rg = _rng(seed, call, layer_id, sample0, call_base)
+    with _lib.on(dw.device):
+        _lib.check(_lib.lib().bt_lowrank_wgrad_finish(dw.data_ptr(), n, int(r), S, _lib.ptr(z), C.byref(Rg), _lib.ptr(dmu), _lib.ptr(dL), _lib.stream_ptr(dw.device)))
+    return dmu, dL
+
+
+def kl_lowrank_backward(mu, L, d, prior_mean, prior_var, grad_kl, *, need_mu=True, need_L=True, bad_pivots=None):
+    """Gradient of ``kl_lowrank``'s un-normalised KL times ``grad_kl`` (a device scalar) on the HIP kernels (bt_kl_lowrank_bwd: fp64, the
+    forward's sweep, its Cholesky factor kept, an explicit r x r inverse; five launches, nothing synchronised)
+    -> (dmu like mu or None, dL like L or None), fp32."""
+    mu, L = _lib.dev_f32(mu, "mu"), _lib.dev_f32(L, "L")
+    pm, pv = _lib.dev_f32(prior_mean, "prior_mean"), _lib.dev_f32(prior_var, "prior_var")
+    g = _lib.dev_f32(grad_kl.reshape(1).contiguous(), "grad_kl")
+    n, r = L.shape
+    if mu.numel() != n or pm.numel() != n or pv.numel() != n:
+        raise RuntimeError("kl_lowrank_backward: mu, prior_mean and prior_var must have L's row count")
+    if not (need_mu or need_L):
+        return None, None
+    lib = _lib.lib()
+    need = int(lib.bt_kl_lowrank_bwd_workspace(n, r))
+    if need == 0:
+        raise NotImplementedError(f"kl_lowrank_backward: rank {r} is above the factorisation kernel's limit")
+    ws = torch.empty(need, dtype=torch.uint8, device=mu.device)
+    dmu = torch.empty_like(mu) if need_mu else None
+    dL = torch.empty_like(L) if need_L else None
+    with _lib.on(mu.device):
+        _lib.check(lib.bt_kl_lowrank_bwd(mu.data_ptr(), L.data_ptr(), n, r, float(d), pm.data_ptr(), pv.data_ptr(), g.data_ptr(), _lib.ptr(dmu), _lib.ptr(dL),
+                                         _lib.ptr(bad_pivots), ws.data_ptr(), ws.numel(), _lib.stream_ptr(mu.device)))
+    return dmu, dL
+
+
 def pack_params(mu_w, rho_w):
     """Tap-major re-layout of a layer's (mu, softplus(rho)) -> (mu_packed, sigma_packed), each [Co, taps, Ci4]
     (include/bt_hip.h, bt_params). A cache of a pure function of the parameters; rebuild when they change."""

@@ -11,8 +11,15 @@ Three paths (``choose_path``; ``layer._last["path"]``):
                     weight-sized is written.
 ``"mean_prepass"``  rank > 4: bt_lowrank_mean writes m_s = mu + L z_s ([S, n] floats, into the layer's workspace) and the same forward
                     kernel runs with rank 0 on it.
-``"materialised"``  a call that needs gradients, or a ``D_param`` that is not one constant: plain torch ops on the device,
-                    w = mu + z @ L^T + sqrt(D) * eps and F.conv2d per sample, with the draws the kernels would have made.
+``"materialised"``  a call that needs gradients (unless ``set_lowrank_train_path("fused")``), or a ``D_param`` that is not one constant:
+                    plain torch ops on the device, w = mu + z @ L^T + sqrt(D) * eps and F.conv2d per sample, with the draws the kernels
+                    would have made.
+
+Training (``set_lowrank_train_path``, environment default ``BT_LOWRANK_TRAIN_PATH``): under ``"materialised"`` (the default) a call that
+needs gradients takes the torch composition and autograd differentiates it. Under ``"fused"`` it keeps its inference path and the HIP
+backward of csrc/bt_lowrank_bwd.hip differentiates it (autograd.LowRankForward: the data gradient regenerates the sampled weights on
+chip, the weight gradient stays per sample, one finishing launch gives dmu and dL); the KL of a diagonal prior is autograd.KLLowRank
+(bt_kl_lowrank / bt_kl_lowrank_bwd). ``layer._last["backward"]`` says which: ``"fused"`` or ``"autograd"`` (None: no gradients asked for).
 
 The KL of a diagonal prior comes from bt_kl_lowrank (an fp64 sweep and an r x r fp64 Cholesky; once per forward, whatever S); a prior
 with a non-zero ``prior_cov_L``, or a call that needs gradients, takes it from torch ops in fp64 (``closed_form_kl``, or
@@ -22,11 +29,13 @@ Deviations from the reference, all documented in DESIGN.md section 4.6d: ``kl_lo
 AttributeError), ``groups != 1`` and a tuple ``kernel_size`` are refused at construction (the reference fails in ``view``), and
 ``martern_prior = True`` raises NotImplementedError (the reference's branch fails its own assert).
 """
+import os
+
 import torch
 import torch.nn.functional as TF
 from torch.nn import Parameter
 
-from .. import _lib, mc, rng
+from .. import _lib, autograd, mc, rng
 from .. import functional as F
 from ._fused import FusedBayesLayer
 from .base_variational_layer import BaseVariationalLayer_
@@ -35,9 +44,34 @@ MAX_R = _lib.LOWRANK_MAX_R
 D_INIT = 1e-10
 
 
-def choose_path(rank, d_uniform, prior_diagonal, needs_grad):
-    """-> (forward path, KL path, reason for leaving the kernels or None). A pure function of what the layer knows before it launches."""
-    if needs_grad:
+TRAIN_PATHS = ("fused", "materialised")
+
+
+def _check_train_path(name, what):
+    if name not in TRAIN_PATHS:
+        raise ValueError(f"{what}: expected one of {TRAIN_PATHS}, got {name!r}")
+    return name
+
+
+_train_path = [_check_train_path(os.environ.get("BT_LOWRANK_TRAIN_PATH", "materialised"), "BT_LOWRANK_TRAIN_PATH")]
+
+
+def set_lowrank_train_path(name):
+    """How a call of the low-rank multivariate layer that needs gradients runs: "materialised" (default) the torch composition under
+    autograd, "fused" the inference launches with the HIP backward (module docstring). Process-wide; also the environment variable
+    BT_LOWRANK_TRAIN_PATH, read at import. Returns the previous setting."""
+    prev, _train_path[0] = _train_path[0], _check_train_path(name, "set_lowrank_train_path")
+    return prev
+
+
+def get_lowrank_train_path():
+    return _train_path[0]
+
+
+def choose_path(rank, d_uniform, prior_diagonal, needs_grad, train_path="materialised"):
+    """-> (forward path, KL path, reason for leaving the kernels or None). A pure function of what the layer knows before it launches.
+    train_path "fused": a call that needs gradients keeps the kernels' paths (a non-diagonal prior keeps the differentiable torch KL)."""
+    if needs_grad and train_path != "fused":
         return "materialised", "materialised", "the call needs gradients"
     if not d_uniform:
         return "materialised", "materialised", "D_param is not one constant"
@@ -192,6 +226,9 @@ class LowRankConv2dLayer(BaseVariationalLayer_):
         if path == "kernel":
             if self._bad_pivots is None or self._bad_pivots.device != mu.device:
                 self._bad_pivots = torch.zeros(1, dtype=torch.int32, device=mu.device)
+            if needs_grad:      # the fused training path: the kernels' KL, differentiated by bt_kl_lowrank_bwd
+                return autograd.KLLowRank.apply(mu, L, dict(d=d, prior_mean=self.prior_mean, prior_var=self.prior_cov_D, owner=("layer", self._ws_id),
+                                                            bad_pivots=self._bad_pivots))
             out = F.kl_lowrank(mu.detach(), L.detach(), d, self.prior_mean, self.prior_cov_D, owner=("layer", self._ws_id), bad_pivots=self._bad_pivots)
             return out[0], out[1]
         if not needs_grad:
@@ -218,7 +255,7 @@ class LowRankConv2dLayer(BaseVariationalLayer_):
         mu = _lib.dev_f32(self.mu_kernel, "mu_kernel")
         needs_grad = self._needs_grad()
         d_uniform, _, prior_diag, _ = self._look(mu.device)
-        _, kl_path, _ = choose_path(self.rank, d_uniform, prior_diag, needs_grad)
+        _, kl_path, _ = choose_path(self.rank, d_uniform, prior_diag, needs_grad, train_path=get_lowrank_train_path())
         return self._kl(kl_path, needs_grad)[0]
 
     # ------------------------------------------------------------------ forward
@@ -268,7 +305,7 @@ class LowRankConv2dLayer(BaseVariationalLayer_):
         B = x.shape[0] // (1 if shared else S)
         needs_grad = self._needs_grad(x)
         d_uniform, d, prior_diag, Dd = self._look(dev)
-        path, kl_path, reason = choose_path(self.rank, d_uniform, prior_diag, needs_grad)
+        path, kl_path, reason = choose_path(self.rank, d_uniform, prior_diag, needs_grad, train_path=get_lowrank_train_path())
         if self.force_path == "materialised" and path != "materialised":
             path, kl_path, reason = "materialised", "materialised", "forced"
         z, eps = self._draws(S, coords, dev, self._take_injected(), path != "materialised")
@@ -282,6 +319,11 @@ class LowRankConv2dLayer(BaseVariationalLayer_):
                 outs = [TF.conv2d(xs[0 if shared else s], w[s].view(self._wshape()), None, conv["stride"], conv["padding"], conv["dilation"], 1) for s in range(S)]
                 out = outs[0] if S == 1 else torch.cat(outs, 0)
             kernel, launch = "torch: mu + z @ L^T + sqrt(D) * eps, conv2d", None
+        elif needs_grad:      # the fused training path: the same launches, differentiated by the HIP backward
+            bwd_rec = {}
+            out = autograd.LowRankForward.apply(x, mu, L, dict(kw, d=d, wshape=self._wshape(), conv=conv, path=path, z=z, eps_w=eps, record=bwd_rec,
+                                                               mean_out=self._mean_workspace(S, dev) if path == "mean_prepass" else None))
+            kernel, launch = _lib.lib().bt_last_kernel_name().decode(), _lib.last_launch_info()
         else:
             if path == "in_kernel":
                 out = F.lowrank_conv2d(x, mu.detach(), L.detach(), d, self._wshape(), conv, z=z, eps_w=eps, **kw)
@@ -291,8 +333,10 @@ class LowRankConv2dLayer(BaseVariationalLayer_):
                 out = F.lowrank_conv2d(x, m, None, d, self._wshape(), conv, eps_w=eps, **kw)
             kernel, launch = _lib.lib().bt_last_kernel_name().decode(), _lib.last_launch_info()
         kl = self._kl(kl_path, needs_grad)[1] if want_kl else None      # once per forward, whatever S: the value does not depend on the sample
+        fused_bwd = needs_grad and path != "materialised"
         self._last = dict(draw=None if z is None else dict(z=z, eps_w=eps), rng=coords, S=S, kernel=kernel, launch=launch, shared_x=shared, path=path,
-                          kl_path=kl_path if want_kl else None, reason=reason, x_shape=(B,) + tuple(x.shape[1:]), out_shape=(B,) + tuple(out.shape[1:]))
+                          kl_path=kl_path if want_kl else None, reason=reason, x_shape=(B,) + tuple(x.shape[1:]), out_shape=(B,) + tuple(out.shape[1:]),
+                          backward=("fused" if fused_bwd else "autograd") if needs_grad else None, backward_launch=bwd_rec if fused_bwd else None)
         if collect:
             ctx.kls.append(kl)
         return (out, kl) if return_kl else out

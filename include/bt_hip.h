@@ -442,6 +442,44 @@ size_t bt_kl_lowrank_workspace(int64_t n, int32_t r);
 int bt_kl_lowrank(const float *mu, const float *L, int64_t n, int32_t r, float d, const float *prior_mean, const float *prior_var,
                   float *kl_out, int32_t *bad_pivots, void *workspace, size_t workspace_bytes, bt_stream_t stream);
 
+/* Training backward of bt_lowrank_conv2d_fwd (the reference differentiates conv_variational.py:516-552 with torch autograd). Two
+ * implicit GEMMs on fp32 MFMA, 64 x 64 tiles, with bt_conv2d_bwd's split of the two reductions (summed in a fixed order, no atomics:
+ * the same coordinates give the same bits):
+ *   dx   [S][B][Ci][H][W] or NULL: dX_s = conv_transpose(g_s, W_s), W_s regenerated per LDS stage as the forward forms it,
+ *        w_s[i] = mean_s[i] + sum_{q < R} L[i][q] * z_s[q] + sd * eps_s[i]   (q ascending, one rounding per operation; sd = sqrtf(d)),
+ *        mean and L read in the weights' natural order [Co][Ci][kh][kw] -- nothing weight-sized per sample is written;
+ *   dW   [S][n] or NULL: D_s[co][ci][tap] = sum_{b,ho,wo} g_s * x_s window, per sample, the weights' natural order (it needs no draws).
+ * mean_s = mean + s * mean_sample_stride (0, or n for the [S][n] output of a bt_lowrank_mean pre-pass recomputed by the caller: a rank
+ * above BT_LOWRANK_MAX_R runs with L = NULL, R = 0). Draws: z [S][R] and eps_w [S][n] are read when eps_w is given (z too when R > 0),
+ * else both come from rng (tensors 4 and 0, the forward's streams). workspace: bt_lowrank_conv2d_bwd_workspace(g, S, r) bytes (r: the
+ * layer's rank; 0 for a refused geometry), contents need not be initialised, 8-byte aligned. Refused before any launch, BT_ERR_BAD_ARG:
+ * a null operand, bad geometry, groups != 1, R outside [0, BT_LOWRANK_MAX_R] or R > 0 without L, sd <= 0 or not finite, neither draws
+ * nor rng, z without eps_w; BT_ERR_UNSUPPORTED: the sizes bt_conv2d_bwd refuses, or more than 65535 samples x pieces in a grid. r above
+ * BT_LOWRANK_MAX_R adds S * n floats behind the partials (at offset bt_lowrank_conv2d_bwd_workspace(g, S, 0)) for that pre-pass. */
+size_t bt_lowrank_conv2d_bwd_workspace(const bt_conv2d_geom *g, int32_t S, int32_t r);
+int bt_lowrank_conv2d_bwd(const bt_conv2d_geom *g, int32_t S, const float *x, int64_t x_sample_stride, const float *grad_out,
+                          const float *mean, int64_t mean_sample_stride, const float *L, int32_t R, float sd, const float *z,
+                          const bt_rng *rng, const float *eps_w, float *dx, float *dW_per_sample, void *workspace,
+                          size_t workspace_bytes, bt_stream_t stream);
+/* What the calling thread's last bt_lowrank_conv2d_bwd planned, as up to 10 values: dgrad launches, wgrad launches, pieces of dgrad's
+ * output-channel reduction, chunks of wgrad's reduction axis, dgrad's grid (x, y, z), wgrad's grid (x, y, z). */
+int bt_lowrank_conv2d_bwd_info(int64_t *out, int32_t n);
+/* The chain rule's finishing pass over the n x (1 + r) parameter gradients, s ascending, one rounding per operation:
+ *   dmu[i] = sum_s dW[s][i],   dL[i][j] = sum_s dW[s][i] * z_s[j]     (any rank r in [1, 4096]).
+ * z: [S][r], or NULL for the tensor 4 stream of rng. dmu or dL may be NULL (not wanted), not both. */
+int bt_lowrank_wgrad_finish(const float *dW_per_sample, int64_t n, int32_t r, int32_t S, const float *z, const bt_rng *rng, float *dmu,
+                            float *dL, bt_stream_t stream);
+/* Gradient of bt_kl_lowrank's KL (kl_out[0]) times grad_kl[0] (a device scalar, never read on the host), in fp64 with fp32 results:
+ *   dmu = c (mu - m) / P,   dL = c (L / P - L (d I + L^T L)^-1)   (row i of L over P_i).
+ * The forward's sweep of L^T L / d, its Cholesky with the factor kept, an explicit r x r inverse from the factor, and one pass over
+ * the n x r gradient: five launches, no host synchronisation. A pivot that is not positive: NaN in every gradient, one more in
+ * *bad_pivots (may be NULL). dmu or dL may be NULL, not both. workspace: bt_kl_lowrank_bwd_workspace(n, r) bytes, 8-byte aligned
+ * (0: r above 4096). */
+size_t bt_kl_lowrank_bwd_workspace(int64_t n, int32_t r);
+int bt_kl_lowrank_bwd(const float *mu, const float *L, int64_t n, int32_t r, float d, const float *prior_mean, const float *prior_var,
+                      const float *grad_kl, float *dmu, float *dL, int32_t *bad_pivots, void *workspace, size_t workspace_bytes,
+                      bt_stream_t stream);
+
 /* MC epilogue (examples/main_bayesian_cifar_dnn2bnn.py:551-557 and :402-412): from logits [S][B][C]
  * accumulate into packed[B*C + B + B*C] = [sum_s softmax | sum_s entropy | sum_s logits] (overwrites). */
 int bt_mc_epilogue(int32_t S, int32_t B, int32_t C, const float *logits, float *packed, bt_stream_t stream);
