@@ -63,6 +63,15 @@ class bt_conv2d_geom(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "Ci", "H", "W", "Co", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "groups")]
 
 
+class bt_chain_member(C.Structure):
+    _fields_ = [("g", C.POINTER(bt_conv2d_geom)), ("x", _vp), ("x_sample_stride", C.c_int64), ("p", C.POINTER(bt_params)), ("d", C.POINTER(bt_draws)),
+                ("ep", C.POINTER(bt_epilogue)), ("out", _vp), ("kl_out", _vp)]
+
+
+CHAIN_MAX = 4          # BT_CHAIN_MAX
+CHAIN_DECLINED = 1     # BT_CHAIN_DECLINED: bt_reparam_conv2d_chain_fwd launched nothing -- the members are not a chain
+
+
 class bt_updil(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("uh", "uw", "lo_h", "hi_h", "lo_w", "hi_w")]
 
@@ -116,6 +125,7 @@ _PROTOS = {
     "bt_flipout_linear_fwd": (C.c_int, [C.c_int32] * 4 + _FWD_TAIL),
     "bt_reparam_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32] + _FWD_TAIL),
     "bt_flipout_conv2d_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.c_int32] + _FWD_TAIL),
+    "bt_reparam_conv2d_chain_fwd": (C.c_int, [C.c_int32, C.POINTER(bt_chain_member), C.c_int32, _vp]),
     "bt_reparam_conv2d_updil_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_updil), C.c_int32] + _FWD_TAIL),
     "bt_flipout_conv2d_updil_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_updil), C.c_int32] + _FWD_TAIL),
     "bt_reparam_conv2d_dwin_fwd": (C.c_int, [C.POINTER(bt_conv2d_geom), C.POINTER(bt_dwin), C.c_int32] + _FWD_TAIL),

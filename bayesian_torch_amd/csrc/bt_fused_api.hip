@@ -264,6 +264,26 @@ extern "C" int bt_flipout_conv2d_fwd(const bt_conv2d_geom* g, int32_t S, const f
   return bt::run({true, false, *g, S, x, x_sample_stride, p, d, ep, out, kl_out, ws, ws_bytes, "bt_flipout_conv2d_fwd", nullptr, nullptr}, stream);
 }
 
+extern "C" int bt_reparam_conv2d_chain_fwd(int32_t n, const bt_chain_member* m, int32_t S, bt_stream_t stream) {
+  using namespace bt;
+  const char* who = "bt_reparam_conv2d_chain_fwd";
+  if (!m || n < 1) return set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_chain_fwd: no members");
+  if (n > BT_CHAIN_MAX) return BT_CHAIN_DECLINED;
+  FwdArgs a[BT_CHAIN_MAX], r;
+  for (int k = 0; k < n; ++k) {
+    if (!m[k].g) return set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_chain_fwd: null geometry");
+    if (m[k].kl_out) return BT_CHAIN_DECLINED;   // (a KL sweep takes a workspace: the member's own call)
+    const Call c{false, false, *m[k].g, S, m[k].x, m[k].x_sample_stride, m[k].p, m[k].d, m[k].ep, m[k].out, nullptr, nullptr, 0, who, nullptr, nullptr};
+    if (int rc = c.validate()) return rc;
+    if (c.packed_eps()) return BT_CHAIN_DECLINED;
+    c.fill_args(false, a[k]);
+  }
+  const int rc = launch_split_chain(n, a, r, (hipStream_t)stream);
+  if (rc != BT_OK) return rc == 1 ? BT_CHAIN_DECLINED : rc;
+  record_plan(r, 0);
+  return BT_OK;
+}
+
 extern "C" int bt_reparam_conv2d_updil_fwd(const bt_conv2d_geom* g, const bt_updil* u, int32_t S, const float* x, int64_t x_sample_stride, const bt_params* p,
                                            const bt_draws* d, const bt_epilogue* ep, float* out, float* kl_out, void* ws, size_t ws_bytes, bt_stream_t stream) {
   if (!g || !u) return bt::set_error(BT_ERR_BAD_ARG, "bt_reparam_conv2d_updil_fwd: null geometry");

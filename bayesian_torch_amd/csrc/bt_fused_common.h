@@ -100,19 +100,21 @@ inline uint64_t digest_arg(uint64_t h, const FwdArgs& a) {
 // its own copy of the arguments: BT_OK and the plan that ran in `ran` when a flavour took the launch, 1 when none applies, < 0 on error.
 int launch_split(FwdArgs a, FwdArgs& ran, hipStream_t stream);
 int launch_split_flip(FwdArgs a, FwdArgs& ran, hipStream_t stream);
+int launch_split_chain(int n, FwdArgs* m, FwdArgs& ran, hipStream_t stream);   // bt_fused_split_chain.hip: n same-shape layers as one launch, or 1
 int contraction_mode();   // 0 automatic, 1 fp32 MFMA only, 2 bf16x2 (opt-in), 3 bf16 (opt-in)
 long long skinny_scratch_bytes(const bt_conv2d_geom& g, int S);   // the split-K flavour's scratch behind the workspace (0: not its launch)
 
 // ---------------------------------------------------------------------------- draw-stream keys
 // The weight draws' key of this launch: (seed, call + the device-side call word, layer, tensor 0).
-__device__ __forceinline__ RngKey weight_key(const FwdArgs& a) {
+__device__ __forceinline__ RngKey weight_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t call, const uint32_t* call_base, uint32_t layer_id) {
   RngKey key_w;
-  key_w.seed_lo = a.seed_lo;
-  key_w.seed_hi = a.seed_hi;
-  key_w.call = a.call + (a.call_base ? __builtin_nontemporal_load(a.call_base) : 0u);
-  key_w.layer_tensor = layer_tensor_word(a.layer_id, 0);
+  key_w.seed_lo = seed_lo;
+  key_w.seed_hi = seed_hi;
+  key_w.call = call + (call_base ? __builtin_nontemporal_load(call_base) : 0u);
+  key_w.layer_tensor = layer_tensor_word(layer_id, 0);
   return key_w;
 }
+__device__ __forceinline__ RngKey weight_key(const FwdArgs& a) { return weight_key(a.seed_lo, a.seed_hi, a.call, a.call_base, a.layer_id); }
 
 // Flipout: the keys of the two sign streams (tensors 2 and 3) of one MC sample.
 __device__ __forceinline__ void sign_keys(const FwdArgs& a, const RngKey& key_w, uint32_t sample, uint32_t* skey_in, uint32_t* skey_out) {
@@ -141,25 +143,34 @@ struct ChannelConsts {
 };
 
 // Channel co_g of group g for the launch's sample s (the index into a.eps_b when the draws are INJected, sample0 + s on chip).
+// The layer's own operands of that computation (one launch: the launch's arguments; a chained launch: the member's, bt_fused_split.h).
+struct ChannelSrc {
+  const float *mu_b, *rho_b, *eps_b, *ep_scale, *ep_shift;
+  uint32_t layer_id;
+};
 template <bool FLIP, bool INJ>
-__device__ __forceinline__ ChannelConsts channel_consts(const FwdArgs& a, const RngKey& key_w, int s, int g, int co_g) {
+__device__ __forceinline__ ChannelConsts channel_consts(const FwdArgs& a, const ChannelSrc& l, const RngKey& key_w, int s, int g, int co_g) {
   ChannelConsts c;
   c.bias0 = 0.f, c.bias1 = 0.f;
-  if (a.mu_b && co_g < a.Cog) {
+  if (l.mu_b && co_g < a.Cog) {
     const int co = g * a.Cog + co_g;
     float e;
-    if constexpr (INJ) e = a.eps_b[(long long)s * a.Co + co];
-    else e = bias_eps(key_w, a.layer_id, a.sample0 + (uint32_t)s, co);
-    const float dl = __fmul_rn(softplus(a.rho_b[co]), e);
-    c.bias0 = FLIP ? a.mu_b[co] : __fadd_rn(a.mu_b[co], dl);
+    if constexpr (INJ) e = l.eps_b[(long long)s * a.Co + co];
+    else e = bias_eps(key_w, l.layer_id, a.sample0 + (uint32_t)s, co);
+    const float dl = __fmul_rn(softplus(l.rho_b[co]), e);
+    c.bias0 = FLIP ? l.mu_b[co] : __fadd_rn(l.mu_b[co], dl);
     c.bias1 = dl;
   }
-  const bool cv = a.ep_scale && co_g < a.Cog;
+  const bool cv = l.ep_scale && co_g < a.Cog;
   const int cs = cv ? g * a.Cog + co_g : 0;
-  const float sc = a.ep_scale ? a.ep_scale[cs] : 1.f, sh = a.ep_shift ? a.ep_shift[cs] : 0.f;
+  const float sc = l.ep_scale ? l.ep_scale[cs] : 1.f, sh = l.ep_shift ? l.ep_shift[cs] : 0.f;
   c.scale = cv ? sc : 1.f;
   c.shift = cv ? sh : 0.f;
   return c;
+}
+template <bool FLIP, bool INJ>
+__device__ __forceinline__ ChannelConsts channel_consts(const FwdArgs& a, const RngKey& key_w, int s, int g, int co_g) {
+  return channel_consts<FLIP, INJ>(a, ChannelSrc{a.mu_b, a.rho_b, a.eps_b, a.ep_scale, a.ep_shift, a.layer_id}, key_w, s, g, co_g);
 }
 
 // ---------------------------------------------------------------------------- KL sweep

@@ -448,19 +448,38 @@ __device__ __forceinline__ void split_one_pixel_tile(const FwdArgs& a, const int
 // 0x00 = +1, 0x80 = -1, a sample's image a multiple of 16 bytes), indexed by exactly the numbers the hash streams take: the element's
 // offset in the sample's x, the output element's index. The s_in bytes of an x item are fetched with its x loads (one stage ahead;
 // where x moves as float4 its four signs are one dword), s_out in the read-out. byte << 24 is the fp32 sign mask.
-template <int BN, int BM, int NP, int NPW, int XM, bool FLIP = false, bool INJ = false>
-__global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdArgs a) {
+//
+// CHAIN (fused_split_chain_kernel below; Reparameterization, on-chip draws, the 64 x 512 tile of whole images with all of a layer's
+// channels): the launch runs a chain of up to kChainMax layers of ONE geometry, layer k + 1 reading what layer k wrote. A tile of such
+// a layer -- t_NI whole images x every channel of one sample -- is exactly the input of the same tile of the next layer, so a workgroup
+// walks the layers over its own images and needs no byte another workgroup produces. What depends on the geometry alone is done once
+// per workgroup: the tile decode, the tap table, the stage shape, the producers' unit and item decode, the consumers' fragment
+// addresses. Per layer: the member's operands (SplitLayer), the buffer clear (the output staging overwrites the zero slots), stage 0,
+// the stage loop, the output stage -- the one-launch code, in its order -- and the hand-off (chain_next).
+constexpr int kChainMax = 4;
+// What differs between the members of a chain; for one launch, the launch's own arguments (split_layer_of).
+struct SplitLayer {
+  const float *x, *mu_pk, *sig_pk, *mu_b, *rho_b, *ep_scale, *ep_shift, *ep_res;
+  float* out;
+  const uint32_t* call_base;
+  long long x_sample_stride, ep_res_stride;
+  uint32_t call, layer_id;
+  int ep_relu, reserved;
+};
+struct ChainTab {
+  int n, reserved;
+  SplitLayer m[kChainMax];
+};
+__host__ __device__ __forceinline__ SplitLayer split_layer_of(const FwdArgs& a) {
+  return SplitLayer{a.x, a.mu_pk, a.sig_pk, a.mu_b, a.rho_b, a.ep_scale, a.ep_shift, a.ep_res, a.out, a.call_base, a.x_sample_stride, a.ep_res_stride, a.call, a.layer_id, a.ep_relu, 0};
+}
+
+template <int BN, int BM, int NP, int NPW, int XM, bool FLIP, bool INJ, bool CHAIN>
+__device__ __forceinline__ void split_tile_body(const FwdArgs& a, [[maybe_unused]] const ChainTab* tab) {
   static_assert((BN == 64 && (BM == 512 || BM == 256 || BM == 128)) || (BN == 32 && BM == 128 && !FLIP), "tile shapes of this flavour");
   static_assert(!FLIP || ((BM == 256 || BM == 128) && NP == 3), "Flipout: the 64 x 256 / 64 x 128 tiles, exact split");
   static_assert(NP >= 1 && NP <= 3 && (NP != 1 || !INJ), "pieces per value; the bf16 mode draws on chip");
-  if constexpr (XM == 1 && !FLIP) {  // one-pixel tiles: a body of their own (above)
-    static_assert(BM == 128 && NPW == 8, "the tile of the 1x1 planes");
-    int tap1;
-    if (one_pixel_tile(a, &tap1)) {  // launch-uniform
-      split_one_pixel_tile<BN, NP, NPW, INJ>(a, tap1);
-      return;
-    }
-  }
+  static_assert(!CHAIN || (BN == 64 && BM == 512 && NP == 3 && NPW == 4 && !FLIP && !INJ && (XM == 3 || XM == 0)), "chains: the whole-image 512-wide tile, exact split, on-chip draws");
   constexpr int kProducers = 64 * NPW, kThreadsAll = 256 + kProducers;
   constexpr int CWM = FLIP ? 2 : 4, CWN = 4 / CWM, WTM = BM / CWM, TN = BN / CWN / 32, TM = WTM / 32;
   constexpr int NOP = FLIP ? 2 : 1;            // weight operands (images per stage) = accumulator sets
@@ -514,7 +533,11 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   const uint32_t sample = a.sample0 + (uint32_t)s;
   const int T = a.T, Cig = a.Cig;
 
-  const RngKey key_w = weight_key(a);
+  // The layer this workgroup is on (CHAIN: member 0 first; chain_next below moves it on) and everything bound to it: not const.
+  SplitLayer lay;
+  if constexpr (CHAIN) lay = tab->m[0];
+  else lay = split_layer_of(a);
+  RngKey key_w = weight_key(a.seed_lo, a.seed_hi, lay.call, lay.call_base, lay.layer_id);
   uint32_t skey_in = 0, skey_out = 0;  // Flipout sign streams
   if constexpr (FLIP) sign_keys(a, key_w, sample, &skey_in, &skey_out);
 
@@ -586,10 +609,27 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   // zeros past the end of the batch / of the channels -- or the shared zero pixel (padding taps, dead columns, the missing
   // half of an odd last pair): clear the two zero pixels. (The barrier that publishes the clear sits in both arms below,
   // behind the work that needs no LDS: the producers have issued stage 0's loads by then.)
-  for (int i = tid; i < 2 * W_BYTES / 16; i += kThreadsAll) reinterpret_cast<uint4*>(smem_c)[i] = make_uint4(0, 0, 0, 0);
-  if (tid < 2 * (PB / 16)) reinterpret_cast<uint4*>(xbuf + (tid / (PB / 16)) * X_BYTES + X_BYTES - PB)[tid % (PB / 16)] = make_uint4(0, 0, 0, 0);
+  auto clear_bufs = [&](int t) {
+    for (int i = t; i < 2 * W_BYTES / 16; i += kThreadsAll) reinterpret_cast<uint4*>(smem_c)[i] = make_uint4(0, 0, 0, 0);
+    if (t < 2 * (PB / 16)) reinterpret_cast<uint4*>(xbuf + (t / (PB / 16)) * X_BYTES + X_BYTES - PB)[t % (PB / 16)] = make_uint4(0, 0, 0, 0);
+  };
+  clear_bufs(tid);
+  // The thread index for what a chain does once per member behind the stage loop (the read-out, the clear). CHAIN: made again from the
+  // wave's number (a scalar) and the lane count, and opaque to the compiler -- so no register carries it across the stage loop, and the
+  // read-out's address arithmetic (the same for every member) is not hoisted out of the chain loop and held there: with the 244 registers
+  // of this tile either would spill.
+  [[maybe_unused]] const int wave_s = CHAIN ? __builtin_amdgcn_readfirstlane(wave) : 0;
+  auto member_tid = [&]() {
+    if constexpr (CHAIN) {
+      int t = wave_s * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      asm volatile("" : "+v"(t));
+      return t;
+    } else {
+      return tid;
+    }
+  };
 
-  const float* const xs = a.x + (long long)s * a.x_sample_stride;
+  const float* xs = lay.x + (long long)s * lay.x_sample_stride;
   constexpr uint32_t kOOB = 0x80000000u;
   // Offset of a guarded load: `off` when the element exists, else an out-of-range offset (the buffer load returns 0). As bit
   // arithmetic on purpose: written as a select, the compiler sinks the offset computation into a branch per load, and the
@@ -601,12 +641,12 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   };
   const int Cig4 = Cig;  // a multiple of 8 here
   const int pk_bytes = a.Co * T * Cig4 * 4;
-  const __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.mu_pk), 0, pk_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sig_pk), 0, pk_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)(a.x_elems * 4), 0x00020000);
+  __amdgpu_buffer_rsrc_t r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lay.mu_pk), 0, pk_bytes, 0x00020000);
+  __amdgpu_buffer_rsrc_t r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lay.sig_pk), 0, pk_bytes, 0x00020000);
+  __amdgpu_buffer_rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)(a.x_elems * 4), 0x00020000);
   // INJ: this sample's image of the packed draws (a wave-uniform base: the descriptor stays in SGPRs)
   [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_ep =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : a.mu_pk), 0, pk_bytes, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(INJ ? a.eps_w + (long long)s * (pk_bytes >> 2) : lay.mu_pk), 0, pk_bytes, 0x00020000);
   auto ldf = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, 0, 0)); };
   auto ldf4 = [](const __amdgpu_buffer_rsrc_t& r, uint32_t byte_off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0)); };
   // FLIP && INJ: this sample's sign images (per sample also when x is shared). The fp32 factor of a packed s_out byte: +-1.0.
@@ -629,14 +669,35 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   float* const bias1 = smem + BN;  // Flipout: the sigma*eps part of the bias
   float* const osc = smem + 2 * BN;
   float* const osh = smem + 3 * BN;
-  const bool kl_block = a.do_kl && (int)blockIdx.x < a.kl_slices;
-  float* const out_s = a.out + (long long)s * a.out_elems;
-  const float* const res_s = a.ep_res ? a.ep_res + (long long)s * a.ep_res_stride : nullptr;
+  const bool kl_block = !CHAIN && a.do_kl && (int)blockIdx.x < a.kl_slices;   // (the host chains no layer that sweeps its KL)
+  float* out_s = lay.out + (long long)s * a.out_elems;
+  const float* res_s = lay.ep_res ? lay.ep_res + (long long)s * lay.ep_res_stride : nullptr;
   // The scalar output stage's two vector forms (below) store 8 / 16 bytes at even / quad element offsets: legal only from bases that
   // are aligned so (a sliced result or residual is 4-byte aligned). Wave-uniform: else the element-wise form, the same values.
-  const uint32_t out_mis = (uint32_t)((uintptr_t)out_s | (uintptr_t)res_s);
-  const bool relu = a.ep_relu != 0;
+  uint32_t out_mis = (uint32_t)((uintptr_t)out_s | (uintptr_t)res_s);
+  bool relu = lay.ep_relu != 0;
   if (stamp0 && tid == 0) dbg_[212] = __builtin_amdgcn_s_memtime();
+  // CHAIN, every wave behind its output stage of member k - 1: on to member k. The member's out is the next one's x (and may be a later
+  // residual): each wave drains its stores, then ONE workgroup barrier, and only behind it is anything of member k read. Writer and reader
+  // are waves of one workgroup, on one CU behind one L1: workgroup scope orders them -- no agent-scope fence, no L2 write-back. Every
+  // intermediate is written once and read only afterwards (the host refuses chains whose buffers overlap), so no line can be stale.
+  // The same barrier frees the staged output tile: the clear that follows it restores the zero slots the staging overwrote.
+  [[maybe_unused]] auto chain_next = [&](int k) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    lay = tab->m[k];
+    key_w = weight_key(a.seed_lo, a.seed_hi, lay.call, lay.call_base, lay.layer_id);
+    xs = lay.x + (long long)s * lay.x_sample_stride;
+    r_mu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lay.mu_pk), 0, pk_bytes, 0x00020000);
+    r_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(lay.sig_pk), 0, pk_bytes, 0x00020000);
+    r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)(a.x_elems * 4), 0x00020000);
+    out_s = lay.out + (long long)s * a.out_elems;
+    res_s = lay.ep_res ? lay.ep_res + (long long)s * lay.ep_res_stride : nullptr;
+    out_mis = (uint32_t)((uintptr_t)out_s | (uintptr_t)res_s);
+    relu = lay.ep_relu != 0;
+    clear_bufs(member_tid());
+  };
+  [[maybe_unused]] const int chain_n = CHAIN ? tab->n : 1;
 
   // Read-out of one staged pass of the output tile (SROWS channels) by every wave (see the output stage below). A thread's
   // items share one pixel quad (the thread count is a multiple of the quads per row) and step RSTEP channels: the quad is
@@ -644,7 +705,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   auto readout_quads = [&](int pass, int t0) {
     constexpr int SROW = BM + 4, QROW = BM / 4, NT_ = kThreadsAll;
     static_assert(NT_ % QROW == 0, "a thread keeps its pixel quad");
-    constexpr int RSTEP = NT_ / QROW, NITc = (SROWS + RSTEP - 1) / RSTEP, U = NITc < 8 ? NITc : 8;
+    constexpr int RSTEP = NT_ / QROW, NITc = (SROWS + RSTEP - 1) / RSTEP, UCAP = CHAIN ? 4 : 8, U = NITc < UCAP ? NITc : UCAP;   // (a chain's producers keep their decoded units and items across the read-out: fewer items in flight)
     const float* const stage = smem + 4 * BN;
     const int m4 = t0 % QROW, row0 = t0 / QROW;
     int bq, hq, wq;
@@ -703,6 +764,9 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
   // A thread keeps one tile column (the thread count is a multiple of BM) and walks the channels: consecutive lanes store
   // consecutive pixels of an image -- contiguous 4-byte stores instead of one scattered store per (lane = channel, pixel).
   const bool stage_cols = !a.out_vec4 && !pix && !a.row_taps && a.Ho * a.Wo > 4;
+  // (a chain's tiles always pass through LDS -- the host chains no layer of the scalar output stage: its per-register decode, the same
+  //  for every member, would be hoisted out of the chain loop and spill)
+  const bool staged_out = CHAIN || a.out_vec4 || stage_cols;
   auto readout_cols = [&](int pass, int t0) {
     constexpr int SROW = BM + 4, NT_ = kThreadsAll;
     static_assert(NT_ % BM == 0, "a thread keeps its column");
@@ -796,7 +860,7 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         }
       }
     };
-    if (NS > 0) load_w(0);  // stage 0's weight loads fly while the x items are decoded
+    if (NS > 0 && !(CHAIN && XM == 0)) load_w(0);  // stage 0's weight loads fly while the x items are decoded
     // x items of this thread (see XM above): global byte offset of the item at octet 0, LDS byte offset inside an x buffer,
     // octet inside the stage.
     constexpr int PIT = (XM == 3 || XM == 4) ? ((XPO - 1) / 2 + kProducers - 1) / kProducers : (XPO - 1 + kProducers - 1) / kProducers;   // (XPO - 1 patch slots + the zero pixel)
@@ -1091,85 +1155,96 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
         }
       }
     };
-    if (NS > 0) load_x(0);
-    if (stamp0) dbg_[215] = __builtin_amdgcn_s_memtime();
-    __syncthreads();  // cleared buffers
     const bool pstamp = dbg_ && blockIdx.x == 0 && tid == 256;
-    for (int st = 0; st <= NS; ++st) {  // NS + 1 barriers, like the consumer arm
-      if (pstamp && st < 60) dbg_[128 + 2 * st] = __builtin_amdgcn_s_memtime();
-      if (pstamp && st == 3) dbg_[250] = dbg_[251] = __builtin_amdgcn_s_memtime();
-      if (st < NS) {
-        char* const Wt = wbuf + (st & 1) * W_BYTES;
-        char* const Xt = xbuf + (st & 1) * X_BYTES;
-        const int oct0 = st * NO;  // first octet of this stage
-        // ---- draws (no load feeds them) ----
-        float ep[UMAX][4];
+    for (int ck = 0;; ++ck) {  // one trip per member of a chain; one launch: one trip
+      if constexpr (CHAIN) {  // (member 0's weight loads were issued above, ahead of the item decode -- but for xm 0, whose five items per thread leave them no registers there)
+        if (ck > 0 && prio_mode == 0) __builtin_amdgcn_s_setprio(3);
+        if ((ck > 0 || XM == 0) && NS > 0) load_w(0);
+      }
+      if (NS > 0) load_x(0);
+      if (stamp0) dbg_[215] = __builtin_amdgcn_s_memtime();
+      __syncthreads();  // cleared buffers
+      for (int st = 0; st <= NS; ++st) {  // NS + 1 barriers, like the consumer arm
+        if (pstamp && st < 60) dbg_[128 + 2 * st] = __builtin_amdgcn_s_memtime();
+        if (pstamp && st == 3) dbg_[250] = dbg_[251] = __builtin_amdgcn_s_memtime();
+        if (st < NS) {
+          char* const Wt = wbuf + (st & 1) * W_BYTES;
+          char* const Xt = xbuf + (st & 1) * X_BYTES;
+          const int oct0 = st * NO;  // first octet of this stage
+          // ---- draws (no load feeds them) ----
+          float ep[UMAX][4];
 #pragma unroll
-        for (int i = 0; i < UMAX; ++i)
-          if (u_live[i]) {  // wave-uniform
-            if constexpr (INJ) ep[i][0] = epl[i].x, ep[i][1] = epl[i].y, ep[i][2] = epl[i].z, ep[i][3] = epl[i].w;
-            else philox_normal4(key_w, sample, (e_off[i] + (uint32_t)(8 * oct0)) >> 2, ep[i]);
-          }
-        if (pstamp && st == 3) dbg_[252] = __builtin_amdgcn_s_memtime();
-        // ---- sampled weights -> pieces -> LDS ----
-#pragma unroll
-        for (int i = 0; i < UMAX; ++i) {
-          if (u_live[i]) {  // wave-uniform
-            const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
-            if constexpr (NP == 1) {  // the sampled weight in fp32 as everywhere (same operations, same order), then rounded once
-              float w4[4];
-#pragma unroll
-              for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j]));
-              if (l_off[i] >= 0) *reinterpret_cast<uint2*>(Wt + l_off[i]) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
-              continue;
+          for (int i = 0; i < UMAX; ++i)
+            if (u_live[i]) {  // wave-uniform
+              if constexpr (INJ) ep[i][0] = epl[i].x, ep[i][1] = epl[i].y, ep[i][2] = epl[i].z, ep[i][3] = epl[i].w;
+              else philox_normal4(key_w, sample, (e_off[i] + (uint32_t)(8 * oct0)) >> 2, ep[i]);
             }
-            uint32_t wh[4], wm_[4], wl[4];
+          if (pstamp && st == 3) dbg_[252] = __builtin_amdgcn_s_memtime();
+          // ---- sampled weights -> pieces -> LDS ----
 #pragma unroll
-            for (int j = 0; j < 4; ++j)  // masked units loaded zeros: w = 0 + 0 * eps = 0.  Flipout: the mean alone
-              split_pieces(FLIP ? m4[j] : __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j])), wh[j], wm_[j], wl[j]);
-            if (l_off[i] >= 0) {
-              char* const dst = Wt + l_off[i];
-              *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
-              if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
-              if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
-            }
-            if constexpr (FLIP) {  // second image: the perturbation sigma * eps
+          for (int i = 0; i < UMAX; ++i) {
+            if (u_live[i]) {  // wave-uniform
+              const float m4[4] = {mu[i].x, mu[i].y, mu[i].z, mu[i].w}, s4[4] = {rs[i].x, rs[i].y, rs[i].z, rs[i].w};
+              if constexpr (NP == 1) {  // the sampled weight in fp32 as everywhere (same operations, same order), then rounded once
+                float w4[4];
 #pragma unroll
-              for (int j = 0; j < 4; ++j) split_pieces(__fmul_rn(s4[j], ep[i][j]), wh[j], wm_[j], wl[j]);
+                for (int j = 0; j < 4; ++j) w4[j] = __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j]));
+                if (l_off[i] >= 0) *reinterpret_cast<uint2*>(Wt + l_off[i]) = make_uint2(rne_pair(w4[0], w4[1]), rne_pair(w4[2], w4[3]));
+                continue;
+              }
+              uint32_t wh[4], wm_[4], wl[4];
+#pragma unroll
+              for (int j = 0; j < 4; ++j)  // masked units loaded zeros: w = 0 + 0 * eps = 0.  Flipout: the mean alone
+                split_pieces(FLIP ? m4[j] : __fadd_rn(m4[j], __fmul_rn(s4[j], ep[i][j])), wh[j], wm_[j], wl[j]);
               if (l_off[i] >= 0) {
-                char* const dst = Wt + W_OP + l_off[i];
+                char* const dst = Wt + l_off[i];
                 *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
-                *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
-                *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
+                if constexpr (NP >= 2) *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+                if constexpr (NP == 3) *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
+              }
+              if constexpr (FLIP) {  // second image: the perturbation sigma * eps
+#pragma unroll
+                for (int j = 0; j < 4; ++j) split_pieces(__fmul_rn(s4[j], ep[i][j]), wh[j], wm_[j], wl[j]);
+                if (l_off[i] >= 0) {
+                  char* const dst = Wt + W_OP + l_off[i];
+                  *reinterpret_cast<uint2*>(dst) = make_uint2(pack_hi16(wh[1], wh[0]), pack_hi16(wh[3], wh[2]));
+                  *reinterpret_cast<uint2*>(dst + W_PIECE) = make_uint2(pack_hi16(wm_[1], wm_[0]), pack_hi16(wm_[3], wm_[2]));
+                  *reinterpret_cast<uint2*>(dst + 2 * W_PIECE) = make_uint2(pack_hi16(wl[1], wl[0]), pack_hi16(wl[3], wl[2]));
+                }
               }
             }
           }
+          if (pstamp && st == 3) dbg_[253] = __builtin_amdgcn_s_memtime();
+          // ---- activations: this thread's items of the stage's NO octet planes, split on the way to LDS ----
+          store_x(Xt, st);
+          if (st + 1 < NS) load_x(st + 1), load_w(st + 1);  // next stage's loads: in flight across the barrier and the draws
         }
-        if (pstamp && st == 3) dbg_[253] = __builtin_amdgcn_s_memtime();
-        // ---- activations: this thread's items of the stage's NO octet planes, split on the way to LDS ----
-        store_x(Xt, st);
-        if (st + 1 < NS) load_x(st + 1), load_w(st + 1);  // next stage's loads: in flight across the barrier and the draws
-      }
-      if (pstamp && st < 60) dbg_[128 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
-      __syncthreads();
-    }
-    // bias draw + output-stage constants of this workgroup's channels
-    if (ptid < BN) {
-      const ChannelConsts c = channel_consts<FLIP, INJ>(a, key_w, s, g, n0 + ptid);
-      bias0[ptid] = c.bias0;
-      if constexpr (FLIP) bias1[ptid] = c.bias1;
-      osc[ptid] = c.scale;
-      osh[ptid] = c.shift;
-    }
-    __syncthreads();
-    if (a.out_vec4 || stage_cols) {  // the consumers pass the output tile through LDS: same barriers and a share of the read-out
-      __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-      for (int ps = 0; ps < NPASS; ++ps) {
-        if (ps > 0) __syncthreads();
+        if (pstamp && st < 60) dbg_[128 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
         __syncthreads();
-        if (a.out_vec4) readout_quads(ps, tid);
-        else readout_cols(ps, tid);
+      }
+      // bias draw + output-stage constants of this workgroup's channels
+      if (ptid < BN) {
+        const ChannelConsts c = channel_consts<FLIP, INJ>(a, ChannelSrc{lay.mu_b, lay.rho_b, a.eps_b, lay.ep_scale, lay.ep_shift, lay.layer_id}, key_w, s, g, n0 + ptid);
+        bias0[ptid] = c.bias0;
+        if constexpr (FLIP) bias1[ptid] = c.bias1;
+        osc[ptid] = c.scale;
+        osh[ptid] = c.shift;
+      }
+      __syncthreads();
+      if (staged_out) {  // the consumers pass the output tile through LDS: same barriers and a share of the read-out
+        __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+        for (int ps = 0; ps < NPASS; ++ps) {
+          if (ps > 0) __syncthreads();
+          __syncthreads();
+          if (a.out_vec4) readout_quads(ps, member_tid());
+          else readout_cols(ps, member_tid());
+        }
+      }
+      if constexpr (!CHAIN) break;
+      else {
+        if (ck + 1 >= chain_n) break;
+        chain_next(ck + 1);
       }
     }
   } else {
@@ -1226,275 +1301,282 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
 #pragma unroll
     for (int q = 0; q < kSplitSteps; ++q) wlq[q] = lh * W_HALF + (li ^ ((2 * q + lh) & 7)) * 16 + wn * TN * 32 * 16;
 
-    f32x16 acc[NOP][TN][TM];
-#pragma unroll
-    for (int o = 0; o < NOP; ++o)
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[o][i][j][r] = 0.f;
-    if (prio_mode == 2) __builtin_amdgcn_s_setprio(3);
-
     const bool cstamp = dbg_ && blockIdx.x == 0 && tid == 0;
-    if (cstamp) dbg_[216] = __builtin_amdgcn_s_memtime();
-    __syncthreads();  // cleared buffers
-    __syncthreads();  // stage 0 staged
-    if (cstamp) dbg_[0] = __builtin_amdgcn_s_memtime();
-    for (int st = 0; st < NS; ++st) {
-      if (cstamp && st < 60) dbg_[2 + 2 * st] = __builtin_amdgcn_s_memtime();
-      const char* const Wt = wbuf + (st & 1) * W_BYTES;
-      const char* const Xt = xbuf + (st & 1) * X_BYTES;
-      int nstep = NSTEP;  // the last stage may hold fewer octets
-      if ((st + 1) * NO > G8) {
-        const int no_l = G8 - st * NO;
-        nstep = nA <= 1 ? (no_l + 1) >> 1 : no_l * SPO;
-      }
-      // (step, column group) units in a software pipeline: the fragments of unit u+1 (and, at a step's last unit, the next
-      // step's weight fragments) are read into the other register set BEFORE the 2*terms MFMAs of unit u, so an LDS round
-      // trip never sits between two MFMAs; only the first unit behind the stage barrier waits for its reads.
-      {
-        constexpr int NXP = NP + (FLIP ? 1 : 0);  // x fragments per unit: the pieces (+ the sign masks)
-        bf16x8 wf[2][NOP][TN][NP], xf[2][NXP];
-        auto read_w = [&](int q) {
+    for (int ck = 0;; ++ck) {  // one trip per member of a chain; one launch: one trip
+      f32x16 acc[NOP][TN][TM];
 #pragma unroll
-          for (int o = 0; o < NOP; ++o)
+      for (int o = 0; o < NOP; ++o)
 #pragma unroll
-            for (int i = 0; i < TN; ++i)
+        for (int i = 0; i < TN; ++i)
 #pragma unroll
-              for (int p = 0; p < NP; ++p)
-                wf[q & 1][o][i][p] = *reinterpret_cast<const bf16x8*>(Wt + o * W_OP + wlq[q] + q * W_STEP + p * W_PIECE + i * 32 * 16);
-        };
-        auto read_x = [&](int u) {
-          const char* const px = Xt + xaddr[u % TM][u / TM];
+          for (int j = 0; j < TM; ++j)
 #pragma unroll
-          for (int p = 0; p < NXP; ++p) xf[u & 1][p] = *reinterpret_cast<const bf16x8*>(px + 16 * p);
-        };
-        read_w(0);
-        read_x(0);
+            for (int r = 0; r < 16; ++r) acc[o][i][j][r] = 0.f;
+      if (prio_mode == 2) __builtin_amdgcn_s_setprio(3);
+
+      if (cstamp) dbg_[216] = __builtin_amdgcn_s_memtime();
+      __syncthreads();  // cleared buffers
+      __syncthreads();  // stage 0 staged
+      if (cstamp) dbg_[0] = __builtin_amdgcn_s_memtime();
+      for (int st = 0; st < NS; ++st) {
+        if (cstamp && st < 60) dbg_[2 + 2 * st] = __builtin_amdgcn_s_memtime();
+        const char* const Wt = wbuf + (st & 1) * W_BYTES;
+        const char* const Xt = xbuf + (st & 1) * X_BYTES;
+        int nstep = NSTEP;  // the last stage may hold fewer octets
+        if ((st + 1) * NO > G8) {
+          const int no_l = G8 - st * NO;
+          nstep = nA <= 1 ? (no_l + 1) >> 1 : no_l * SPO;
+        }
+        // (step, column group) units in a software pipeline: the fragments of unit u+1 (and, at a step's last unit, the next
+        // step's weight fragments) are read into the other register set BEFORE the 2*terms MFMAs of unit u, so an LDS round
+        // trip never sits between two MFMAs; only the first unit behind the stage barrier waits for its reads.
+        {
+          constexpr int NXP = NP + (FLIP ? 1 : 0);  // x fragments per unit: the pieces (+ the sign masks)
+          bf16x8 wf[2][NOP][TN][NP], xf[2][NXP];
+          auto read_w = [&](int q) {
 #pragma unroll
-        for (int q = 0; q < kSplitSteps; ++q) {
-          if (q < nstep) {  // uniform
+            for (int o = 0; o < NOP; ++o)
 #pragma unroll
-            for (int j = 0; j < TM; ++j) {
-              const int u = q * TM + j;
-              if (j + 1 < TM) {
-                read_x(u + 1);
-              } else if (q + 1 < kSplitSteps) {
-                if (q + 1 < nstep) {
+              for (int i = 0; i < TN; ++i)
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+                  wf[q & 1][o][i][p] = *reinterpret_cast<const bf16x8*>(Wt + o * W_OP + wlq[q] + q * W_STEP + p * W_PIECE + i * 32 * 16);
+          };
+          auto read_x = [&](int u) {
+            const char* const px = Xt + xaddr[u % TM][u / TM];
+#pragma unroll
+            for (int p = 0; p < NXP; ++p) xf[u & 1][p] = *reinterpret_cast<const bf16x8*>(px + 16 * p);
+          };
+          read_w(0);
+          read_x(0);
+#pragma unroll
+          for (int q = 0; q < kSplitSteps; ++q) {
+            if (q < nstep) {  // uniform
+#pragma unroll
+              for (int j = 0; j < TM; ++j) {
+                const int u = q * TM + j;
+                if (j + 1 < TM) {
                   read_x(u + 1);
-                  read_w(q + 1);
-                }
-              }
-              __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-              for (int o = 0; o < NOP; ++o) {
-                if (o == 1) {  // Flipout: x o s_in -- flip the sign bits of every piece (the split of -v is the negated split of v)
-#pragma unroll
-                  for (int p = 0; p < NP; ++p) xf[u & 1][p] ^= xf[u & 1][NXP - 1];
-                }
-#pragma unroll
-                for (int i = 0; i < TN; ++i) {
-                  // D[pixel][channel]: x is the A operand, W the B operand; terms in decreasing weight
-                  acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
-                  if constexpr (NP >= 2) {
-                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
-                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
-                  }
-                  if constexpr (NP == 3) {
-                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][2], acc[o][i][j], 0, 0, 0);
-                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
-                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][2], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                } else if (q + 1 < kSplitSteps) {
+                  if (q + 1 < nstep) {
+                    read_x(u + 1);
+                    read_w(q + 1);
                   }
                 }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int o = 0; o < NOP; ++o) {
+                  if (o == 1) {  // Flipout: x o s_in -- flip the sign bits of every piece (the split of -v is the negated split of v)
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) xf[u & 1][p] ^= xf[u & 1][NXP - 1];
+                  }
+#pragma unroll
+                  for (int i = 0; i < TN; ++i) {
+                    // D[pixel][channel]: x is the A operand, W the B operand; terms in decreasing weight
+                    acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                    if constexpr (NP >= 2) {
+                      acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
+                      acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                    }
+                    if constexpr (NP == 3) {
+                      acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][0], wf[q & 1][o][i][2], acc[o][i][j], 0, 0, 0);
+                      acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][1], wf[q & 1][o][i][1], acc[o][i][j], 0, 0, 0);
+                      acc[o][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[u & 1][2], wf[q & 1][o][i][0], acc[o][i][j], 0, 0, 0);
+                    }
+                  }
+                }
+                __builtin_amdgcn_sched_barrier(0);
               }
-              __builtin_amdgcn_sched_barrier(0);
             }
           }
         }
+        if (cstamp && st < 60) dbg_[2 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
+        if (kl_block) kls.group(a);   // (fetching the group one stage ahead was tried in round 3: the 16 registers it holds across the MFMA loop spill on
+                                      //  the 256-wide tiles -- layer3 +5..19 % -- and layer4's 128-wide launches did not move: dropped)
+        __syncthreads();
       }
-      if (cstamp && st < 60) dbg_[2 + 2 * st + 1] = __builtin_amdgcn_s_memtime();
-      if (kl_block) kls.group(a);   // (fetching the group one stage ahead was tried in round 3: the 16 registers it holds across the MFMA loop spill on
-                                    //  the 256-wide tiles -- layer3 +5..19 % -- and layer4's 128-wide launches did not move: dropped)
-      __syncthreads();
-    }
-    if (kl_block) kl_finish();
-    if (cstamp) dbg_[1] = __builtin_amdgcn_s_memtime();
-    __syncthreads();  // the producers have staged bias / output-stage constants; every consumer wave has published its KL partial
-    if (kl_block && wave == 0) kl_ticket();
-    if (cstamp) dbg_[120] = __builtin_amdgcn_s_memtime();
+      if (kl_block) kl_finish();
+      if (cstamp) dbg_[1] = __builtin_amdgcn_s_memtime();
+      __syncthreads();  // the producers have staged bias / output-stage constants; every consumer wave has published its KL partial
+      if (kl_block && wave == 0) kl_ticket();
+      if (cstamp) dbg_[120] = __builtin_amdgcn_s_memtime();
 
-    // ---- output stage + store (bt_fused_fast.h: lane = one channel, registers 4q..4q+3 = 4 consecutive positions) ----
-    if (a.out_vec4 || stage_cols) {
-      constexpr int SROW = BM + 4;
-      static_assert((4 * BN + NOP * SROWS * SROW) * 4 <= STAGE_CAP, "output staging fits the operand buffers");
-      float* const stage = smem + 4 * BN;
-      float bsv[TN], scv[TN], shv[TN], b1v[TN];
-#pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        const int co_l = (wn * TN + i) * 32 + li;
-        bsv[i] = bias0[co_l], scv[i] = osc[co_l], shv[i] = osh[co_l];
-        b1v[i] = FLIP ? bias1[co_l] : 0.f;
-      }
-#pragma unroll
-      for (int ps = 0; ps < NPASS; ++ps) {
-        if (ps > 0) __syncthreads();  // the previous pass has been read out
+      // ---- output stage + store (bt_fused_fast.h: lane = one channel, registers 4q..4q+3 = 4 consecutive positions) ----
+      if (staged_out) {
+        constexpr int SROW = BM + 4;
+        static_assert((4 * BN + NOP * SROWS * SROW) * 4 <= STAGE_CAP, "output staging fits the operand buffers");
+        float* const stage = smem + 4 * BN;
+        float bsv[TN], scv[TN], shv[TN], b1v[TN];
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
-          const int cg = wn * TN + i;  // this wave's 32-channel group inside the tile
-          if (cg >= ps * (SROWS / 32) && cg < (ps + 1) * (SROWS / 32)) {
-            float* const srow = stage + ((cg - ps * (SROWS / 32)) * 32 + li) * SROW + wm * WTM + 4 * lh;
+          const int co_l = (wn * TN + i) * 32 + li;
+          bsv[i] = bias0[co_l], scv[i] = osc[co_l], shv[i] = osh[co_l];
+          b1v[i] = FLIP ? bias1[co_l] : 0.f;
+        }
 #pragma unroll
-            for (int j = 0; j < TM; ++j) {
+        for (int ps = 0; ps < NPASS; ++ps) {
+          if (ps > 0) __syncthreads();  // the previous pass has been read out
 #pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                float v[4];
-                if constexpr (FLIP) {  // both sets as they are (+ their bias parts): s_out and the constants meet them in the read-out
+          for (int i = 0; i < TN; ++i) {
+            const int cg = wn * TN + i;  // this wave's 32-channel group inside the tile
+            if (cg >= ps * (SROWS / 32) && cg < (ps + 1) * (SROWS / 32)) {
+              float* const srow = stage + ((cg - ps * (SROWS / 32)) * 32 + li) * SROW + wm * WTM + 4 * lh;
 #pragma unroll
-                  for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(acc[0][i][j][4 * q + e], bsv[i]);
-                  *reinterpret_cast<float4*>(srow + j * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+              for (int j = 0; j < TM; ++j) {
 #pragma unroll
-                  for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(acc[NOP - 1][i][j][4 * q + e], b1v[i]);
-                  *reinterpret_cast<float4*>(srow + SROWS * SROW + j * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
+                for (int q = 0; q < 4; ++q) {
+                  float v[4];
+                  if constexpr (FLIP) {  // both sets as they are (+ their bias parts): s_out and the constants meet them in the read-out
 #pragma unroll
-                  for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(__fmul_rn(__fadd_rn(acc[0][i][j][4 * q + e], bsv[i]), scv[i]), shv[i]);
-                  *reinterpret_cast<float4*>(srow + j * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+                    for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(acc[0][i][j][4 * q + e], bsv[i]);
+                    *reinterpret_cast<float4*>(srow + j * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(acc[NOP - 1][i][j][4 * q + e], b1v[i]);
+                    *reinterpret_cast<float4*>(srow + SROWS * SROW + j * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+                  } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = __fadd_rn(__fmul_rn(__fadd_rn(acc[0][i][j][4 * q + e], bsv[i]), scv[i]), shv[i]);
+                    *reinterpret_cast<float4*>(srow + j * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+                  }
                 }
               }
             }
           }
+          if (cstamp) dbg_[121] = __builtin_amdgcn_s_memtime();
+          __syncthreads();
+          if (cstamp) dbg_[122] = __builtin_amdgcn_s_memtime();
+          if (a.out_vec4) readout_quads(ps, member_tid());
+          else readout_cols(ps, member_tid());
+          if (cstamp) dbg_[123] = __builtin_amdgcn_s_memtime();
         }
-        if (cstamp) dbg_[121] = __builtin_amdgcn_s_memtime();
-        __syncthreads();
-        if (cstamp) dbg_[122] = __builtin_amdgcn_s_memtime();
-        if (a.out_vec4) readout_quads(ps, tid);
-        else readout_cols(ps, tid);
-        if (cstamp) dbg_[123] = __builtin_amdgcn_s_memtime();
-      }
-    } else {
-      // Scalar stores: lanes run along the channels (consecutive addresses when Ho*Wo == 1: Linear and 1x1 maps).
-      float bsv[TN], scv[TN], shv[TN], b1v[TN];
-      bool cok[TN];
+      } else {
+        // Scalar stores: lanes run along the channels (consecutive addresses when Ho*Wo == 1: Linear and 1x1 maps).
+        float bsv[TN], scv[TN], shv[TN], b1v[TN];
+        bool cok[TN];
 #pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        const int co_l = (wn * TN + i) * 32 + li;
-        bsv[i] = bias0[co_l], scv[i] = osc[co_l], shv[i] = osh[co_l];
-        b1v[i] = FLIP ? bias1[co_l] : 0.f;
-        cok[i] = n0 + co_l < a.Cog;
-      }
-      const int HoWo = a.Ho * a.Wo;
-      auto outv = [&](int i, int j, int r, uint32_t oi) -> float {   // output-stage value of accumulator register r (before residual / ReLU)
-        float v = __fadd_rn(acc[0][i][j][r], bsv[i]);
-        if constexpr (SGN) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), so_f((uint32_t)so_s[oi], 0)));
-        else if constexpr (FLIP) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), hash_sign(skey_out, oi)));
-        return __fadd_rn(__fmul_rn(v, scv[i]), shv[i]);
-      };
-      // In all three forms below the residual values of a column group are fetched in ONE batch before its first store: written
-      // as load -> add -> store per element, the loads cannot be moved above the stores (the compiler has to assume out and
-      // residual alias) and every element pays a full memory round trip -- 17 K of layer3's 170 K cycles per workgroup.
-      if (a.row_taps && t_Wt == 2 && (a.Wo & 1) == 0 && (out_mis & 7u) == 0) {
-        // Row tiles of two-pixel rows: columns 2i, 2i + 1 are the two pixels of one image's row -- 8 contiguous bytes per channel.
+        for (int i = 0; i < TN; ++i) {
+          const int co_l = (wn * TN + i) * 32 + li;
+          bsv[i] = bias0[co_l], scv[i] = osc[co_l], shv[i] = osh[co_l];
+          b1v[i] = FLIP ? bias1[co_l] : 0.f;
+          cok[i] = n0 + co_l < a.Cog;
+        }
+        const int HoWo = a.Ho * a.Wo;
+        auto outv = [&](int i, int j, int r, uint32_t oi) -> float {   // output-stage value of accumulator register r (before residual / ReLU)
+          float v = __fadd_rn(acc[0][i][j][r], bsv[i]);
+          if constexpr (SGN) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), so_f((uint32_t)so_s[oi], 0)));
+          else if constexpr (FLIP) v = __fadd_rn(v, __fmul_rn(__fadd_rn(acc[NOP - 1][i][j][r], b1v[i]), hash_sign(skey_out, oi)));
+          return __fadd_rn(__fmul_rn(v, scv[i]), shv[i]);
+        };
+        // In all three forms below the residual values of a column group are fetched in ONE batch before its first store: written
+        // as load -> add -> store per element, the loads cannot be moved above the stores (the compiler has to assume out and
+        // residual alias) and every element pays a full memory round trip -- 17 K of layer3's 170 K cycles per workgroup.
+        if (a.row_taps && t_Wt == 2 && (a.Wo & 1) == 0 && (out_mis & 7u) == 0) {
+          // Row tiles of two-pixel rows: columns 2i, 2i + 1 are the two pixels of one image's row -- 8 contiguous bytes per channel.
+#pragma unroll
+          for (int j = 0; j < TM; ++j) {
+            uint32_t base[8];
+            bool live[8];
+            float2 rr[8][TN];
+#pragma unroll
+            for (int r2 = 0; r2 < 8; ++r2) {
+              const int r = 2 * r2, row = (r & 3) + 8 * (r >> 2) + 4 * lh;   // even
+              int bb, hh, ww;
+              live[r2] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (ww == 0; column + 1 is the same image's second pixel)
+              base[r2] = live[r2] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo + hh * a.Wo + ww) : 0u;
+#pragma unroll
+              for (int i = 0; i < TN; ++i) {
+                rr[r2][i] = make_float2(0.f, 0.f);
+                if (res_s && live[r2] && cok[i]) rr[r2][i] = *reinterpret_cast<const float2*>(res_s + base[r2] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo));
+              }
+            }
+#pragma unroll
+            for (int r2 = 0; r2 < 8; ++r2) {
+              const int r = 2 * r2;
+#pragma unroll
+              for (int i = 0; i < TN; ++i) {
+                if (live[r2] && cok[i]) {
+                  const uint32_t oi = base[r2] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo);
+                  float v0 = outv(i, j, r, oi), v1 = outv(i, j, r + 1, oi + 1u);
+                  if (res_s) v0 = __fadd_rn(v0, rr[r2][i].x), v1 = __fadd_rn(v1, rr[r2][i].y);
+                  v0 = (relu && v0 < 0.f) ? 0.f : v0, v1 = (relu && v1 < 0.f) ? 0.f : v1;
+                  *reinterpret_cast<float2*>(out_s + oi) = make_float2(v0, v1);
+                }
+              }
+            }
+          }
+        } else if (!pix && !a.row_taps && HoWo == 4 && t_R == a.Ho && t_Wt == a.Wo && (out_mis & 15u) == 0) {
+          // Tiles of whole four-pixel images: columns 4i .. 4i + 3 are one image's plane -- 16 contiguous bytes per channel.
+#pragma unroll
+          for (int j = 0; j < TM; ++j) {
+            uint32_t base[4];
+            bool live[4];
+            float4 rr[4][TN];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int row = 8 * q + 4 * lh;   // a multiple of 4
+              int bb, hh, ww;
+              live[q] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (pixel 0 of image bb)
+              base[q] = live[q] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo) : 0u;
+#pragma unroll
+              for (int i = 0; i < TN; ++i) {
+                rr[q][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (res_s && live[q] && cok[i]) rr[q][i] = *reinterpret_cast<const float4*>(res_s + base[q] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo));
+              }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+              for (int i = 0; i < TN; ++i) {
+                if (live[q] && cok[i]) {
+                  const uint32_t oi = base[q] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo);
+                  float v[4];
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) v[e] = outv(i, j, 4 * q + e, oi + (uint32_t)e);
+                  if (res_s) v[0] = __fadd_rn(v[0], rr[q][i].x), v[1] = __fadd_rn(v[1], rr[q][i].y), v[2] = __fadd_rn(v[2], rr[q][i].z), v[3] = __fadd_rn(v[3], rr[q][i].w);
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) v[e] = (relu && v[e] < 0.f) ? 0.f : v[e];
+                  *reinterpret_cast<float4*>(out_s + oi) = make_float4(v[0], v[1], v[2], v[3]);
+                }
+              }
+            }
+          }
+        } else
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
-          uint32_t base[8];
-          bool live[8];
-          float2 rr[8][TN];
+          uint32_t base[16];
+          bool live[16];
+          float rr[16][TN];
 #pragma unroll
-          for (int r2 = 0; r2 < 8; ++r2) {
-            const int r = 2 * r2, row = (r & 3) + 8 * (r >> 2) + 4 * lh;   // even
+          for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
             int bb, hh, ww;
-            live[r2] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (ww == 0; column + 1 is the same image's second pixel)
-            base[r2] = live[r2] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo + hh * a.Wo + ww) : 0u;
+            live[r] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);
+            base[r] = live[r] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo + hh * a.Wo + ww) : 0u;  // channel n0 of this pixel
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
-              rr[r2][i] = make_float2(0.f, 0.f);
-              if (res_s && live[r2] && cok[i]) rr[r2][i] = *reinterpret_cast<const float2*>(res_s + base[r2] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo));
+              rr[r][i] = 0.f;
+              if (res_s && live[r] && cok[i]) rr[r][i] = res_s[base[r] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo)];
             }
           }
 #pragma unroll
-          for (int r2 = 0; r2 < 8; ++r2) {
-            const int r = 2 * r2;
+          for (int r = 0; r < 16; ++r) {
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
-              if (live[r2] && cok[i]) {
-                const uint32_t oi = base[r2] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo);
-                float v0 = outv(i, j, r, oi), v1 = outv(i, j, r + 1, oi + 1u);
-                if (res_s) v0 = __fadd_rn(v0, rr[r2][i].x), v1 = __fadd_rn(v1, rr[r2][i].y);
-                v0 = (relu && v0 < 0.f) ? 0.f : v0, v1 = (relu && v1 < 0.f) ? 0.f : v1;
-                *reinterpret_cast<float2*>(out_s + oi) = make_float2(v0, v1);
+              if (live[r] && cok[i]) {
+                const uint32_t oi = base[r] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo);
+                float v = outv(i, j, r, oi);
+                if (res_s) v = __fadd_rn(v, rr[r][i]);
+                v = (relu && v < 0.f) ? 0.f : v;
+                out_s[oi] = v;
               }
             }
           }
         }
-      } else if (!pix && !a.row_taps && HoWo == 4 && t_R == a.Ho && t_Wt == a.Wo && (out_mis & 15u) == 0) {
-        // Tiles of whole four-pixel images: columns 4i .. 4i + 3 are one image's plane -- 16 contiguous bytes per channel.
-#pragma unroll
-        for (int j = 0; j < TM; ++j) {
-          uint32_t base[4];
-          bool live[4];
-          float4 rr[4][TN];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int row = 8 * q + 4 * lh;   // a multiple of 4
-            int bb, hh, ww;
-            live[q] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);   // (pixel 0 of image bb)
-            base[q] = live[q] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo) : 0u;
-#pragma unroll
-            for (int i = 0; i < TN; ++i) {
-              rr[q][i] = make_float4(0.f, 0.f, 0.f, 0.f);
-              if (res_s && live[q] && cok[i]) rr[q][i] = *reinterpret_cast<const float4*>(res_s + base[q] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo));
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int i = 0; i < TN; ++i) {
-              if (live[q] && cok[i]) {
-                const uint32_t oi = base[q] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo);
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = outv(i, j, 4 * q + e, oi + (uint32_t)e);
-                if (res_s) v[0] = __fadd_rn(v[0], rr[q][i].x), v[1] = __fadd_rn(v[1], rr[q][i].y), v[2] = __fadd_rn(v[2], rr[q][i].z), v[3] = __fadd_rn(v[3], rr[q][i].w);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = (relu && v[e] < 0.f) ? 0.f : v[e];
-                *reinterpret_cast<float4*>(out_s + oi) = make_float4(v[0], v[1], v[2], v[3]);
-              }
-            }
-          }
-        }
-      } else
-#pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        uint32_t base[16];
-        bool live[16];
-        float rr[16][TN];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-          int bb, hh, ww;
-          live[r] = cols.decode(wm * WTM + j * 32 + row, bb, hh, ww);
-          base[r] = live[r] ? (uint32_t)((bb * a.Co + g * a.Cog + n0) * HoWo + hh * a.Wo + ww) : 0u;  // channel n0 of this pixel
-#pragma unroll
-          for (int i = 0; i < TN; ++i) {
-            rr[r][i] = 0.f;
-            if (res_s && live[r] && cok[i]) rr[r][i] = res_s[base[r] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo)];
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-#pragma unroll
-          for (int i = 0; i < TN; ++i) {
-            if (live[r] && cok[i]) {
-              const uint32_t oi = base[r] + (uint32_t)(((wn * TN + i) * 32 + li) * HoWo);
-              float v = outv(i, j, r, oi);
-              if (res_s) v = __fadd_rn(v, rr[r][i]);
-              v = (relu && v < 0.f) ? 0.f : v;
-              out_s[oi] = v;
-            }
-          }
-        }
+      }
+      if constexpr (!CHAIN) break;
+      else {
+        if (ck + 1 >= chain_n) break;
+        chain_next(ck + 1);
       }
     }
   }
@@ -1503,6 +1585,25 @@ __global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdAr
     dbg_[256 + 4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
     dbg_[256 + 4 * blockIdx.x + 2] = __builtin_amdgcn_s_memtime() - dbg_[256 + 4 * blockIdx.x + 2];
   }
+}
+
+template <int BN, int BM, int NP, int NPW, int XM, bool FLIP = false, bool INJ = false>
+__global__ __launch_bounds__(256 + 64 * NPW) void fused_split_kernel(const FwdArgs a) {
+  if constexpr (XM == 1 && !FLIP) {  // one-pixel tiles: a body of their own (above)
+    static_assert(BM == 128 && NPW == 8, "the tile of the 1x1 planes");
+    int tap1;
+    if (one_pixel_tile(a, &tap1)) {  // launch-uniform
+      split_one_pixel_tile<BN, NP, NPW, INJ>(a, tap1);
+      return;
+    }
+  }
+  split_tile_body<BN, BM, NP, NPW, XM, FLIP, INJ, false>(a, nullptr);
+}
+
+// A chain of tab.n layers of the geometry in `a` as one launch (split_tile_body's CHAIN form; bt_fused_split_chain.hip plans and launches it).
+template <int BN, int BM, int NP, int NPW, int XM>
+__global__ __launch_bounds__(256 + 64 * NPW) void fused_split_chain_kernel(const FwdArgs a, const ChainTab tab) {
+  split_tile_body<BN, BM, NP, NPW, XM, false, false, true>(a, &tab);
 }
 
 }  // namespace bt

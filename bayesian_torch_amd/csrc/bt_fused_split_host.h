@@ -245,4 +245,56 @@ static int split_plan(FwdArgs& a, int mode, int* bm_out, int* xm_out) {
   return BT_OK;
 }
 
+// ---------------------------------------------------------------------------- chains of same-shape layers
+// Can the n layers m[0..n) -- each as bt::run fills it for a launch of its own, in execution order -- run as ONE launch of the chain
+// kernel (bt_fused_split.h, CHAIN)? Every member is planned by split_plan exactly as its own launch would be, so a chained layer
+// computes what it computes alone; the chain needs every plan to be the same whole-image 64 x 512 tile, member k to read what member
+// k - 1 wrote, and no buffer to overlap another. BT_OK: m[k] hold their plans and *xm_out the common x fetch mode. 1: not a chain (a
+// refusal is never an error: the caller launches the layers one by one).
+static inline bool chain_overlap(const void* p, long long pn, const void* q, long long qn) {   // byte ranges [p, p + pn) and [q, q + qn)
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + (uintptr_t)qn && b < a + (uintptr_t)pn;
+}
+static int split_chain_plan(int n, FwdArgs* m, int mode, int* xm_out) {
+  if (n < 1 || n > kChainMax || mode != 0) return 1;   // the exact split alone
+  int xm0 = 0;
+  for (int k = 0; k < n; ++k) {
+    FwdArgs& a = m[k];
+    // what launch_split_one asks of the general kernel's launches, and what only single launches do: a KL sweep, a pool, supplied draws
+    if (!packed_ok(a) || a.eps_w || a.eps_b || a.sign_in || a.sign_out || a.updil || a.dwin || a.lowrank || a.ep_pool || a.do_kl || a.kl_out) return 1;
+    if (a.Cig <= 4 || (a.Cig & 7) || a.pixel_major || a.HoWo <= 1 || a.H * a.W <= 1 || (a.KH == 1 && a.KW == 1)) return 1;   // (stems, one-pixel maps and 1x1 kernels have kernels of their own)
+    if (a.G != 1 || a.SH != 1 || a.SW != 1) return 1;
+    if (!a.out_vec4 && a.HoWo <= 4) return 1;   // the scalar output stage: not in the chain kernel (bt_fused_split.h, staged_out)
+    int bm, xm;
+    if (split_plan<false>(a, mode, &bm, &xm)) return 1;
+    if (bm != 512 || (xm != 3 && xm != 0) || a.n_tiles != 1 || a.t_R != a.Ho || a.t_Wt != a.Wo || a.row_taps || a.bn32) return 1;
+    if (k == 0) { xm0 = xm; continue; }
+    const FwdArgs& f = m[0], &p = m[k - 1];
+    if (xm != xm0 || a.t_NI != f.t_NI || a.n_bt != f.n_bt || a.m_tiles != f.m_tiles || a.total_blocks != f.total_blocks || a.S != f.S || a.B != f.B ||
+        a.H != f.H || a.W != f.W || a.Ho != f.Ho || a.Wo != f.Wo)
+      return 1;
+    // one geometry: the workgroup decodes it once (the shapes, the window, the output layout)
+    if (a.Ci != f.Ci || a.Co != f.Co || a.Cig != p.Cog || a.KH != f.KH || a.KW != f.KW || a.PH != f.PH || a.PW != f.PW || a.DH != f.DH || a.DW != f.DW ||
+        a.out_vec4 != f.out_vec4 || a.x_flat != f.x_flat || a.x_elems != f.x_elems || a.out_elems != f.out_elems || a.seed_lo != f.seed_lo ||
+        a.seed_hi != f.seed_hi || a.sample0 != f.sample0 || a.dbg != f.dbg)
+      return 1;
+    if (a.x != p.out || a.x_sample_stride != p.out_elems) return 1;   // member k reads what member k - 1 wrote, sample by sample
+  }
+  // No two of {chain input, outs} overlap; a residual is the chain input, something outside the chain, or exactly an EARLIER member's out.
+  const long long xin = 4 * ((long long)(m[0].S - 1) * m[0].x_sample_stride + m[0].x_elems), on = 4 * (long long)m[0].S * m[0].out_elems;
+  for (int k = 0; k < n; ++k) {
+    if (chain_overlap(m[0].x, xin, m[k].out, on)) return 1;
+    for (int j = 0; j < k; ++j)
+      if (chain_overlap(m[j].out, on, m[k].out, on)) return 1;
+    if (!m[k].ep_res) continue;
+    const long long rn = 4 * ((long long)(m[k].S - 1) * m[k].ep_res_stride + m[k].out_elems);
+    for (int j = 0; j < n; ++j) {
+      if (!chain_overlap(m[k].ep_res, rn, m[j].out, on)) continue;
+      if (j >= k || m[k].ep_res != m[j].out || m[k].ep_res_stride != m[j].out_elems) return 1;
+    }
+  }
+  *xm_out = xm0;
+  return BT_OK;
+}
+
 }  // namespace bt

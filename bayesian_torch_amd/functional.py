@@ -123,6 +123,11 @@ def _pack_supplied_draw(tens, flip, S, x_elems, n_so, R, state):
 
 def _epilogue(tens, out, S, relu, pool):
     """The fused output stage as a bt_epilogue reference, or None when the launch has none."""
+    ep = _epilogue_struct(tens, out, S, relu, pool)
+    return None if ep is None else C.byref(ep)
+
+
+def _epilogue_struct(tens, out, S, relu, pool):
     scale, shift, res = tens["post_scale"], tens["post_shift"], tens["residual"]
     if scale is None and res is None and not relu and not pool:
         return None
@@ -134,7 +139,7 @@ def _epilogue(tens, out, S, relu, pool):
             raise RuntimeError(f"residual has {res.numel()} elements, out has {out.numel()} (S={S})")
     if scale is not None and (scale.numel() != Co or shift is None or shift.numel() != Co):
         raise RuntimeError("post_scale / post_shift must both have Co elements")
-    return C.byref(_lib.bt_epilogue(_lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res), rstride, 1 if relu else 0, 1 if pool else 0))
+    return _lib.bt_epilogue(_lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res), rstride, 1 if relu else 0, 1 if pool else 0)
 
 
 def _f32_on(dev, tens):
@@ -243,6 +248,65 @@ def _fused_forward(x, mu_w, rho_w, mu_b=None, rho_b=None, *, flip=False, conv=No
             return None
         _lib.check(rc)
     return out, kl
+
+
+def fused_chain_forward(x, members, *, S=1, shared_x=True, outs=None):
+    """A chain of Conv2dReparameterization layers of one shape as ONE launch (bt_reparam_conv2d_chain_fwd): member k + 1 convolves what
+    member k wrote. x: the chain's input, [B, Ci, H, W] or S stacked batches (``shared_x`` False). members: dicts, in execution order, of
+    what ``fused_forward`` takes per layer -- mu_w, rho_w, conv, packed=(mu_packed, sigma_packed), seed, call, layer_id, and optionally
+    mu_b, rho_b, sample0, call_base, post_scale, post_shift, relu, residual. A member's residual is None, a tensor, the string "input"
+    (the chain's input) or the index of an EARLIER member (that member's out). On-chip draws only; no KL (the pack check produces it).
+    outs: the result tensors to write ([S * B, Co, Ho, Wo] each), else fresh ones.
+    Returns the members' outs, bit for bit what the calls one by one give -- or None when the library declines (the shapes are not a
+    chain it runs): nothing was launched, and the caller makes the calls."""
+    x = _lib.dev_f32(x, "input")
+    dev, L = x.device, _lib.lib()
+    if not 1 <= len(members) <= _lib.CHAIN_MAX:
+        return None
+    # What the library's planner refuses from the shapes alone (split_chain_plan: one 64-channel tile, groups 1, stride 1, a window larger
+    # than 1x1, whole images of at most 512 positions in a tile) is refused here, BEFORE any result is allocated: a stage of large maps
+    # never holds n full activations for a chain that cannot be. What is left to the library -- the tile split_plan picks, alignment,
+    # overlap -- is decided with the results allocated; forward_chain remembers a refusal, so that happens once.
+    if outs is None:
+        for m in members:
+            w, cv = m["mu_w"], m["conv"]
+            if (w.dim() != 4 or w.shape[0] > 64 or cv["groups"] != 1 or tuple(cv["stride"]) != (1, 1) or tuple(w.shape[2:]) == (1, 1) or x.dim() != 4
+                    or math.prod(conv_out_hw(x.shape[2], x.shape[3], w.shape[2], w.shape[3], *cv["stride"], *cv["padding"], *cv["dilation"])) > 512):
+                return None
+    arr = (_lib.bt_chain_member * len(members))()
+    keep, res_outs, cur, cur_shared = [], [], x, shared_x
+    for k, m in enumerate(members):
+        res = m.get("residual")
+        if isinstance(res, str):
+            if res != "input":
+                raise ValueError("a member's residual is None, a tensor, \"input\" or an earlier member's index")
+            res = x
+        elif isinstance(res, int) and not isinstance(res, bool):
+            if not 0 <= res < k:
+                raise ValueError("a member's residual index names an EARLIER member")
+            res = res_outs[res]
+        tens = dict(mu_w=m["mu_w"], rho_w=m["rho_w"], mu_b=m.get("mu_b"), rho_b=m.get("rho_b"), post_scale=m.get("post_scale"), post_shift=m.get("post_shift"),
+                    residual=res, mu_packed=m["packed"][0], sigma_packed=m["packed"][1])
+        _f32_on(dev, tens)
+        B, geom, x_elems, tail = _geometry(cur, tens["mu_w"], m["conv"], S, cur_shared)
+        if m["conv"].get("updil") is not None or m["conv"].get("dwin") is not None:
+            return None
+        out = torch.empty((S * B,) + tail, dtype=torch.float32, device=dev) if outs is None else outs[k]
+        P = _lib.bt_params(tens["mu_w"].data_ptr(), tens["rho_w"].data_ptr(), _lib.ptr(tens["mu_b"]), _lib.ptr(tens["rho_b"]), None, None, None, None,
+                           tens["mu_packed"].data_ptr(), tens["sigma_packed"].data_ptr(), _lib.PRIOR_NORMAL, 0)
+        D = _lib.bt_draws(None, None, None, None, _rng(m["seed"], m["call"], m["layer_id"], m.get("sample0", 0), m.get("call_base")))
+        E = _epilogue_struct(tens, out, S, bool(m.get("relu")), False)
+        ep = C.pointer(E) if E is not None else None
+        arr[k] = _lib.bt_chain_member(C.pointer(geom), cur.data_ptr(), 0 if cur_shared else x_elems, C.pointer(P), C.pointer(D), ep, out.data_ptr(), None)
+        keep.append((tens, geom, P, D, E, cur))
+        res_outs.append(out)
+        cur, cur_shared = out, False
+    with _lib.on(dev):
+        rc = L.bt_reparam_conv2d_chain_fwd(len(members), arr, S, _lib.stream_ptr(dev))
+    if rc == _lib.CHAIN_DECLINED:
+        return None
+    _lib.check(rc)
+    return res_outs
 
 
 def _rng(seed, call, layer_id, sample0, call_base):

@@ -44,6 +44,15 @@ class _Basic(nn.Module):
             return _qact().add_relu(y, skip)
         return self.relu(y + skip)
 
+    def chain_members(self):
+        """The fused forward above as a run of layers, each reading what the one before wrote -- what ``ResNet._run_stage`` may hand to
+        ``FusedBayesLayer.forward_chain`` in this block's place: [(layer, residual)], residual None, "input" (the block's input) or the index
+        of an earlier layer of the list. None when the block is not that: not fused, a shortcut that computes, u8 carriers, hooks on it."""
+        if (not getattr(self, "fused", False) or self.downsample is not None or getattr(self, "u8", False) or self._forward_hooks
+                or self._forward_pre_hooks):
+            return None
+        return [(self.conv1, None), (self.conv2, "input")]
+
 
 class _Bottle(nn.Module):
     expansion = 4
@@ -98,12 +107,43 @@ class ResNet(nn.Module):
         mods += [block(cout, planes, 1, None) for _ in range(n - 1)]
         return nn.Sequential(*mods)
 
+    @staticmethod
+    def _run_stage(stage, x):
+        """A stage of the fused model (fuse_inference). Consecutive blocks that describe themselves as a run of same-shape layers
+        (``chain_members``: identity-shortcut basic blocks) go two blocks (four convs) at a time through
+        ``FusedBayesLayer.forward_chain``: one launch where the shapes allow it (CIFAR-sized layer1). Anything else, and whatever the chain
+        helper passes up (hooks on a member, gradients, no MC context, BT_CHAIN=0, shapes the library declines ...), runs block by block:
+        the same results. Hooks on the stage, or registered for every module, see each call: then the stage runs as the Sequential it is."""
+        from torch.nn.modules import module as _m
+        from ..layers._fused import FusedBayesLayer
+        if stage._forward_hooks or stage._forward_pre_hooks or _m._global_forward_hooks or _m._global_forward_pre_hooks:
+            return stage(x)
+        blocks, i = list(stage), 0
+        while i < len(blocks):
+            members, used = [], 0
+            for b in blocks[i:i + 2]:
+                desc = b.chain_members() if hasattr(b, "chain_members") else None
+                if desc is None:
+                    break
+                base = len(members)      # the block's "input" is the run's input, or what the block before it wrote
+                members += [(m, ("input" if base == 0 else base - 1) if r == "input" else r if r is None else base + r) for m, r in desc]
+                used += 1
+            if members:
+                outs = FusedBayesLayer.forward_chain([m for m, _ in members], x, [r for _, r in members])
+                if outs is not None:
+                    x, i = outs[-1], i + used
+                    continue
+            x, i = blocks[i](x), i + 1
+        return x
+
     def forward(self, x):
         if getattr(self, "fused", False):
             x = self.conv1(x)  # bn1 / relu / maxpool live in its output stage
+            for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
+                x = self._run_stage(stage, x)
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+            x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         if x.shape[-2:] != (1, 1):     # (CIFAR-sized inputs end on 1x1 maps: the mean of one element is that element -- no launch)
             x = self.avgpool(x)
         return self.fc(torch.flatten(x, 1))

@@ -29,6 +29,21 @@ import os as _os
 _NO_SEG_CACHE = bool(_os.environ.get("BT_NO_SEG_CACHE"))   # A/B knob of the eager path's host time (tools/profile_eager.py)
 BT_FUSED_KL = bool(_os.environ.get("BT_FUSED_KL"))         # A/B knob: inference forwards sweep their own KL instead of the pack check
 MAX_TAPS = 128     # kernel positions (kh * kw of the Conv2d launch) the fused kernels and bt_pack_sync support (kMaxTaps)
+# Runs of same-shape layers as one launch (FusedBayesLayer.forward_chain); BT_CHAIN=0 / set_chain(False): never. Off, too, in the counter
+# passes bench.py --full starts of itself (BT_BENCH_CHILD): its roofline leg hooks every layer and so times per-layer launches, and the
+# measured traffic it sets against them has to come from the same launches.
+_chain = [_os.environ.get("BT_CHAIN", "1") != "0" and not _os.environ.get("BT_BENCH_CHILD")]
+
+
+def set_chain(on):
+    """Switch the chained launches (``FusedBayesLayer.forward_chain``) on or off; returns the previous setting. Off, every layer is its
+    own launch: the same results (tests, A/B measurements)."""
+    prev, _chain[0] = _chain[0], bool(on)
+    return prev
+
+
+def chain_enabled():
+    return _chain[0]
 
 
 class FusedBayesLayer(BaseVariationalLayer_, CalibrationMixin):
@@ -357,6 +372,65 @@ class FusedBayesLayer(BaseVariationalLayer_, CalibrationMixin):
         if collect:
             ctx.kls.append(kl)
         return (out, kl) if return_kl else out
+
+    # ------------------------------------------------------------------ chains
+    _chain_declined = set()     # what the library declined to chain, by everything its answer depends on in forward_chain (class-level)
+
+    @classmethod
+    def forward_chain(cls, layers, x, residuals):
+        """``layers`` -- Conv2dReparameterization modules of one shape, each convolving what the one before wrote -- as ONE launch
+        (``functional.fused_chain_forward``), with the bookkeeping of their forwards one by one: the same call coordinates in the same
+        order, the pack check's KL terms appended to the context in that order, every member's ``_last``. residuals[k]: None, "input" (the
+        chain's input) or the index of an earlier member. Returns the members' outputs -- or None, with nothing launched and no
+        coordinate consumed, when the chain does not apply: chaining off, gradients on, no ``mc_samples`` context, draws that are not made
+        on chip, a member of another kind or with forward hooks, a KL term the pack check did not produce, shapes the library declines.
+        The caller then calls the layers one by one."""
+        ctx = mc.current()
+        if (not _chain[0] or ctx is None or torch.is_grad_enabled() or rng.get_mode() == "torch" or not 2 <= len(layers) <= _lib.CHAIN_MAX
+                or not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4):
+            return None
+        for m in layers:
+            if (not isinstance(m, FusedBayesLayer) or m._kind != "conv" or m._flip or getattr(m, "_one_d", False) or type(m)._forward is not FusedBayesLayer._forward
+                    or type(m)._pack_source is not FusedBayesLayer._pack_source or m.inject_draw is not None or m.quant_prepare or m.post_pool
+                    or m._forward_hooks or m._forward_pre_hooks or isinstance(m.padding, str)):
+                return None
+            collect = ctx.collect_kl and not m._kl_muted
+            if collect and (BT_FUSED_KL or id(m) not in ctx.synced or id(m) not in ctx.sync_kl or m._pack is None or m._pack_force):
+                return None     # (this member's forward would sweep its KL itself: a launch of its own)
+        x = x.contiguous()
+        if x.shape[0] not in (ctx.batch, ctx.S * ctx.batch) or x.shape[1] != layers[0].in_channels:
+            return None
+        shared0 = x.shape[0] == ctx.batch
+        # what the library's answer depends on here: the shapes, and -- not geometry -- the contraction mode and the input's alignment (the
+        # members' outs are fresh allocations: aligned, and never overlapping)
+        key = (tuple(x.shape), ctx.S, shared0, tuple(residuals), int(_lib.lib().bt_get_contraction()), x.data_ptr() % 16,
+               tuple((tuple(m._w("mu").shape), tuple(sorted((k, v) for k, v in m._conv_desc().items())), m.mu_bias is not None) for m in layers))
+        if key in cls._chain_declined:
+            return None
+        call0, kls0 = rng.peek_call(), {id(m): ctx.sync_kl.get(id(m)) for m in layers}
+        B, members, frames = ctx.batch, [], []
+        for k, m in enumerate(layers):
+            collect = ctx.collect_kl and not m._kl_muted
+            S, shared, coords = m._call_coords(ctx, x.shape[0] if k == 0 else ctx.S * B)
+            mu_pk, sg_pk, kl = m._packed_kl(collect)
+            members.append(dict(mu_w=m._w("mu"), rho_w=m._w("rho"), mu_b=m.mu_bias, rho_b=m.rho_bias, conv=m._conv_desc(), packed=(mu_pk, sg_pk),
+                                seed=coords.seed, call=coords.call, layer_id=coords.layer_id, sample0=coords.sample0, call_base=coords.call_base,
+                                post_scale=m.post_scale, post_shift=m.post_shift, relu=m.post_relu, residual=residuals[k]))
+            frames.append((collect, kl, S, shared, coords))
+        outs = F.fused_chain_forward(x, members, S=ctx.S, shared_x=shared0)
+        if outs is None:      # declined: nothing ran -- give the coordinates and the KL terms back, remember the shapes
+            rng.set_call(call0)
+            ctx.sync_kl.update({i: k for i, k in kls0.items() if k is not None})
+            cls._chain_declined.add(key)
+            return None
+        kernel, launch = _lib.lib().bt_last_kernel_name().decode(), _lib.last_launch_info()
+        for k, (m, (collect, kl, S, shared, coords)) in enumerate(zip(layers, frames)):
+            xin = x if k == 0 else outs[k - 1]
+            m._last = dict(draw=None, rng=coords, S=S, kernel=kernel, launch=dict(launch), shared_x=shared, residual=residuals[k] is not None, fused_kl=False,
+                           x_shape=(B,) + tuple(xin.shape[1:]), out_shape=(B,) + tuple(outs[k].shape[1:]))
+            if collect:
+                ctx.kls.append(kl)
+        return outs
 
     # ------------------------------------------------------------------ draws
     def _draw_torch(self, x, S, B, conv):

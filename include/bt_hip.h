@@ -172,6 +172,30 @@ int bt_reparam_conv2d_fwd(const bt_conv2d_geom *g, int32_t S,
                           float *out /* [S][B][Co][Ho][Wo] */, float *kl_out,
                           void *workspace, size_t workspace_bytes, bt_stream_t stream);
 
+/* A CHAIN of n <= BT_CHAIN_MAX Conv2dReparameterization layers of one shape -- member k + 1 convolves what member k wrote, as in the
+ * identity-shortcut blocks of a ResNet stage -- as ONE launch: every workgroup walks the n layers over its own images. m[k] is the call
+ * bt_reparam_conv2d_fwd would get for member k (its geometry, x, parameters, draws, epilogue, out), in execution order; the results are
+ * bit for bit those of the n calls. The launch is taken only when every member, planned exactly as its own call would be, gets the same
+ * tile of whole images and all of a layer's channels (64 channels x 512 positions: small maps, Co <= 64, groups 1, stride 1, a window
+ * larger than 1x1), with on-chip draws, packed parameters, the automatic contraction mode, no fused max-pool and no KL sweep
+ * (kl_out NULL); m[k].x is m[k - 1].out with x_sample_stride = one sample's out; a residual is the chain's input, exactly an earlier
+ * member's out, or a buffer outside the chain; and no two of {m[0].x, the outs} overlap. Returns BT_OK, an error (< 0), or
+ * BT_CHAIN_DECLINED when the members are valid but not such a chain: NOTHING is launched then, and the caller makes the n calls.
+ * bt_last_kernel_name / bt_last_launch_info describe the chain launch (the tile geometry every member shares). */
+#define BT_CHAIN_MAX 4
+#define BT_CHAIN_DECLINED 1
+typedef struct bt_chain_member {
+  const bt_conv2d_geom *g;
+  const float *x;
+  int64_t x_sample_stride;
+  const bt_params *p;
+  const bt_draws *d;
+  const bt_epilogue *ep; /* or NULL */
+  float *out;            /* [S][B][Co][Ho][Wo] */
+  float *kl_out;         /* NULL in a chain (a member that asks for its KL is declined) */
+} bt_chain_member;
+int bt_reparam_conv2d_chain_fwd(int32_t n, const bt_chain_member *m, int32_t S, bt_stream_t stream);
+
 /* The same two convolutions over an INPUT-DILATED image: the forward of a transposed convolution without its zero-upsampled copy.
  * x is the real input [B][Ci][g->H][g->W]; the kernels convolve the virtual image of
  *     Hv = (H - 1) * uh + 1 + lo_h + hi_h,   Wv = (W - 1) * uw + 1 + lo_w + hi_w
